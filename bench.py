@@ -9,6 +9,11 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--buffers 4096] [--size 1048576]
                     [--scaling strong|weak] [--level 1] [--foreign LEVEL] [--uncompress-only]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (round trip verified), times --steps steps and prints the line; --dump-outputs writes
+what the last timed step computed.  Everything else the bench measures or checks -- 64 streams against the oracle, the
+parallel-parse leg, the transfer leg, BASELINE configs 2-5, the CPU baseline -- runs after the headline with --full.
 
 One process per GPU.  N > 1 is launched by `python -m torch.distributed.run` (the driver does
 that itself; a plain `python bench.py --gpus N` re-executes itself under it) and fails loudly
@@ -18,7 +23,7 @@ zippy.nim:11-16):
       by contiguous index ranges (zippy_amd/sharding.py shard_range) -- BASELINE.json's
       "4096 x 1 MiB on 8 GPUs";
   --scaling weak: every rank runs --buffers buffers of its own.
-The timed region has no data-path collective (barrier + max-over-ranks only).  For N > 1 a
+The timed region has no data-path collective (barrier + max-over-ranks only).  For N > 1 and --full a
 separate, separately reported leg moves the batch from and to rank 0 over RCCL
 (scatter_fixed / gather_variable / scatter_variable / gather_fixed): `transfer`.
 Prints ONE JSON line on rank 0.
@@ -681,6 +686,58 @@ def pp_fields(pp, N, comp_rank_exact, roof):
     }
 
 
+DUMP_SEED = 0x44554D50  # "DUMP": the samples --dump-outputs takes are the same from run to run
+
+
+def dump_outputs(out_dir, torch, d_comp, d_back, n, size, slot, cplan, uplan, do_c, do_u):
+    """--dump-outputs: what the last timed step left for a caller of the timed path, as .npy files (float64 / float32,
+    about 40 MB at BASELINE's sizes) by which two builds can be compared output for output.
+      compress (timed):   compressed_lengths, compress_status, compressed_crc32 (zlib.crc32 of every stream, so
+                          every stream byte counts), compressed_sample (the bytes of a seeded sample of streams, back
+                          to back, <= 4 MiB of them) and compressed_sample_index (which streams);
+      uncompress (timed): uncompressed_lengths, uncompress_status, uncompressed_sample (the output's bytes at 2 Mi seeded
+                          positions, in order) and uncompressed_sample_pos."""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    arrays = {}
+    if do_c:
+        clens, csts = cplan.results()
+        arrays["compressed_lengths"] = np.array(clens, dtype=np.float64)
+        arrays["compress_status"] = np.array(csts, dtype=np.float64)
+        rows = d_comp.view(n, slot)
+        width = max(clens) if n else 0
+        crcs = []
+        chunk = max(1, (256 << 20) // max(1, width))  # rows per device-to-host copy
+        with ThreadPoolExecutor(8) as ex:  # (zlib releases the GIL)
+            for lo in range(0, n, chunk):
+                host = rows[lo:lo + chunk, :width].cpu().numpy()
+                crcs += ex.map(lambda i, host=host, lo=lo: zlib.crc32(host[i - lo, :clens[i]]),
+                               range(lo, min(n, lo + chunk)))
+        arrays["compressed_crc32"] = np.array(crcs, dtype=np.float64)
+        pick, budget = [], 4 << 20
+        for i in sorted(rng.permutation(n)[:8].tolist()):
+            if clens[i] <= budget:
+                pick.append(i)
+                budget -= clens[i]
+        arrays["compressed_sample_index"] = np.array(pick, dtype=np.float64)
+        arrays["compressed_sample"] = (torch.cat([rows[i, :clens[i]] for i in pick]).cpu().numpy().astype(np.float32)
+                                       if pick else np.zeros(0, np.float32))
+    if do_u:
+        ulens, usts = uplan.results()
+        arrays["uncompressed_lengths"] = np.array(ulens, dtype=np.float64)
+        arrays["uncompress_status"] = np.array(usts, dtype=np.float64)
+        pos = np.unique(rng.integers(0, n * size, min(n * size, 2 << 20), dtype=np.int64))
+        arrays["uncompressed_sample_pos"] = pos.astype(np.float64)
+        arrays["uncompressed_sample"] = (d_back[torch.from_numpy(pos).to(d_back.device)].cpu().numpy()
+                                         .astype(np.float32))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def relaunch_under_torchrun(args):
     import socket
     import subprocess
@@ -713,14 +770,20 @@ def main():
     ap.add_argument("--uncompress-only", action="store_true",
                     help="BASELINE config 3: time only the uncompress pass (inflate + CRC-32)")
     ap.add_argument("--compress-only", action="store_true", help="BASELINE configs 2/4: time only the compress pass")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the comparison of 64 streams with the "
+                         "oracle's, the parallel-parse leg, the RCCL transfer leg (N > 1), BASELINE configs 2-5 and "
+                         "the CPU baseline (the --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-parallel-parse", action="store_true",
-                    help="skip the second timing with the opt-in parallel BestSpeed parse")
+                    help="with --full: skip the second timing with the opt-in parallel BestSpeed parse")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip BASELINE configs 2-5 (run after the headline at N=1 with the default workload)")
-    ap.add_argument("--no-transfer", action="store_true", help="skip the RCCL scatter/gather leg (N > 1)")
+                    help="with --full: skip BASELINE configs 2-5 (run after the headline at N=1 with the default workload)")
+    ap.add_argument("--no-transfer", action="store_true", help="with --full: skip the RCCL scatter/gather leg (N > 1)")
     ap.add_argument("--no-parity-sample", action="store_true",
-                    help="skip the comparison of 64 of the streams with the oracle's (outside the timed region)")
+                    help="with --full: skip the comparison of 64 of the streams with the oracle's (outside the timed region)")
     args = ap.parse_args()
     if args.foreign is not None:
         args.uncompress_only = True
@@ -827,7 +890,7 @@ def main():
     # ---- the headline carries its own parity evidence: a sample of the streams about to be timed against the
     # oracle's compress(), byte for byte (the checker, outside the timed region; rank 0's shard) ----
     parity_sample = None
-    if args.foreign is None and rank == 0 and not args.no_parity_sample:
+    if args.full and args.foreign is None and rank == 0 and not args.no_parity_sample:
         import oracle
         pick = list(range(0, n, max(1, n // 64)))[:64]
         same = 0
@@ -862,6 +925,8 @@ def main():
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before anything else runs the plans: rank 0's shard)
+        dump_outputs(args.dump_outputs, torch, d_comp, d_back, n, size, slot, cplan, uplan, do_c, do_u)
     comp_all = comp_total
     if use_dist:
         t = torch.tensor([elapsed, t_comp, t_unc], device="cuda", dtype=torch.float64)
@@ -880,7 +945,7 @@ def main():
     # encoder contract (round trip exact, size within 2 % of zippy's).  `value` stays the
     # byte-identical parse.  Every rank, timed like the headline (barrier, max over ranks). ----
     pp = None
-    if do_c and do_u and args.foreign is None and args.level == 1 and not args.no_parallel_parse:
+    if args.full and do_c and do_u and args.foreign is None and args.level == 1 and not args.no_parallel_parse:
         import zlib
         eng.set_l1_parse(1)
         pstate = {}
@@ -932,7 +997,7 @@ def main():
 
     # ---- N > 1: the batch lives on rank 0 and comes home to rank 0 (RCCL over xGMI) ----
     transfer = None
-    if use_dist and scaling == "strong" and not args.no_transfer and do_c and do_u:
+    if args.full and use_dist and scaling == "strong" and not args.no_transfer and do_c and do_u:
         try:  # (a side measurement, never run on more than one GPU before the driver does: it must not cost the line)
             transfer = transfer_leg(torch, dist, sharding, synth, rank, world, args.buffers, size, slot, lo, hi,
                                     d_src, d_comp, d_back, cplan, uplan, stream, t_comp / args.steps,
@@ -1014,7 +1079,7 @@ def main():
                     and size == 1 << 20 and n >= 8)
         if pp:
             out.update(pp_fields(pp, N, comp_total, roof))
-        if headline and not args.no_configs:
+        if headline and args.full and not args.no_configs:
             # the other BASELINE configs, so that the driver's line carries all five
             cplan.close()
             uplan.close()
@@ -1028,7 +1093,7 @@ def main():
                 if e and full_ms and n == 8 * (n // 8):
                     e["perfect_eighth_ms"] = round(full_ms / 8.0, 3)
                     e["efficiency_vs_perfect_eighth"] = round(full_ms / 8.0 / e["ms_per_step"], 4)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             # every host core this process may run on (no cap); a repetition is >= 2 core-seconds of
             # work a core pair, i.e. ~ 32 MiB a thread, so that thread start-up and a straggler are
             # a few percent of it: ~ 20 s in all

@@ -95,7 +95,7 @@ def test_gpu_bench_under_torchrun_with_transfer_leg():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--buffers", "96", "--size", "262144", "--steps", "1", "--warmup", "1",
-           "--scaling", "strong", "--no-cpu-baseline"]
+           "--scaling", "strong", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

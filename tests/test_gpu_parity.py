@@ -274,10 +274,43 @@ def test_gpu_config4_whole_batch_on_one_gpu(eng):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--level", "-1", "--steps", "1",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["value"] > 0 and 2.4 < line["ratio"] < 2.9
+
+
+def test_gpu_bench_plain_run_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the headline only, --steps timed steps, and --dump-outputs writes what the last step
+    computed -- every stream's CRC-32 equals that of the oracle's stream, the sampled bytes are the oracle's and the
+    input's."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, size = 16, 1 << 20
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--buffers", str(n), "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert not {"configs", "cpu_baseline", "parallel_parse", "transfer"} & set(line) and line["parity_sample"] is None
+    files = sorted(tmp_path.glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    out = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    src = synth.gen_batch("mix", n, size)
+    want = [oracle.compress(b.tobytes(), 1, oracle.dfGzip, fname_len=0) for b in src]
+    assert out["compressed_lengths"].tolist() == [len(z) for z in want]
+    assert out["compressed_crc32"].tolist() == [zlib.crc32(z) for z in want]
+    assert not out["compress_status"].any() and not out["uncompress_status"].any()
+    pick = out["compressed_sample_index"].astype(np.int64)
+    assert len(pick) > 0
+    assert np.array_equal(out["compressed_sample"], np.frombuffer(b"".join(want[i] for i in pick), np.uint8))
+    assert out["uncompressed_lengths"].tolist() == [size] * n
+    pos = out["uncompressed_sample_pos"].astype(np.int64)
+    assert np.array_equal(out["uncompressed_sample"], src.reshape(-1)[pos])
 
 
 def test_gpu_config5_single_large_buffer(eng):

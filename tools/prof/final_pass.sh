@@ -14,11 +14,11 @@ mkdir -p profiles && cp $O/hbm_traffic.json profiles/hbm_traffic.json
 # scheduler / L2 counters per kernel (SQ_*, TCC_*: valu busy, lane utilisation, waits, L2 hit rate, requests by size)
 bash tools/prof/pmc_sq.sh ${T} 1024 > $O/${T}_pmc_sq.log 2>&1
 timeout 1200 python -m pytest tests -m gpu -q > $O/${T}_pytest_gpu.log 2>&1
-timeout 900 python bench.py --steps 10 --warmup 2 2>$O/${T}_bench.err | tail -1 > $O/${T}_bench.json
-timeout 600 python bench.py --level -1 --compress-only --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${T}_c4.json
-timeout 300 python bench.py --buffers 512 --level -1 --compress-only --steps 5 --warmup 1 --no-cpu-baseline --no-configs --no-parallel-parse 2>/dev/null | tail -1 > $O/${T}_c4share.json
+timeout 900 python bench.py --steps 10 --warmup 2 --full 2>$O/${T}_bench.err | tail -1 > $O/${T}_bench.json
+timeout 600 python bench.py --level -1 --compress-only --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/${T}_c4.json
+timeout 300 python bench.py --buffers 512 --level -1 --compress-only --steps 5 --warmup 1 --full --no-cpu-baseline --no-configs --no-parallel-parse 2>/dev/null | tail -1 > $O/${T}_c4share.json
 # one GPU's share of the batch when eight GPUs split it (strong scaling, 512 x 1 MiB)
-timeout 300 python bench.py --buffers 512 --steps 10 --warmup 2 --no-cpu-baseline --no-configs 2>/dev/null | tail -1 > $O/${T}_share512.json
+timeout 300 python bench.py --buffers 512 --steps 10 --warmup 2 --full --no-cpu-baseline --no-configs 2>/dev/null | tail -1 > $O/${T}_share512.json
 # the same two steps with the fragments as numbered in every run (ZH_L1_ORDER=0): what a plan's FIRST run costs, before
 # the matcher knows what its fragments cost (the lines above are steady state: the plans have run before)
 ZH_L1_ORDER=0 timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-configs --no-parallel-parse --no-parity-sample 2>/dev/null | tail -1 > $O/${T}_bench_first_run_order.json
@@ -42,7 +42,7 @@ timeout 300 python tools/kprof.py --foreign 6 --buffers 1024 > $O/${T}_kprof_for
 timeout 300 python tools/kprof.py --buffers 1024 > $O/${T}_kprof_exact.txt 2>&1   # (with the sub-phases of the Huffman replay)
 cd /tmp
 rm -rf /tmp/kt
-timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-configs > $O/${T}_rocprof_bench.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-configs > $O/${T}_rocprof_bench.log 2>&1
 cd $R
 python tools/rocpd_summary.py $(find /tmp/kt -name "*.db" | head -1) > $O/${T}_kernel_stats.csv 2>$O/${T}_summary.err
 tail -2 $O/${T}_pytest_gpu.log; for f in bench c4 share512; do echo "== $f"; cut -c1-600 $O/${T}_$f.json; done; head -14 $O/${T}_kernel_stats.csv

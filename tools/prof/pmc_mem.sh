@@ -6,7 +6,7 @@
 R=$(pwd); T=${1:-r06}; N=${2:-1024}; shift; shift
 O=$R/gpurun_out; mkdir -p $O/pmcm_$T
 export TMPDIR=/tmp
-B="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-parity-sample"
+B="python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-configs --no-parity-sample"
 declare -A CMD
 CMD[l1]="$B --buffers $N --compress-only --no-parallel-parse"
 CMD[l1p]="$B --buffers $N --compress-only"

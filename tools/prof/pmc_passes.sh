@@ -5,7 +5,7 @@
 #   bash tools/prof/pmc_passes.sh [workload ...]        (default: all)
 R=$(pwd); O=$R/gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
-B="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-parity-sample"
+B="python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-configs --no-parity-sample"
 declare -A CMD KNOWN ENVV
 CMD[headline]="$B";                                                                     KNOWN[headline]=$((4096*1048576))
 CMD[c2]="$B --buffers 1024 --size 65536 --compress-only --no-parallel-parse";          KNOWN[c2]=$((1024*65536))

@@ -10,7 +10,7 @@
 R=$(pwd); T=${1:-r05}; N=${2:-1024}; shift; shift
 O=$R/gpurun_out; mkdir -p $O/pmc_$T
 export TMPDIR=/tmp
-B="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-parity-sample"
+B="python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-configs --no-parity-sample"
 declare -A CMD
 CMD[headline]="$B --buffers $N"
 CMD[c4_share]="$B --buffers 512 --level -1 --compress-only --no-parallel-parse"

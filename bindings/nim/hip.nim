@@ -178,3 +178,35 @@ proc hipCreateZipArchive*(entries: OrderedTable[string, string]): string {.raise
   let st = zh_zip_create(engine(), paths[0].addr, pathLens[0].addr, contents[0].addr,
                          contentLens[0].addr, paths.len.csize_t, t, d, p.addr, n.addr)
   take(p, n, st)
+
+# ---- writing tarballs (src/zippy/tarballs_v1.nim) ----
+type
+  ZhTarNewEntry {.bycopy.} = object
+    path: cstring                       # not NUL-terminated: use pathLen
+    pathLen: csize_t
+    contents: pointer
+    len: csize_t
+    kind: char                          # '0' ekNormalFile, '5' ekDirectory
+    mtime: int64                        # lastModified.toUnix
+
+const ZH_TAR_PLAIN = -1.cint
+
+proc zh_tar_create_batch(ctx: ZhCtx, entries: ptr ZhTarNewEntry, first: ptr csize_t, nTar: csize_t,
+                         dataFormat, level: cint, dsts: ptr pointer, dstLens: ptr csize_t,
+                         statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipTarballImage*(entries: openArray[tuple[path, contents: string, kind: char, mtime: int64]],
+                      gzip: bool): string {.raises: [ZippyError].} =
+  ## writeTarball's `data` (tarballs_v1.nim:209-261), and with gzip its compress(data, DefaultCompression, dfGzip)
+  ## (:269), in one call: headers, padding and trailer are written on the device
+  var es = newSeq[ZhTarNewEntry](entries.len)
+  for i, e in entries:                 # insertion order
+    es[i] = ZhTarNewEntry(path: e.path.cstring, pathLen: e.path.len.csize_t,
+                          contents: (if e.contents.len > 0: e.contents[0].unsafeAddr else: nil),
+                          len: e.contents.len.csize_t, kind: e.kind, mtime: e.mtime)
+  var first = [0.csize_t, es.len.csize_t]
+  var p: pointer; var n: csize_t; var st: int32
+  let rc = zh_tar_create_batch(engine(), (if es.len > 0: es[0].addr else: nil), first[0].addr, 1,
+                               (if gzip: dfGzip.cint else: ZH_TAR_PLAIN), DefaultCompression.cint,
+                               p.addr, n.addr, st.addr)
+  take(p, n, if rc != 0: rc else: st.cint)

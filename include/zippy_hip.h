@@ -73,7 +73,11 @@ enum {
   ZH_ERR_ZIP_NAME = 33,           /* ziparchives.nim:506-511 empty / absolute / over-long path */
   ZH_ERR_TAR_HEADER_TYPE = 34,    /* tarballs.nim:119 */
   ZH_ERR_UNSAFE_PATH = 35,        /* internal.nim:294-302 verifyPathIsSafeToExtract */
-  ZH_ERR_TAR_NUMBER = 36          /* tarballs.nim:17-23 (octal field that is not octal) */
+  ZH_ERR_TAR_NUMBER = 36,         /* tarballs.nim:17-23 (octal field that is not octal) */
+  /* tarball writer (zh_tar_create_batch): the ZippyError raise sites of tarballs_v1.nim writeTarball */
+  ZH_ERR_TAR_EMPTY = 37,          /* tarballs_v1.nim:210-211 */
+  ZH_ERR_TAR_PATH = 38,           /* tarballs_v1.nim:218-222 (splitPath head >= 155 bytes) */
+  ZH_ERR_TAR_NAME = 39            /* tarballs_v1.nim:223-227 (splitPath tail >= 100 bytes) */
 };
 
 /* Engine context: one GPU, one HIP stream, reusable scratch. Thread-compatible
@@ -396,6 +400,41 @@ void zh_tar_close(zh_tar_reader *reader);
 size_t zh_tar_num_entries(const zh_tar_reader *reader);
 int zh_tar_entry_at(const zh_tar_reader *reader, size_t i, zh_tar_entry *out);
 const void *zh_tar_data(const zh_tar_reader *reader, size_t *len);
+
+/* Writing tarballs: writeTarball(tarball, path) -- tarballs_v1.nim:203-270 -- for n_tar in-memory
+ * tarballs at once, without the file write.  The host lays the images out and sends every entry's
+ * contents straight to its place in HBM; one kernel writes the 512-byte ustar headers, the zero
+ * padding and the 1024-byte trailers; for ZH_DF_GZIP the images are then compressed as one batch
+ * (compress(image, level, dfGzip), tarballs_v1.nim:269, FNAME as zh_set_gzip_fname_len says). */
+typedef struct zh_tar_new_entry { /* one TarballEntry of Tarball.contents (tarballs_v1.nim:8-15) */
+  const char *path;               /* the table key; '/' is the only separator (std/os splitPath on POSIX) */
+  size_t path_len;
+  const void *contents;           /* may be NULL when len == 0 */
+  size_t len;
+  char kind;                      /* '0' (ekNormalFile) or '5' (ekDirectory); a directory's contents are written too */
+  int64_t mtime;                  /* lastModified.toUnix() */
+} zh_tar_new_entry;
+enum { ZH_TAR_PLAIN = -1 };       /* data_format: the .tar image itself */
+/* Tarball t is entries[first[t] .. first[t+1]) in insertion order (first has n_tar + 1 elements, non-decreasing).
+ * data_format: ZH_TAR_PLAIN (.tar) or ZH_DF_GZIP (.tar.gz / .taz / .tgz); anything else returns
+ * ZH_ERR_INVALID_FORMAT.  level: -2..9 as in zh_compress (ZH_DEFAULT_COMPRESSION is the drop-in value); ignored for
+ * ZH_TAR_PLAIN.  dsts[t] is library-allocated (zh_free), NULL for a tarball that failed.
+ * The return value is a call-level error: NULL pointers (also an entry's path or contents that is NULL with a
+ * non-zero length), bad first[], level or format, allocation, device.  Everything about a tarball's own entries
+ * is statuses[t]; a bad tarball never changes the bytes of the others:
+ *  - ZH_ERR_TAR_EMPTY: no entries;
+ *  - entry by entry in insertion order, the first failure wins; within one entry the checks run in this order:
+ *    ZH_ERR_TAR_PATH (splitPath head >= 155 bytes), ZH_ERR_TAR_NAME (tail >= 100 bytes), then ZH_ERR_ARGUMENT
+ *    for what the reference has no answer to or would write a broken header for:
+ *      kind other than '0' / '5';
+ *      len >= 8^11 or mtime outside [0, 8^11) (toOct(x, 11) would silently drop digits, and a negative
+ *        time's unsigned conversion depends on the Nim version);
+ *      a path equal to an earlier entry's of the same tarball (a table key cannot repeat).
+ * Header bytes: name = tail, mode "000777 \0" (permissions are not written, as in the reference), uid / gid 0,
+ * size and mtime in 11 octal digits, checksum, kind, "ustar\0" "00", devmajor / devminor 0, prefix = head;
+ * contents zero-padded to 512 bytes; the image ends with 1024 zero bytes (tarballs_v1.nim:229-261). */
+int zh_tar_create_batch(zh_ctx *ctx, const zh_tar_new_entry *entries, const size_t *first, size_t n_tar,
+                        int data_format, int level, void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
  * Introspection for parity tests (not part of the drop-in surface).   *

@@ -120,6 +120,9 @@ _SIGS = {
     "zh_tar_num_entries": (_c.c_size_t, [_c.c_void_p]),
     "zh_tar_entry_at": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "zh_tar_data": (_c.c_void_p, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "zh_tar_create_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
+                                       _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                       _c.POINTER(_c.c_int32)]),
     "zh_debug_tokens": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
                                    _c.POINTER(_c.POINTER(_c.c_uint16)), _c.POINTER(_c.c_size_t)]),
     "zh_debug_huffman": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_int, _c.c_int,
@@ -320,6 +323,26 @@ class TarReader:
             pass
 
 
+class TarNewEntry(_c.Structure):
+    _fields_ = [("path", _c.c_char_p), ("path_len", _c.c_size_t), ("contents", _c.c_void_p), ("len", _c.c_size_t),
+                ("kind", _c.c_char), ("mtime", _c.c_int64)]
+
+
+def _tar_entries(entries):
+    """A Tarball's contents (tarballs_v1.nim:8-18) as (path bytes, contents bytes, kind byte, mtime) tuples: an ordered
+    mapping or (path, value) pairs; a value is the contents, or (contents, kind, mtime) -- kind '0' / '5', mtime the
+    Unix time (defaults '0' and 0)."""
+    out = []
+    for path, v in (entries.items() if hasattr(entries, "items") else entries):
+        contents, kind, mtime = v, "0", 0
+        if isinstance(v, tuple):
+            contents, kind, mtime = v + ("0", 0)[len(v) - 1:]
+        p = path.encode("utf-8", "surrogateescape") if isinstance(path, str) else bytes(path)
+        k = kind.encode("latin-1") if isinstance(kind, str) else bytes(kind)
+        out.append((p, bytes(contents), k if len(k) == 1 else b"\0", int(mtime)))  # (a kind of other length: rejected)
+    return out
+
+
 class Engine:
     def __init__(self, lib_path, device=-1, stream=None):
         self.lib = load_library(lib_path)
@@ -473,6 +496,47 @@ class Engine:
 
     def open_tar(self, image):
         return TarReader(self, image)
+
+    def create_tars(self, tarballs, data_format=dfGzip, level=DefaultCompression):
+        """writeTarball (tarballs_v1.nim:203-270) of every tarball in one call (zh_tar_create_batch).
+        tarballs: a list of entry collections (see _tar_entries); data_format: dfGzip or TAR_PLAIN.
+        -> (list of bytes | None, statuses)"""
+        return self.create_tars_prepared(self.prepare_tars(tarballs), data_format, level)
+
+    @staticmethod
+    def prepare_tars(tarballs):
+        """The C arrays of zh_tar_create_batch for `tarballs` (kept alive by the returned tuple)."""
+        groups = [_tar_entries(t) for t in tarballs]
+        flat = [e for g in groups for e in g]
+        arr = (TarNewEntry * max(1, len(flat)))()
+        for i, (p, c, k, m) in enumerate(flat):
+            arr[i].path, arr[i].path_len = p, len(p)
+            arr[i].contents = _c.cast(_c.c_char_p(c), _c.c_void_p) if c else None
+            arr[i].len, arr[i].kind, arr[i].mtime = len(c), k, m
+        first = [0]
+        for g in groups:
+            first.append(first[-1] + len(g))
+        return arr, (_c.c_size_t * len(first))(*first), len(groups), flat
+
+    def create_tars_prepared(self, prepared, data_format=dfGzip, level=DefaultCompression):
+        arr, c_first, n, _ = prepared
+        dsts, dlens, sts = (_c.c_void_p * max(1, n))(), (_c.c_size_t * max(1, n))(), (_c.c_int32 * max(1, n))()
+        rc = self.lib.zh_tar_create_batch(self._h, arr, c_first, n, data_format, level, dsts, dlens, sts)
+        outs = []
+        try:
+            for t in range(n):
+                outs.append(_c.string_at(dsts[t], dlens[t]) if dsts[t] and sts[t] == 0 else None)
+        finally:
+            for t in range(n):
+                if dsts[t]:
+                    self.lib.zh_free(dsts[t])
+        self._check(rc)
+        return outs, list(sts)[:n]
+
+    def create_tar(self, entries, data_format=dfGzip, level=DefaultCompression):
+        """One tarball's bytes; raises ZippyError on failure."""
+        outs, sts = self.create_tars([entries], data_format, level)
+        return self._raise_first(outs, sts)[0]
 
     def crc32_batch(self, bufs):
         n = len(bufs)

@@ -13,7 +13,7 @@ import os
 
 from ._binding import Engine
 from .common import (ZippyError, dfDetect, dfZlib, dfGzip, dfDeflate, NoCompression, BestSpeed,
-                     BestCompression, DefaultCompression, HuffmanOnly)
+                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN)
 
 # ZIPPY_HIP_LIB: tuning builds of the same library (tools/); never a different implementation
 LIB_PATH = os.environ.get("ZIPPY_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
@@ -71,6 +71,13 @@ def createZipArchive(entries, dos_time=0, dos_date=0):
 def openTarball(image):
     """tarballs.nim:26-124 on the bytes of a .tar.gz / .tar -> reader with .entries, .contents(i)."""
     return engine().open_tar(image)
+
+
+def writeTarball(entries, dataFormat=dfGzip, level=DefaultCompression):
+    """tarballs_v1.nim:203-270 writeTarball without the file write -> the bytes of the .tar.gz (dfGzip) or .tar
+    (TAR_PLAIN).  entries: ordered mapping / (path, value) pairs; a value is the contents, or (contents, kind, mtime)
+    with kind '0' (file) / '5' (directory) and mtime the Unix time (defaults '0', 0)."""
+    return engine().create_tar(entries, dataFormat, level)
 
 
 def crc32(src):

@@ -19,3 +19,6 @@ BestSpeed = 1
 BestCompression = 9
 DefaultCompression = -1
 HuffmanOnly = -2
+
+# zh_tar_create_batch's data format for a plain .tar image (include/zippy_hip.h ZH_TAR_PLAIN)
+TAR_PLAIN = -1

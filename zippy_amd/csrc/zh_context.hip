@@ -117,6 +117,9 @@ extern "C" const char* zh_strerror(int status) {
     case ZH_ERR_TAR_HEADER_TYPE: return "Unsupported header type";
     case ZH_ERR_UNSAFE_PATH: return "Path not allowed (absolute or containing ../)";
     case ZH_ERR_TAR_NUMBER: return "Invalid octal number in tar header";
+    case ZH_ERR_TAR_EMPTY: return "Tarball has no contents";
+    case ZH_ERR_TAR_PATH: return "File path too long, must be < 155 characters";
+    case ZH_ERR_TAR_NAME: return "File name too long, must be < 100 characters";
     default: return "Unknown status";
   }
 }

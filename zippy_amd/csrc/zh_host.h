@@ -314,6 +314,10 @@ struct Trace {
 // (zh_host_batch.hip) pack host buffers into one device allocation / results into fresh host buffers
 ZH_INTERNAL int zhh_upload(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n, DevBuf& dev,
                            std::vector<uint64_t>& off, std::vector<uint64_t>& len64);
+// host buffers -> dev at arbitrary byte offsets: srcs[i] (len64[i] bytes) lands at dev + off[i], off[] ascending;
+// the whole range [0, total) goes over the link, so bytes between the slices hold stale staging contents afterwards
+ZH_INTERNAL int zhh_upload_slices(zh_ctx* ctx, const void* const* srcs, const std::vector<uint64_t>& off,
+                                  const std::vector<uint64_t>& len64, uint64_t total, uint8_t* dev);
 ZH_INTERNAL int zhh_download(zh_ctx* ctx, const uint8_t* d_dst, size_t n, const std::vector<uint64_t>& doff,
                              const std::vector<uint64_t>& olen, const std::vector<char>& take, void** dsts,
                              size_t* dst_lens, int32_t* statuses);

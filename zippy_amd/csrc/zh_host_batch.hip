@@ -929,6 +929,10 @@ int zhh_upload(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t 
                std::vector<uint64_t>& len64) {
   return upload(ctx, srcs, lens, n, dev, off, len64);
 }
+int zhh_upload_slices(zh_ctx* ctx, const void* const* srcs, const std::vector<uint64_t>& off,
+                      const std::vector<uint64_t>& len64, uint64_t total, uint8_t* dev) {
+  return upload_slices(ctx, ctx->stream, srcs, off, len64, total, dev);
+}
 int zhh_download(zh_ctx* ctx, const uint8_t* d_dst, size_t n, const std::vector<uint64_t>& doff,
                  const std::vector<uint64_t>& olen, const std::vector<char>& take, void** dsts, size_t* dst_lens,
                  int32_t* statuses) {

@@ -210,3 +210,47 @@ proc hipTarballImage*(entries: openArray[tuple[path, contents: string, kind: cha
                                (if gzip: dfGzip.cint else: ZH_TAR_PLAIN), DefaultCompression.cint,
                                p.addr, n.addr, st.addr)
   take(p, n, if rc != 0: rc else: st.cint)
+
+# ---- writing zip archives (src/zippy/ziparchives_v1.nim) ----
+import std/times
+
+type
+  ZhZipNewEntry {.bycopy.} = object
+    path: cstring                       # not NUL-terminated: use pathLen
+    pathLen: csize_t
+    contents: pointer
+    len: csize_t
+    isDirectory: cint                   # ekDirectory: external attributes 0x10, else 0x20
+    dosTime, dosDate: uint16            # toMsDos(lastModified)
+
+proc zh_zip_write_batch(ctx: ZhCtx, entries: ptr ZhZipNewEntry, first: ptr csize_t, nZip: csize_t,
+                        level: cint, dsts: ptr pointer, dstLens: ptr csize_t,
+                        statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipMsDos(t: Time): (uint16, uint16) =
+  ## toMsDos (ziparchives_v1.nim:356-369), field for field: the reference's proc is private to its module
+  let d = t.local()
+  let years = max(0, d.year - 1980).uint16
+  ((d.second div 2).uint16 or (d.minute.uint16 shl 5) or (d.hour.uint16 shl 11),
+   d.monthday.uint16 or (ord(d.month).uint16 shl 5) or (years shl 9))
+
+proc hipWriteZipArchive*[ZipArchive](archive: ZipArchive): string {.raises: [ZippyError].} =
+  ## writeZipArchive's `data` (ziparchives_v1.nim:371-479) in one call: every entry's compress(contents,
+  ## DefaultCompression, dfDeflate) and crc32, and every header, written on the device.  Generic in the archive type
+  ## (ziparchives_v1.ZipArchive), so that this module does not import the module that calls it.
+  var paths: seq[string]               # the keys, kept alive for the call
+  var es: seq[ZhZipNewEntry]
+  for path, e in archive.contents.mpairs:   # insertion order; `e` is the table's own entry
+    let (t, d) = hipMsDos(e.lastModified)
+    paths.add path
+    es.add ZhZipNewEntry(pathLen: path.len.csize_t,
+                         contents: (if e.contents.len > 0: e.contents[0].addr else: nil),
+                         len: e.contents.len.csize_t, isDirectory: cint(ord(e.kind) == 1),  # ekFile, ekDirectory
+                         dosTime: t, dosDate: d)
+  for i in 0 ..< es.len:
+    es[i].path = paths[i].cstring
+  var first = [0.csize_t, es.len.csize_t]
+  var p: pointer; var n: csize_t; var st: int32
+  let rc = zh_zip_write_batch(engine(), (if es.len > 0: es[0].addr else: nil), first[0].addr, 1,
+                              DefaultCompression.cint, p.addr, n.addr, st.addr)
+  take(p, n, if rc != 0: rc else: st.cint)

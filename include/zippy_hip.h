@@ -77,7 +77,10 @@ enum {
   /* tarball writer (zh_tar_create_batch): the ZippyError raise sites of tarballs_v1.nim writeTarball */
   ZH_ERR_TAR_EMPTY = 37,          /* tarballs_v1.nim:210-211 */
   ZH_ERR_TAR_PATH = 38,           /* tarballs_v1.nim:218-222 (splitPath head >= 155 bytes) */
-  ZH_ERR_TAR_NAME = 39            /* tarballs_v1.nim:223-227 (splitPath tail >= 100 bytes) */
+  ZH_ERR_TAR_NAME = 39,           /* tarballs_v1.nim:223-227 (splitPath tail >= 100 bytes) */
+  /* v1 zip writer (zh_zip_write_batch): ziparchives_v1.nim writeZipArchive */
+  ZH_ERR_ZIP_EMPTY = 40,          /* ziparchives_v1.nim:375-376 */
+  ZH_ERR_ZIP_TOO_LARGE = 41       /* a count, length or offset that does not fit its 16- / 32-bit field */
 };
 
 /* Engine context: one GPU, one HIP stream, reusable scratch. Thread-compatible
@@ -435,6 +438,47 @@ enum { ZH_TAR_PLAIN = -1 };       /* data_format: the .tar image itself */
  * contents zero-padded to 512 bytes; the image ends with 1024 zero bytes (tarballs_v1.nim:229-261). */
 int zh_tar_create_batch(zh_ctx *ctx, const zh_tar_new_entry *entries, const size_t *first, size_t n_tar,
                         int data_format, int level, void **dsts, size_t *dst_lens, int32_t *statuses);
+
+/* Writing zip archives: writeZipArchive(archive, path) -- ziparchives_v1.nim:371-486 -- for n_zip in-memory
+ * archives at once, without the file write.  Every non-empty entry goes through ONE compress plan (deflate + its
+ * CRC-32); the host lays the archives out from the compressed lengths, and one kernel writes every byte of every
+ * image: local headers, the compressed streams gathered from the plan's slots, the central directories, the EOCDs. */
+typedef struct zh_zip_new_entry { /* one (path, ArchiveEntry) of ZipArchive.contents (ziparchives_v1.nim:12-21) */
+  const char *path;               /* the table key, bytes as given */
+  size_t path_len;
+  const void *contents;           /* may be NULL when len == 0 */
+  size_t len;
+  int is_directory;               /* ekDirectory: external attributes 0x10, else 0x20 */
+  uint16_t dos_time, dos_date;    /* toMsDos(lastModified) (:356-369), from the caller: the call stays pure */
+} zh_zip_new_entry;
+/* Archive t is entries[first[t] .. first[t+1]) in insertion order (first has n_zip + 1 elements, non-decreasing).
+ * level: -2..9 (ZH_DEFAULT_COMPRESSION gives the reference's bytes; other levels and contract mode give valid
+ * archives with other deflate streams), else ZH_ERR_INVALID_LEVEL.  dsts[t] is library-allocated (zh_free), NULL for
+ * an archive that failed.  The return value is a call-level error: NULL pointers (also an entry's path or contents
+ * that is NULL with a non-zero length), bad first[] or level, allocation, device.  Everything about an archive's own
+ * entries is statuses[t]; a bad archive never changes the bytes of the others.  The checks run step by step; within
+ * a step, entry by entry in insertion order, and the first failure wins:
+ *  1. ZH_ERR_ZIP_EMPTY: no entries (:375-376);
+ *  2. ZH_ERR_ZIP_TOO_LARGE: more than 65535 entries, a path longer than 65535 bytes, or len >= 2^32 (the reference
+ *     would truncate the value silently);
+ *  3. ZH_ERR_ARGUMENT: contents that are not empty under method 0 (a path that is empty or ends in '/'; the
+ *     reference would write deflate bytes under method 0);
+ *  4. ZH_ERR_ZIP_DUPLICATE: a path equal to an earlier entry's of the same archive (a table key cannot repeat);
+ *  5. after compression, ZH_ERR_ZIP_TOO_LARGE: a compressed length, a local header's offset, or the central
+ *     directory's size or offset >= 2^32 (ZH_ZIP32_LIMIT, read at each call, lowers this limit: a test aid).
+ * Paths are written as given: zh_zip_create's ZH_ERR_ZIP_NAME checks do not apply (v1 writes empty and absolute
+ * paths).  Bytes (all little-endian, no zip64 records, :379-479):
+ *  - each entry in insertion order: local header 50 4b 03 04, version 20, flags 0x0800, method, dos_time, dos_date,
+ *    crc32(contents), compressed length, length, path length, extra length 0, the path, the compressed stream.
+ *    Method 0 when the contents are empty or splitFile(path).name is empty (the path is empty or ends in '/'): no
+ *    data, CRC 0, both lengths 0; else method 8 and compress(contents, level, dfDeflate);
+ *  - the central directory in the same order: 50 4b 01 02, made-by 63, version 20, flags 0x0800, method, time, date,
+ *    CRC, both lengths, path length, extra / comment / disk / internal attributes 0, external attributes
+ *    10 00 00 00 (directory) or 20 00 00 00, the local header's offset, the path;
+ *  - the end of central directory record: 50 4b 05 06, 0, 0, the entry count twice, the directory's size and offset,
+ *    comment length 0. */
+int zh_zip_write_batch(zh_ctx *ctx, const zh_zip_new_entry *entries, const size_t *first, size_t n_zip,
+                       int level, void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
  * Introspection for parity tests (not part of the drop-in surface).   *

@@ -1,0 +1,157 @@
+"""CPU-only: zh_zip_write_batch (zippy_amd/csrc/zh_zip_write.hip) under the fiber emulator of tests/hipemu, with the
+emulator's 128 KiB staging chunks, so that entries cross chunk borders.  The device's archives must equal
+tests/zip_v1_writer_model.py byte for byte."""
+import io
+import os
+import zipfile
+
+import pytest
+
+import emu
+import synth
+import zip_v1_writer_model as zm
+from zippy_amd.common import ZippyError
+
+
+@pytest.fixture(scope="module")
+def eng():
+    return emu.engine()
+
+
+def _blob(n, seed=1):
+    return bytes((i * 131 + seed * 7 + (i >> 7) + (i * i >> 11)) & 0xFF for i in range(n))
+
+
+SIZES = [0, 1, 3, 4, 15, 16, 17, 140000]
+
+
+def test_emu_zip_entry_sizes(eng):
+    entries = [("f%d.bin" % n, (_blob(n, n), False, 0x6000 + i, 0x5521)) for i, n in enumerate(SIZES)]
+    assert eng.write_zip(entries) == zm.image(entries)
+
+
+def test_emu_zip_record_alignments(eng):
+    """path lengths chosen so that entry i's stream starts at i mod 16: the streams go to every alignment, and the
+    records behind them (local headers, central directory records, the end record) with them"""
+    import oracle
+    entries, starts, o = [], [], 0
+    for i in range(32):
+        contents = _blob(40 + 97 * i, i)
+        plen = (i - o - 30) % 16 + 16
+        entries.append((("n%d_" % i).ljust(plen, "x"), (contents, False, i, i)))
+        starts.append(o + 30 + plen)
+        o += 30 + plen + len(oracle.compress(contents, -1, oracle.dfDeflate))
+        entries.append(("ef"[i // 16] * (i % 16 + 1) + "/", (b"", True, i, i)))
+        o += 30 + i % 16 + 2
+    assert {s % 16 for s in starts} == set(range(16))
+    img = eng.write_zip(entries)
+    assert img == zm.image(entries)
+    assert all(img[at - len(p):at] == p.encode() for (p, _), at in zip(entries[::2], starts))
+
+
+def test_emu_zip_directories_and_paths(eng):
+    entries = [("dir/", (b"", True, 1, 2)), ("dir2", (b"contents of a directory", True, 3, 4)),
+               ("/abs/path.txt", b"absolute"), ("ünicøde/日本語.txt", "UTF-8".encode() * 40), ("", b""),
+               ("a//b", b"zzz"), ("x" * 300, _blob(3000, 5))]
+    img = eng.write_zip(entries)
+    assert img == zm.image(entries)
+    with zipfile.ZipFile(io.BytesIO(img)) as zf:
+        assert zf.testzip() is None
+        assert [i.external_attr for i in zf.infolist()][:2] == [0x10, 0x10]
+
+
+@pytest.mark.parametrize("level", [-2, 0, 1, -1, 9])
+def test_emu_zip_levels(eng, level):
+    entries = [("f%d" % n, _blob(n, n)) for n in SIZES[:7]] + [
+        ("text/alice.txt", (synth.corpus_file("alice29.txt")[:60000], False, 0x6000, 0x5521))]
+    assert eng.write_zip(entries, level) == zm.image(entries, level)
+
+
+@pytest.mark.parametrize("entries,status", [
+    ([], zm.ZH_ERR_ZIP_EMPTY),
+    ([("x" * 65536, b"")], zm.ZH_ERR_ZIP_TOO_LARGE),
+    ([("d/", b"x")], zm.ZH_ERR_ARGUMENT),
+    ([("", b"x")], zm.ZH_ERR_ARGUMENT),
+    ([("a", b"1"), ("b", b"2"), ("a", b"")], zm.ZH_ERR_ZIP_DUPLICATE),
+    ([("a", b""), ("a", b""), ("d/", b"x"), ("x" * 65536, b"")], zm.ZH_ERR_ZIP_TOO_LARGE),
+    ([("a", b""), ("a", b""), ("d/", b"x")], zm.ZH_ERR_ARGUMENT),
+])
+def test_emu_zip_errors(eng, entries, status):
+    assert zm.status(entries) == status
+    outs, sts = eng.write_zips([entries])
+    assert outs == [None] and sts == [status]
+    with pytest.raises(ZippyError) as ei:
+        eng.write_zip(entries)
+    assert ei.value.status == status
+    assert eng.lib.zh_strerror(status).decode().startswith(
+        {40: "Zip archive has no contents", 41: "Zip archive too large", 22: "Invalid argument",
+         31: "Unsupported archive, duplicate entry"}[status][:20])
+
+
+def test_emu_zip_call_level_errors(eng):
+    with pytest.raises(ZippyError) as ei:
+        eng.write_zips([[("a", b"x")]], 10)
+    assert ei.value.status == 1  # ZH_ERR_INVALID_LEVEL
+    assert eng.write_zips([]) == ([], [])
+
+
+def test_emu_zip_batch_mixes_good_and_bad(eng):
+    good = [[("one.txt", b"hello")],
+            [("f%d" % n, _blob(n, n)) for n in SIZES],
+            [("d/", (b"", True, 1, 1)), ("d/x", _blob(1000, 3))],
+            [("only/", (b"", True, 0, 0))]]
+    bad = [[], [("d/", b"x")], [("a", b""), ("a", b"")]]
+    zips = [good[0], bad[0], good[1], bad[1], good[2], bad[2], good[3]]
+    want = [zm.status(z) for z in zips]
+    assert sorted(set(want)) == [0, zm.ZH_ERR_ARGUMENT, zm.ZH_ERR_ZIP_DUPLICATE, zm.ZH_ERR_ZIP_EMPTY]
+    outs, sts = eng.write_zips(zips)
+    assert sts == want
+    for z, out, st in zip(zips, outs, sts):
+        assert out == (zm.image(z) if st == 0 else None)
+    # the good ones alone: the same bytes
+    alone, sts = eng.write_zips(good)
+    assert sts == [0] * 4 and alone == [o for o in outs if o is not None]
+
+
+def test_emu_zip_post_compression_refusal(eng, monkeypatch):
+    """step 5 through ZH_ZIP32_LIMIT (read at each call): the compressed length, a local header's offset, the
+    central directory's offset -- the other archives of the call keep their bytes"""
+    big = [("a", _blob(3000, 1)), ("b", _blob(500, 2))]
+    small = [("s", b"small")]
+    img = zm.image(big)
+    cd_off = int.from_bytes(img[-6:-2], "little")
+    clen_a = int.from_bytes(img[18:22], "little")
+    for limit in (clen_a, cd_off, cd_off + 1):
+        want = zm.status(big, limit=limit)
+        monkeypatch.setenv("ZH_ZIP32_LIMIT", str(limit))
+        outs, sts = eng.write_zips([small, big, small])
+        assert sts == [0, want, 0]
+        assert outs[0] == outs[2] == zm.image(small)
+        assert outs[1] == (img if want == 0 else None)
+    assert [zm.status(big, limit=x) for x in (clen_a, cd_off, cd_off + 1)] == [41, 41, 0]
+    monkeypatch.delenv("ZH_ZIP32_LIMIT")
+    assert eng.write_zip(big) == img
+
+
+def test_emu_zip_round_trip_zh_zip_open(eng):
+    entries = [("r/%d" % i, (_blob(37 * i, i), False, i, i)) for i in range(1, 40)] + [("r/", (b"", True, 0, 0))]
+    img = eng.write_zip(entries)
+    reader = eng.open_zip(img)
+    assert [e["path"] for e in reader.entries] == [p for p, _ in entries]
+    outs, sts = reader.extract_batch(list(range(39)))
+    assert sts == [0] * 39 and outs == [v[0] for _, v in entries[:39]]
+    reader.close()
+
+
+def test_emu_zip_mmap_contents(eng):
+    """contents given as a writable buffer go to the library without a copy"""
+    import mmap
+    mm = mmap.mmap(-1, 5000)
+    mm[:] = _blob(5000, 9)
+    try:
+        assert eng.write_zip([("m", mm)]) == zm.image([("m", bytes(mm))])
+    finally:
+        import gc
+        gc.collect()
+        mm.close()
+    assert os.environ.get("ZH_ZIP32_LIMIT") is None

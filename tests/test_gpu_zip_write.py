@@ -1,0 +1,144 @@
+"""zh_zip_write_batch on a real MI355X (-m gpu): the archives of zh_zip_write_kernel against
+tests/zip_v1_writer_model.py byte for byte (deflate streams from the oracle's compress(contents, level, dfDeflate))."""
+import io
+import mmap
+import random
+import zipfile
+
+import pytest
+
+import synth
+import zip_v1_writer_model as zm
+from zippy_amd.common import BestSpeed, DefaultCompression, ZippyError, to_msdos
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng():
+    import torch  # torch's bundled HIP runtime has to initialise before libzippy_hip.so's
+    torch.cuda.init()
+    from zippy_amd import api
+    return api.engine()
+
+
+def _random_entries(rng, n, max_len, pool, prefix="e"):
+    out = []
+    for i in range(n):
+        k = rng.randrange(max_len + 1)
+        at = rng.randrange(len(pool) - k + 1)
+        if rng.random() < 0.05:
+            out.append(("%s/%d/d%d/" % (prefix, i % 17, i), (b"", True, rng.randrange(1 << 16), rng.randrange(1 << 16))))
+        else:
+            out.append(("%s/%d/n%d" % (prefix, i % 17, i),
+                        (pool[at:at + k], False, rng.randrange(1 << 16), rng.randrange(1 << 16))))
+    return out
+
+
+def test_gpu_zip_bagnon_written_back(eng):
+    """tests/test_ziparchives_read.nim's fixture: read on the device (zh_zip_open + zh_zip_extract_batch), written
+    back as a v1 archive"""
+    reader = eng.open_zip(synth.fixture("ziparchives/Bagnon-10.2.31.zip"))
+    files = [i for i, e in enumerate(reader.entries) if not e["is_directory"]]
+    outs, sts = reader.extract_batch(files)
+    assert sts == [0] * len(files)
+    got = dict(zip(files, outs))
+    t, d = to_msdos(1600000000)
+    entries = [(e["path"], (got.get(i, b""), e["is_directory"], t, d)) for i, e in enumerate(reader.entries)]
+    reader.close()
+    img = zm.image(entries)
+    assert eng.write_zip(entries) == img
+    with zipfile.ZipFile(io.BytesIO(img)) as zf:
+        assert zf.testzip() is None
+
+
+def test_gpu_zip_libressl_entries(eng):
+    """tests/test_tarballs_read.nim's fixture: its 1743 entries as one zip"""
+    reader = eng.open_tar(synth.fixture("tarballs/libressl-3.4.2.tar.gz"))
+    entries = []
+    for i, e in enumerate(reader.entries):
+        is_dir = e["typeflag"] == b"5"
+        path = e["path"] + (b"/" if is_dir and not e["path"].endswith(b"/") else b"")
+        entries.append((path, (reader.contents(i), is_dir) + to_msdos(e["mtime"])))
+    reader.close()
+    assert len(entries) == 1743
+    img = eng.write_zip(entries)
+    assert img == zm.image(entries)
+    from oracle import zip_oracle
+    r = zip_oracle.open_archive(img)
+    assert len(r.records) == 1743
+
+
+def test_gpu_zip_256_archives_one_call(eng):
+    rng = random.Random(20261016)
+    pool = synth.gen_batch("mix", 1, 1 << 20)[0].tobytes()
+    zips = [_random_entries(rng, rng.randrange(1, 40), rng.choice([0, 600, 5000, 70000]), pool, "z%d" % t)
+            for t in range(256)]
+    outs, sts = eng.write_zips(zips)
+    assert sts == [0] * 256
+    for z, out in zip(zips, outs):
+        assert out == zm.image(z)
+
+
+def test_gpu_zip_65535_tiny_entries(eng):
+    entries = [("t/%05d" % i, (bytes([i & 255]) * (i % 7), False, i & 0xFFFF, 0x5521)) for i in range(65535)]
+    assert eng.write_zip(entries) == zm.image(entries)
+    outs, sts = eng.write_zips([entries + [("t/one-more", b"x")], entries[:3]])
+    assert sts == [zm.ZH_ERR_ZIP_TOO_LARGE, 0] and outs[0] is None and outs[1] == zm.image(entries[:3])
+
+
+def test_gpu_zip_64mib_entry(eng):
+    big = synth.gen_batch("mix", 1, 64 << 20)[0].tobytes() + b"tail" * 1001
+    entries = [("head.txt", b"small " * 50), ("big/blob.bin", (big, False) + to_msdos(1700000000)),
+               ("big/", (b"", True, 0, 0))]
+    img = eng.write_zip(entries)
+    assert img == zm.image(entries)
+    with zipfile.ZipFile(io.BytesIO(img)) as zf:
+        assert zf.read("big/blob.bin") == big
+
+
+def test_gpu_zip_4gib_entry_refused_before_reading(eng):
+    """len == 2^32 does not fit the 32-bit fields: refused from the length alone -- the untouched anonymous mapping
+    behind it is never read, so it costs no memory"""
+    mm = mmap.mmap(-1, 1 << 32, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
+    try:
+        small = [("ok.txt", b"fine")]
+        outs, sts = eng.write_zips([[("huge.bin", mm)], small])
+        assert sts == [zm.ZH_ERR_ZIP_TOO_LARGE, 0]
+        assert outs == [None, zm.image(small)]
+    finally:
+        import gc
+        gc.collect()
+        mm.close()
+
+
+def test_gpu_zip_contract_mode(eng):
+    """zh_set_l1_parse(1) at BestSpeed: other deflate streams than zippy's, valid archives of the same contents"""
+    rng = random.Random(11)
+    pool = synth.gen_batch("mix", 1, 1 << 20)[0].tobytes()
+    entries = _random_entries(rng, 300, 20000, pool)
+    eng.set_l1_parse(1)
+    try:
+        img = eng.write_zip(entries, BestSpeed)
+    finally:
+        eng.set_l1_parse(-1)
+    from oracle import zip_oracle
+    r = zip_oracle.open_archive(img)
+    with zipfile.ZipFile(io.BytesIO(img)) as zf:
+        assert zf.testzip() is None
+        for p, v in entries:
+            if not v[1]:
+                assert zf.read(p) == v[0] == zip_oracle.extract_file(r, p)
+
+
+def test_gpu_write_zip_archive_api(eng):
+    """zippy_amd.api.writeZipArchive: an ordered mapping in, the archive's bytes out, ZippyError on failure"""
+    from collections import OrderedDict
+    from zippy_amd import api
+    entries = OrderedDict([("README.txt", (b"Hello, World!", False) + to_msdos(1600000000)),
+                           ("docs/", (b"", True, 0, 0)), ("docs/a.txt", b"a" * 1000)])
+    assert api.writeZipArchive(entries) == zm.image(entries)
+    assert api.writeZipArchive(entries, 9) == zm.image(entries, 9)
+    with pytest.raises(ZippyError, match="Zip archive has no contents"):
+        api.writeZipArchive({})
+    assert DefaultCompression == -1

@@ -123,6 +123,8 @@ _SIGS = {
     "zh_tar_create_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
                                        _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
                                        _c.POINTER(_c.c_int32)]),
+    "zh_zip_write_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
+                                      _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
     "zh_debug_tokens": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
                                    _c.POINTER(_c.POINTER(_c.c_uint16)), _c.POINTER(_c.c_size_t)]),
     "zh_debug_huffman": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_int, _c.c_int,
@@ -343,6 +345,39 @@ def _tar_entries(entries):
     return out
 
 
+class ZipNewEntry(_c.Structure):
+    _fields_ = [("path", _c.c_char_p), ("path_len", _c.c_size_t), ("contents", _c.c_void_p), ("len", _c.c_size_t),
+                ("is_directory", _c.c_int), ("dos_time", _c.c_uint16), ("dos_date", _c.c_uint16)]
+
+
+def _zip_entries(entries):
+    """A ZipArchive's contents (ziparchives_v1.nim:12-21) as (path bytes, contents, is_directory, dos_time, dos_date)
+    tuples: an ordered mapping or (path, value) pairs; a value is the contents, or (contents, is_directory, dos_time,
+    dos_date) (defaults False, 0, 0).  Contents may be any buffer: bytes and writable buffers (an mmap, a bytearray) go
+    to the library as they are, other read-only buffers are copied first (the library reads nothing of an entry it
+    refuses before compressing)."""
+    out = []
+    for path, v in (entries.items() if hasattr(entries, "items") else entries):
+        contents, is_dir, t, d = v, False, 0, 0
+        if isinstance(v, tuple):
+            contents, is_dir, t, d = v + (False, 0, 0)[len(v) - 1:]
+        p = path.encode("utf-8", "surrogateescape") if isinstance(path, str) else bytes(path)
+        out.append((p, contents, bool(is_dir), int(t), int(d)))
+    return out
+
+
+def _buffer_address(obj):
+    """-> (address or None, length, the object that keeps the memory alive)"""
+    if not isinstance(obj, bytes):
+        mv = memoryview(obj)
+        if mv.readonly or not mv.contiguous:
+            obj = bytes(mv)
+        else:
+            n = mv.nbytes
+            return (_c.addressof(_c.c_char.from_buffer(mv.cast("B"))) if n else None), n, mv
+    return (_c.cast(_c.c_char_p(obj), _c.c_void_p).value if obj else None), len(obj), obj
+
+
 class Engine:
     def __init__(self, lib_path, device=-1, stream=None):
         self.lib = load_library(lib_path)
@@ -536,6 +571,48 @@ class Engine:
     def create_tar(self, entries, data_format=dfGzip, level=DefaultCompression):
         """One tarball's bytes; raises ZippyError on failure."""
         outs, sts = self.create_tars([entries], data_format, level)
+        return self._raise_first(outs, sts)[0]
+
+    def write_zips(self, archives, level=DefaultCompression):
+        """writeZipArchive (ziparchives_v1.nim:371-486) of every archive in one call (zh_zip_write_batch).
+        archives: a list of entry collections (see _zip_entries).  -> (list of bytes | None, statuses)"""
+        return self.write_zips_prepared(self.prepare_zips(archives), level)
+
+    @staticmethod
+    def prepare_zips(archives):
+        """The C arrays of zh_zip_write_batch for `archives` (kept alive by the returned tuple)."""
+        groups = [_zip_entries(a) for a in archives]
+        flat = [e for g in groups for e in g]
+        arr = (ZipNewEntry * max(1, len(flat)))()
+        keep = []
+        for i, (p, c, is_dir, t, d) in enumerate(flat):
+            addr, n, k = _buffer_address(c)
+            keep.append(k)
+            arr[i].path, arr[i].path_len, arr[i].contents, arr[i].len = p, len(p), addr, n
+            arr[i].is_directory, arr[i].dos_time, arr[i].dos_date = int(is_dir), t & 0xFFFF, d & 0xFFFF
+        first = [0]
+        for g in groups:
+            first.append(first[-1] + len(g))
+        return arr, (_c.c_size_t * len(first))(*first), len(groups), (flat, keep)
+
+    def write_zips_prepared(self, prepared, level=DefaultCompression):
+        arr, c_first, n, _ = prepared
+        dsts, dlens, sts = (_c.c_void_p * max(1, n))(), (_c.c_size_t * max(1, n))(), (_c.c_int32 * max(1, n))()
+        rc = self.lib.zh_zip_write_batch(self._h, arr, c_first, n, level, dsts, dlens, sts)
+        outs = []
+        try:
+            for t in range(n):
+                outs.append(_c.string_at(dsts[t], dlens[t]) if dsts[t] and sts[t] == 0 else None)
+        finally:
+            for t in range(n):
+                if dsts[t]:
+                    self.lib.zh_free(dsts[t])
+        self._check(rc)
+        return outs, list(sts)[:n]
+
+    def write_zip(self, entries, level=DefaultCompression):
+        """One archive's bytes; raises ZippyError on failure."""
+        outs, sts = self.write_zips([entries], level)
         return self._raise_first(outs, sts)[0]
 
     def crc32_batch(self, bufs):

@@ -13,7 +13,7 @@ import os
 
 from ._binding import Engine
 from .common import (ZippyError, dfDetect, dfZlib, dfGzip, dfDeflate, NoCompression, BestSpeed,
-                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN)
+                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN, to_msdos)
 
 # ZIPPY_HIP_LIB: tuning builds of the same library (tools/); never a different implementation
 LIB_PATH = os.environ.get("ZIPPY_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
@@ -78,6 +78,13 @@ def writeTarball(entries, dataFormat=dfGzip, level=DefaultCompression):
     (TAR_PLAIN).  entries: ordered mapping / (path, value) pairs; a value is the contents, or (contents, kind, mtime)
     with kind '0' (file) / '5' (directory) and mtime the Unix time (defaults '0', 0)."""
     return engine().create_tar(entries, dataFormat, level)
+
+
+def writeZipArchive(entries, level=DefaultCompression):
+    """ziparchives_v1.nim:371-486 writeZipArchive without the file write -> the bytes of the archive.
+    entries: ordered mapping / (path, value) pairs; a value is the contents, or (contents, is_directory, dos_time,
+    dos_date) with the DOS time and date of toMsDos (to_msdos(unix_time)); defaults False, 0, 0."""
+    return engine().write_zip(entries, level)
 
 
 def crc32(src):

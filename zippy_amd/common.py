@@ -22,3 +22,12 @@ HuffmanOnly = -2
 
 # zh_tar_create_batch's data format for a plain .tar image (include/zippy_hip.h ZH_TAR_PLAIN)
 TAR_PLAIN = -1
+
+
+def to_msdos(unix_time):
+    """toMsDos (ziparchives_v1.nim:356-369) of a Unix time, in local time -> (dos_time, dos_date)"""
+    import time
+    t = time.localtime(unix_time)
+    dos_time = (t.tm_sec // 2) | (t.tm_min << 5) | (t.tm_hour << 11)
+    dos_date = t.tm_mday | (t.tm_mon << 5) | (((max(0, t.tm_year - 1980) & 0xFFFF) << 9) & 0xFFFF)
+    return dos_time & 0xFFFF, dos_date

@@ -120,6 +120,8 @@ extern "C" const char* zh_strerror(int status) {
     case ZH_ERR_TAR_EMPTY: return "Tarball has no contents";
     case ZH_ERR_TAR_PATH: return "File path too long, must be < 155 characters";
     case ZH_ERR_TAR_NAME: return "File name too long, must be < 100 characters";
+    case ZH_ERR_ZIP_EMPTY: return "Zip archive has no contents";
+    case ZH_ERR_ZIP_TOO_LARGE: return "Zip archive too large: a count, length or offset does not fit its field (no zip64)";
     default: return "Unknown status";
   }
 }

@@ -33,6 +33,44 @@ def test_emu_compress_identical_level1(eng):
     pc.check_compress_identical(eng, inputs, levels=(1,))
 
 
+def _first_cap_batches():
+    """a batch below the emulator's ZH_PIPE_GROUP (one group: the plain path) and one of two groups (pipelined); both
+    mix outputs that fit in 64 bytes with outputs that do not"""
+    edge = pc.edge_inputs()[:15]
+    return {"plain": [synth.corpus_file("geo.protodata")[:40000]] + edge,
+            "pipelined": [synth.corpus_file("alice29.txt")[:100000], synth.corpus_file("geo.protodata")[:70000]] + edge}
+
+
+def _compress_batch_crc32(eng, bufs, level, fmt):
+    import ctypes as c
+    n = len(bufs)
+    srcs = (c.c_void_p * n)(*[c.cast(c.c_char_p(b), c.c_void_p) for b in bufs])
+    lens = (c.c_size_t * n)(*[len(b) for b in bufs])
+    dsts, dlens, sts, crcs = (c.c_void_p * n)(), (c.c_size_t * n)(), (c.c_int32 * n)(), (c.c_uint32 * n)()
+    rc = eng.lib.zh_compress_batch_crc32(eng._h, srcs, lens, n, level, fmt, dsts, dlens, sts, crcs)
+    outs = [c.string_at(dsts[i], dlens[i]) if dsts[i] else None for i in range(n)]
+    for i in range(n):
+        if dsts[i]:
+            eng.lib.zh_free(dsts[i])
+    eng._check(rc)
+    return outs, list(sts), list(crcs)
+
+
+@pytest.mark.parametrize("kind", ["plain", "pipelined"])
+def test_emu_compress_first_cap_retry(eng, monkeypatch, kind):
+    """ZH_COMPRESS_FIRST_CAP=64: most outputs outgrow their first slots, so the plain path runs its plan a second time
+    with zh_compress_bound slots, and a pipelined batch falls back to the plain path -- the same bytes and CRC-32s"""
+    import zlib
+    batch = _first_cap_batches()[kind]
+    want = eng.compress_batch(batch, 1, oracle.dfGzip)
+    want_crc = _compress_batch_crc32(eng, batch, 1, oracle.dfDeflate)
+    assert want_crc[2] == [zlib.crc32(b) for b in batch]
+    monkeypatch.setenv("ZH_COMPRESS_FIRST_CAP", "64")
+    assert eng.compress_batch(batch, 1, oracle.dfGzip) == want
+    assert _compress_batch_crc32(eng, batch, 1, oracle.dfDeflate) == want_crc
+    pc.check_compress_identical(eng, batch, levels=(1,), formats=(oracle.dfGzip, oracle.dfDeflate))
+
+
 def test_emu_trailer_behind_the_emission(eng, monkeypatch):
     """Large batches write the trailer with a kernel of its own behind the emission (the checksum runs beside both the
     code builder and the emission: zh_plan_run.hip); ZH_TRAILER_LATE=1 takes the tests' small ones that way too."""

@@ -1,7 +1,7 @@
 """The kernel sources and the host side of the library under AddressSanitizer: the g++ / emulator build of
 zippy_amd/csrc (tests/hipemu) with -fsanitize=address, a run through every family of kernels -- both BestSpeed
 parses and code builders, a chain level, both inflate paths on fixtures, damaged headers and streams, the `_into`
-calls, plans whose scratch is forced into ranges, large streams on many workgroups with planted false block
+calls, the batch writers with and without the compress retry, plans whose scratch is forced into ranges, large streams on many workgroups with planted false block
 starts -- in a child process (the sanitizer runtime has to be the first
 library the process loads).  `__shared__` arrays are plain memory under the emulator, so an index that runs off
 one is an error here where the hardware would read its neighbour."""
@@ -30,6 +30,20 @@ for mode in (0, 1):
     pc.check_errors_match_oracle(eng, pc.mutated_fixtures(12, seed=3, max_len=40000))
 eng.set_inflate_mode(-1)
 pc.check_batch_into(eng)
+# the batch writers, with and without the compress step's retry (its slots change hands between functions)
+import os, tar_writer_model as twm, zip_v1_writer_model as zm
+tars = [[("t/a", inputs[0][:5000]), ("t/b", inputs[1][:3000])], [], [("u", b"x" * 700)]]
+zips = [[("z/a", inputs[0][:5000]), ("z/", b""), ("z/b", inputs[1][:3000])], [("d/", b"x")], [("e", b"")]]
+for cap in (None, "64"):
+    if cap:
+        os.environ["ZH_COMPRESS_FIRST_CAP"] = cap
+    gz, sts = eng.create_tars(tars, oracle.dfGzip, 1)
+    assert sts == [twm.status(t) for t in tars], sts
+    assert gz == [oracle.compress(twm.image(t), 1, oracle.dfGzip, fname_len=0) if s == 0 else None
+                  for t, s in zip(tars, sts)], cap
+    assert eng.write_zips(zips) == ([zm.image(z) if zm.status(z) == 0 else None for z in zips],
+                                    [zm.status(z) for z in zips]), cap
+os.environ.pop("ZH_COMPRESS_FIRST_CAP")
 # large streams on many workgroups: the search queues, the two candidates a segment, sub-starts, the repair round
 # (a found start that is none planted in the middle of a block and right before a real block start)
 import os, zlib

@@ -83,6 +83,48 @@ def test_emu_tar_call_level_errors(eng):
     assert eng.create_tars([], TAR_PLAIN) == ([], [])
 
 
+def _raw_tar_call(eng, entries, first, data_format, level):
+    """zh_tar_create_batch through ctypes with a hand-made table, poisoned outputs -> (rc, dsts, dst_lens, statuses)"""
+    import ctypes as c
+    from zippy_amd._binding import TarNewEntry
+    n = len(first) - 1
+    arr = None if entries is None else (TarNewEntry * len(entries))(*entries)
+    dsts = (c.c_void_p * n)(*[0xDEAD000 + 16 * t for t in range(n)])
+    dlens, sts = (c.c_size_t * n)(*[12345] * n), (c.c_int32 * n)(*[77] * n)
+    rc = eng.lib.zh_tar_create_batch(eng._h, arr, (c.c_size_t * len(first))(*first), n, data_format, level, dsts,
+                                     dlens, sts)
+    return rc, list(dsts), list(dlens), list(sts)
+
+
+def _tar_entry(path, contents, path_len=None, length=None):
+    """a TarNewEntry with the pointers as given (None: NULL) and the lengths of the data unless given"""
+    import ctypes as c
+    from zippy_amd._binding import TarNewEntry
+    return TarNewEntry(path, len(path or b"") if path_len is None else path_len,
+                       c.cast(c.c_char_p(contents), c.c_void_p) if contents else None,
+                       len(contents or b"") if length is None else length, b"0", 0)
+
+
+_GOOD = [(b"a", b"xy"), (b"b", b"z")]
+
+
+@pytest.mark.parametrize("table,first,fmt,level,rc", [
+    (_GOOD, [0, 2, 1], TAR_PLAIN, 1, twm.ZH_ERR_ARGUMENT),  # decreasing first[]
+    (_GOOD, [0, 2, 1], dfGzip, 1, twm.ZH_ERR_ARGUMENT),
+    (None, [0, 0, 1], dfGzip, 1, twm.ZH_ERR_ARGUMENT),  # entries == NULL with a non-zero count
+    ([(b"a", b"xy"), (None, b"z", 1)], [0, 1, 2], TAR_PLAIN, 1, twm.ZH_ERR_ARGUMENT),  # path NULL, path_len 1
+    ([(b"a", b"xy"), (b"b", None, None, 5)], [0, 1, 2], dfGzip, 1, twm.ZH_ERR_ARGUMENT),  # contents NULL, len 5
+    (_GOOD, [0, 2, 1], dfZlib, 1, 2),  # the format is checked before the table (ZH_ERR_INVALID_FORMAT)
+    (_GOOD, [0, 2, 1], dfGzip, 10, 1),  # ... and a .tar.gz's level (ZH_ERR_INVALID_LEVEL)
+    (_GOOD, [0, 2, 1], TAR_PLAIN, 10, twm.ZH_ERR_ARGUMENT),  # (a plain image has no level)
+    (None, [0, 1], dfZlib, 10, 2),
+])
+def test_emu_tar_c_level_refusals(eng, table, first, fmt, level, rc):
+    entries = None if table is None else [_tar_entry(*e) for e in table]
+    n = len(first) - 1
+    assert _raw_tar_call(eng, entries, first, fmt, level) == (rc, [None] * n, [0] * n, [0] * n)
+
+
 def _batch():
     good = [
         [("one.txt", b"hello")],
@@ -110,6 +152,18 @@ def test_emu_tar_batch_mixes_good_and_bad(eng):
     for t, out, st in zip(tars, gz, sts):
         if st == 0:
             assert out == eng.create_tar(t, dfGzip, 1) == oracle.compress(twm.image(t), 1, oracle.dfGzip, fname_len=0)
+
+
+def test_emu_tar_gzip_first_cap_retry(eng, monkeypatch):
+    """ZH_COMPRESS_FIRST_CAP=64: the images of a mixed batch outgrow their first slots and are compressed again into
+    zh_compress_bound slots -- the same bytes as without it, the oracle's compress() of the model's images"""
+    tars = _batch()
+    want = eng.create_tars(tars, dfGzip, 1)
+    monkeypatch.setenv("ZH_COMPRESS_FIRST_CAP", "64")
+    assert eng.create_tars(tars, dfGzip, 1) == want
+    assert want[1] == [twm.status(t) for t in tars]
+    for t, out, st in zip(tars, want[0], want[1]):
+        assert out == (oracle.compress(twm.image(t), 1, oracle.dfGzip, fname_len=0) if st == 0 else None)
 
 
 @pytest.mark.parametrize("level", [-2, 0, 1, -1, 9])

@@ -95,6 +95,44 @@ def test_emu_zip_call_level_errors(eng):
     assert eng.write_zips([]) == ([], [])
 
 
+def _raw_zip_call(eng, entries, first, level):
+    """zh_zip_write_batch through ctypes with a hand-made table, poisoned outputs -> (rc, dsts, dst_lens, statuses)"""
+    import ctypes as c
+    from zippy_amd._binding import ZipNewEntry
+    n = len(first) - 1
+    arr = None if entries is None else (ZipNewEntry * len(entries))(*entries)
+    dsts = (c.c_void_p * n)(*[0xDEAD000 + 16 * t for t in range(n)])
+    dlens, sts = (c.c_size_t * n)(*[12345] * n), (c.c_int32 * n)(*[77] * n)
+    rc = eng.lib.zh_zip_write_batch(eng._h, arr, (c.c_size_t * len(first))(*first), n, level, dsts, dlens, sts)
+    return rc, list(dsts), list(dlens), list(sts)
+
+
+def _zip_entry(path, contents, path_len=None, length=None):
+    """a ZipNewEntry with the pointers as given (None: NULL) and the lengths of the data unless given"""
+    import ctypes as c
+    from zippy_amd._binding import ZipNewEntry
+    return ZipNewEntry(path, len(path or b"") if path_len is None else path_len,
+                       c.cast(c.c_char_p(contents), c.c_void_p) if contents else None,
+                       len(contents or b"") if length is None else length, 0, 0, 0)
+
+
+_GOOD = [(b"a", b"xy"), (b"b", b"z")]
+
+
+@pytest.mark.parametrize("table,first,level,rc", [
+    (_GOOD, [0, 2, 1], 1, zm.ZH_ERR_ARGUMENT),  # decreasing first[]
+    (None, [0, 0, 1], 1, zm.ZH_ERR_ARGUMENT),  # entries == NULL with a non-zero count
+    ([(b"a", b"xy"), (None, b"z", 1)], [0, 1, 2], 1, zm.ZH_ERR_ARGUMENT),  # path NULL, path_len 1
+    ([(b"a", b"xy"), (b"b", None, None, 5)], [0, 1, 2], -1, zm.ZH_ERR_ARGUMENT),  # contents NULL, len 5
+    (_GOOD, [0, 2, 1], 10, 1),  # the level is checked before the table (ZH_ERR_INVALID_LEVEL)
+    (None, [0, 1], -3, 1),
+])
+def test_emu_zip_c_level_refusals(eng, table, first, level, rc):
+    entries = None if table is None else [_zip_entry(*e) for e in table]
+    n = len(first) - 1
+    assert _raw_zip_call(eng, entries, first, level) == (rc, [None] * n, [0] * n, [0] * n)
+
+
 def test_emu_zip_batch_mixes_good_and_bad(eng):
     good = [[("one.txt", b"hello")],
             [("f%d" % n, _blob(n, n)) for n in SIZES],
@@ -111,6 +149,17 @@ def test_emu_zip_batch_mixes_good_and_bad(eng):
     # the good ones alone: the same bytes
     alone, sts = eng.write_zips(good)
     assert sts == [0] * 4 and alone == [o for o in outs if o is not None]
+
+
+def test_emu_zip_first_cap_retry(eng, monkeypatch):
+    """ZH_COMPRESS_FIRST_CAP=64: the larger contents of a mixed batch outgrow their first slots and are compressed again
+    into zh_compress_bound slots (their CRC-32s with them) -- the same bytes as without it, the model's"""
+    zips = [[("f%d" % n, _blob(n, n)) for n in SIZES], [], [("d/", (b"", True, 1, 1)), ("d/x", _blob(1000, 3))],
+            [("only/", (b"", True, 0, 0))], [("t.txt", synth.corpus_file("alice29.txt")[:30000])]]
+    want = eng.write_zips(zips)
+    monkeypatch.setenv("ZH_COMPRESS_FIRST_CAP", "64")
+    assert eng.write_zips(zips) == want
+    assert want == ([zm.image(z) if z else None for z in zips], [zm.status(z) for z in zips])
 
 
 def test_emu_zip_post_compression_refusal(eng, monkeypatch):

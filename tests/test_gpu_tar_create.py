@@ -71,6 +71,21 @@ def test_gpu_tar_256_tarballs_one_call(eng):
         assert out == oracle.compress(img, 1, oracle.dfGzip, fname_len=0)
 
 
+def test_gpu_tar_gzip_first_cap_retry(eng, monkeypatch):
+    """ZH_COMPRESS_FIRST_CAP=4096: the larger images of the call outgrow their first slots and are compressed again
+    into zh_compress_bound slots, the small ones keep theirs -- the oracle's bytes either way"""
+    rng = random.Random(4096)
+    pool = synth.gen_batch("mix", 1, 1 << 20)[0].tobytes()
+    tars = [_random_entries(rng, rng.randrange(1, 30), rng.choice([0, 600, 70000]), pool, "c%d" % t) for t in range(64)]
+    monkeypatch.setenv("ZH_COMPRESS_FIRST_CAP", "4096")
+    outs, sts = eng.create_tars(tars, dfGzip, 1)
+    assert sts == [0] * 64
+    sizes = [len(o) for o in outs]
+    assert min(sizes) <= 4096 < max(sizes)
+    for t, out in zip(tars, outs):
+        assert out == oracle.compress(twm.image(t), 1, oracle.dfGzip, fname_len=0)
+
+
 def test_gpu_tar_100k_small_entries(eng):
     """headers dominate: 100 000 entries of 0-600 bytes"""
     rng = random.Random(7)

@@ -80,6 +80,19 @@ def test_gpu_zip_256_archives_one_call(eng):
         assert out == zm.image(z)
 
 
+def test_gpu_zip_first_cap_retry(eng, monkeypatch):
+    """ZH_COMPRESS_FIRST_CAP=4096: the larger contents of the call outgrow their first slots and are compressed again
+    (with their CRC-32s) into zh_compress_bound slots, the small ones keep theirs -- the model's archives either way"""
+    rng = random.Random(4096)
+    pool = synth.gen_batch("mix", 1, 1 << 20)[0].tobytes()
+    zips = [_random_entries(rng, rng.randrange(1, 30), rng.choice([0, 600, 70000]), pool, "c%d" % t) for t in range(64)]
+    monkeypatch.setenv("ZH_COMPRESS_FIRST_CAP", "4096")
+    outs, sts = eng.write_zips(zips)
+    assert sts == [0] * 64
+    for z, out in zip(zips, outs):
+        assert out == zm.image(z)
+
+
 def test_gpu_zip_65535_tiny_entries(eng):
     entries = [("t/%05d" % i, (bytes([i & 255]) * (i % 7), False, i & 0xFFFF, 0x5521)) for i in range(65535)]
     assert eng.write_zip(entries) == zm.image(entries)

@@ -366,6 +366,19 @@ def _zip_entries(entries):
     return out
 
 
+def _writer_table(entry_type, groups, fill):
+    """groups: lists of entry tuples -> (entry array, first[], number of groups, the entry tuples); fill(entry, *tuple)
+    sets one entry"""
+    flat = [e for g in groups for e in g]
+    arr = (entry_type * max(1, len(flat)))()
+    for i, e in enumerate(flat):
+        fill(arr[i], *e)
+    first = [0]
+    for g in groups:
+        first.append(first[-1] + len(g))
+    return arr, (_c.c_size_t * len(first))(*first), len(groups), flat
+
+
 def _buffer_address(obj):
     """-> (address or None, length, the object that keeps the memory alive)"""
     if not isinstance(obj, bytes):
@@ -541,32 +554,14 @@ class Engine:
     @staticmethod
     def prepare_tars(tarballs):
         """The C arrays of zh_tar_create_batch for `tarballs` (kept alive by the returned tuple)."""
-        groups = [_tar_entries(t) for t in tarballs]
-        flat = [e for g in groups for e in g]
-        arr = (TarNewEntry * max(1, len(flat)))()
-        for i, (p, c, k, m) in enumerate(flat):
-            arr[i].path, arr[i].path_len = p, len(p)
-            arr[i].contents = _c.cast(_c.c_char_p(c), _c.c_void_p) if c else None
-            arr[i].len, arr[i].kind, arr[i].mtime = len(c), k, m
-        first = [0]
-        for g in groups:
-            first.append(first[-1] + len(g))
-        return arr, (_c.c_size_t * len(first))(*first), len(groups), flat
+        def fill(e, p, c, k, m):
+            e.path, e.path_len = p, len(p)
+            e.contents = _c.cast(_c.c_char_p(c), _c.c_void_p) if c else None
+            e.len, e.kind, e.mtime = len(c), k, m
+        return _writer_table(TarNewEntry, [_tar_entries(t) for t in tarballs], fill)
 
     def create_tars_prepared(self, prepared, data_format=dfGzip, level=DefaultCompression):
-        arr, c_first, n, _ = prepared
-        dsts, dlens, sts = (_c.c_void_p * max(1, n))(), (_c.c_size_t * max(1, n))(), (_c.c_int32 * max(1, n))()
-        rc = self.lib.zh_tar_create_batch(self._h, arr, c_first, n, data_format, level, dsts, dlens, sts)
-        outs = []
-        try:
-            for t in range(n):
-                outs.append(_c.string_at(dsts[t], dlens[t]) if dsts[t] and sts[t] == 0 else None)
-        finally:
-            for t in range(n):
-                if dsts[t]:
-                    self.lib.zh_free(dsts[t])
-        self._check(rc)
-        return outs, list(sts)[:n]
+        return self._run_writer(self.lib.zh_tar_create_batch, prepared, data_format, level)
 
     def create_tar(self, entries, data_format=dfGzip, level=DefaultCompression):
         """One tarball's bytes; raises ZippyError on failure."""
@@ -581,24 +576,24 @@ class Engine:
     @staticmethod
     def prepare_zips(archives):
         """The C arrays of zh_zip_write_batch for `archives` (kept alive by the returned tuple)."""
-        groups = [_zip_entries(a) for a in archives]
-        flat = [e for g in groups for e in g]
-        arr = (ZipNewEntry * max(1, len(flat)))()
         keep = []
-        for i, (p, c, is_dir, t, d) in enumerate(flat):
+
+        def fill(e, p, c, is_dir, t, d):
             addr, n, k = _buffer_address(c)
             keep.append(k)
-            arr[i].path, arr[i].path_len, arr[i].contents, arr[i].len = p, len(p), addr, n
-            arr[i].is_directory, arr[i].dos_time, arr[i].dos_date = int(is_dir), t & 0xFFFF, d & 0xFFFF
-        first = [0]
-        for g in groups:
-            first.append(first[-1] + len(g))
-        return arr, (_c.c_size_t * len(first))(*first), len(groups), (flat, keep)
+            e.path, e.path_len, e.contents, e.len = p, len(p), addr, n
+            e.is_directory, e.dos_time, e.dos_date = int(is_dir), t & 0xFFFF, d & 0xFFFF
+        arr, first, n, flat = _writer_table(ZipNewEntry, [_zip_entries(a) for a in archives], fill)
+        return arr, first, n, (flat, keep)
 
     def write_zips_prepared(self, prepared, level=DefaultCompression):
+        return self._run_writer(self.lib.zh_zip_write_batch, prepared, level)
+
+    def _run_writer(self, fn, prepared, *args):
+        """fn(ctx, entries, first, n, *args, dsts, dst_lens, statuses) of a batch writer -> (list of bytes | None, statuses)"""
         arr, c_first, n, _ = prepared
         dsts, dlens, sts = (_c.c_void_p * max(1, n))(), (_c.c_size_t * max(1, n))(), (_c.c_int32 * max(1, n))()
-        rc = self.lib.zh_zip_write_batch(self._h, arr, c_first, n, level, dsts, dlens, sts)
+        rc = fn(self._h, arr, c_first, n, *args, dsts, dlens, sts)
         outs = []
         try:
             for t in range(n):

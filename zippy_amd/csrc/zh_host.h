@@ -321,3 +321,56 @@ ZH_INTERNAL int zhh_upload_slices(zh_ctx* ctx, const void* const* srcs, const st
 ZH_INTERNAL int zhh_download(zh_ctx* ctx, const uint8_t* d_dst, size_t n, const std::vector<uint64_t>& doff,
                              const std::vector<uint64_t>& olen, const std::vector<char>& take, void** dsts,
                              size_t* dst_lens, int32_t* statuses);
+// host byte spans packed into one device buffer, each at a 16-byte aligned offset off[k], in one upload
+ZH_INTERNAL int zhh_upload_spans(zh_ctx* ctx, std::initializer_list<std::pair<const void*, size_t>> spans, DevBuf& dev,
+                                 std::vector<uint64_t>& off);
+// One compress plan over the device buffers d_src + soff[i] (slen[i] bytes each), run once more with every output
+// slot at zh_compress_bound when a buffer did not fit its first slot (the first attempt's slots are freed before the
+// second's are allocated).  On ZH_OK, dst holds the last attempt's slots and doff / clen / cst its results (crcs, if
+// given: the CRC-32 of every buffer).  n == 0 does nothing.
+ZH_INTERNAL int zhh_compress(zh_ctx* ctx, const uint8_t* d_src, const std::vector<uint64_t>& soff,
+                             const std::vector<uint64_t>& slen, int level, int fmt, uint32_t* crcs, DevBuf& dst,
+                             std::vector<uint64_t>& doff, std::vector<uint64_t>& clen, std::vector<int32_t>& cst);
+
+// ---- the batch writers (zh_tar_create_batch, zh_zip_write_batch) ----
+// Their call-level checks, in this order: the pointers; dsts / dst_lens / statuses cleared; `bad_call` (the code of a
+// bad level or format, ZH_OK if none); then the table -- first[] ascending, entries there, every path and contents
+// there.  The caller goes on only on ZH_OK with n > 0.
+template <class Entry>
+static int writer_checks(zh_ctx* ctx, const Entry* entries, const size_t* first, size_t n, int bad_call, void** dsts,
+                         size_t* dst_lens, int32_t* statuses) {
+  if (!ctx || (n && (!first || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
+  for (size_t t = 0; t < n; t++) {
+    dsts[t] = nullptr;
+    dst_lens[t] = 0;
+    statuses[t] = ZH_OK;
+  }
+  if (bad_call || !n) return bad_call;
+  for (size_t t = 0; t < n; t++)
+    if (first[t + 1] < first[t]) return ZH_ERR_ARGUMENT;
+  if (first[n] > first[0] && !entries) return ZH_ERR_ARGUMENT;
+  for (size_t i = first[0]; i < first[n]; i++)
+    if ((!entries[i].path && entries[i].path_len) || (!entries[i].contents && entries[i].len)) return ZH_ERR_ARGUMENT;
+  return ZH_OK;
+}
+// Their results: the device ranges [off[k], + len[k]) of d_img whose st[k] is ZH_OK into fresh buffers, handed out
+// with st[k] at batch position pos[k].  Nothing is handed out from a failed call.
+static inline int writer_hand_out(zh_ctx* ctx, const uint8_t* d_img, const std::vector<size_t>& pos,
+                                  const std::vector<uint64_t>& off, const std::vector<uint64_t>& len,
+                                  std::vector<int32_t> st, void** dsts, size_t* dst_lens, int32_t* statuses) {
+  const size_t n = pos.size();
+  std::vector<void*> odst(n, nullptr);
+  std::vector<size_t> olen(n, 0);
+  std::vector<char> take(n);
+  for (size_t k = 0; k < n; k++) take[k] = st[k] == ZH_OK;
+  if (const int e = zhh_download(ctx, d_img, n, off, len, take, odst.data(), olen.data(), st.data())) {
+    for (void* p : odst) free(p);
+    return e;
+  }
+  for (size_t k = 0; k < n; k++) {
+    dsts[pos[k]] = odst[k];
+    dst_lens[pos[k]] = olen[k];
+    statuses[pos[k]] = st[k];
+  }
+  return ZH_OK;
+}

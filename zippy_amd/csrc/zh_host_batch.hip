@@ -192,6 +192,24 @@ int upload_slices(zh_ctx* ctx, hipStream_t stream, const void* const* srcs,
   }
   return ZH_OK;
 }
+// Output slots of a compress plan over buffers of len[0, n) bytes, 256-aligned in one range: doff / dcap, returns its
+// size.  A retry's slot is zh_compress_bound; a first attempt's is typical_cap, or ZH_COMPRESS_FIRST_CAP bytes when
+// that is smaller (a test aid, read at each call, so that the tests reach the retry and the pipelined fallback).
+uint64_t layout_dst(const uint64_t* len, size_t n, int fmt, bool retry, std::vector<uint64_t>& doff,
+                    std::vector<uint64_t>& dcap) {
+  const char* e = getenv("ZH_COMPRESS_FIRST_CAP");
+  const long long first_cap = e ? atoll(e) : 0;
+  doff.resize(n);
+  dcap.resize(n);
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    doff[i] = total;
+    dcap[i] = retry ? zh_compress_bound(len[i], fmt) : typical_cap(len[i], fmt);
+    if (!retry && first_cap > 0) dcap[i] = std::min<uint64_t>(dcap[i], (uint64_t)first_cap);
+    total += (dcap[i] + 255) & ~(uint64_t)255;
+  }
+  return total;
+}
 // Pack host buffers into one device allocation.
 int upload(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n, DevBuf& dev,
            std::vector<uint64_t>& off, std::vector<uint64_t>& len64) {
@@ -387,13 +405,7 @@ int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t*
     q.i0 = cut[g];
     q.n = cut[g + 1] - cut[g];
     q.src_total = layout_slices(lens + q.i0, q.n, q.soff, q.slen);
-    q.doff.resize(q.n);
-    q.dcap.resize(q.n);
-    for (size_t i = 0; i < q.n; i++) {
-      q.doff[i] = q.dst_total;
-      q.dcap[i] = typical_cap(lens[q.i0 + i], data_format);
-      q.dst_total += (q.dcap[i] + 255) & ~(uint64_t)255;
-    }
+    q.dst_total = layout_dst(q.slen.data(), q.n, data_format, false, q.doff, q.dcap);
     set_src[g & 1] = std::max(set_src[g & 1], q.src_total);
     set_dst[g & 1] = std::max(set_dst[g & 1], q.dst_total);
   }
@@ -501,43 +513,18 @@ static int compress_batch_impl(zh_ctx* ctx, const void* const* srcs, const size_
   if (st) return st;
   tr.mark(ctx, "compress: upload");
 
-  for (int attempt = 0; attempt < 2; attempt++) {
-    std::vector<uint64_t> doff(n), dcap(n);
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-      doff[i] = total;
-      dcap[i] = attempt == 0 ? typical_cap(lens[i], data_format) : zh_compress_bound(lens[i], data_format);
-      total += (dcap[i] + 255) & ~(uint64_t)255;
-    }
-    DevBuf d_dst;
-    if (dev_alloc(ctx, d_dst, total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    PlanGuard pg;
-    st = zh_plan_compress(ctx, n, soff.data(), slen.data(), doff.data(), dcap.data(), level,
-                          data_format, &pg.p);
-    if (st) return st;
-    tr.mark(ctx, "compress: alloc + plan");
-    if (crcs) zh_plan_request_crc32(pg.p, 1);
-    st = zh_plan_run(pg.p, d_src.p, d_dst.p);
-    if (st) return st;
-    std::vector<uint64_t> olen(n);
-    std::vector<int32_t> ost(n);
-    st = zh_plan_results(pg.p, olen.data(), ost.data());
-    if (st) return st;
-    tr.mark(ctx, "compress: kernels");
-    if (crcs && (st = zh_plan_crc32(pg.p, crcs))) return st;
-    bool retry = false;
-    for (size_t i = 0; i < n; i++)
-      if (ost[i] == ZH_ERR_DST_TOO_SMALL) retry = true;
-    if (retry && attempt == 0) continue;
-    std::vector<char> take(n);
-    for (size_t i = 0; i < n; i++) {
-      statuses[i] = ost[i];
-      take[i] = ost[i] == ZH_OK;
-    }
-    if ((st = download(ctx, d_dst.p, n, doff, olen, take, dsts, dst_lens, statuses))) return st;
-    tr.mark(ctx, "compress: download");
-    break;
+  DevBuf d_dst;
+  std::vector<uint64_t> doff, olen;
+  std::vector<int32_t> ost;
+  if ((st = zhh_compress(ctx, d_src.p, soff, slen, level, data_format, crcs, d_dst, doff, olen, ost))) return st;
+  tr.mark(ctx, "compress: kernels");
+  std::vector<char> take(n);
+  for (size_t i = 0; i < n; i++) {
+    statuses[i] = ost[i];
+    take[i] = ost[i] == ZH_OK;
   }
+  if ((st = download(ctx, d_dst.p, n, doff, olen, take, dsts, dst_lens, statuses))) return st;
+  tr.mark(ctx, "compress: download");
   return ZH_OK;
 }
 
@@ -937,4 +924,44 @@ int zhh_download(zh_ctx* ctx, const uint8_t* d_dst, size_t n, const std::vector<
                  const std::vector<uint64_t>& olen, const std::vector<char>& take, void** dsts, size_t* dst_lens,
                  int32_t* statuses) {
   return download(ctx, d_dst, n, doff, olen, take, dsts, dst_lens, statuses);
+}
+int zhh_upload_spans(zh_ctx* ctx, std::initializer_list<std::pair<const void*, size_t>> spans, DevBuf& dev,
+                     std::vector<uint64_t>& off) {
+  size_t total = 0;
+  for (const auto& s : spans) {
+    off.push_back(total);
+    total += (s.second + 15) & ~(size_t)15;
+  }
+  std::vector<uint8_t> host(total);
+  size_t i = 0;
+  for (const auto& s : spans)
+    if (const size_t at = off[i++]; s.second) memcpy(host.data() + at, s.first, s.second);
+  const void* src = host.data();
+  std::vector<uint64_t> o, l;
+  return upload(ctx, &src, &total, 1, dev, o, l);
+}
+int zhh_compress(zh_ctx* ctx, const uint8_t* d_src, const std::vector<uint64_t>& soff,
+                 const std::vector<uint64_t>& slen, int level, int fmt, uint32_t* crcs, DevBuf& dst,
+                 std::vector<uint64_t>& doff, std::vector<uint64_t>& clen, std::vector<int32_t>& cst) {
+  const size_t n = soff.size();
+  clen.assign(n, 0);
+  cst.assign(n, ZH_OK);
+  for (int attempt = 0; n && attempt < 2; attempt++) {
+    std::vector<uint64_t> dcap;
+    const uint64_t total = layout_dst(slen.data(), n, fmt, attempt == 1, doff, dcap);
+    if (dst.p) {  // (the first attempt's slots: synchronised by zh_plan_results)
+      ctx_free(ctx, dst.p);
+      dst.p = nullptr;
+    }
+    if (dev_alloc(ctx, dst, total + 256) != hipSuccess) return ZH_ERR_NOMEM;
+    PlanGuard pg;
+    int st = zh_plan_compress(ctx, n, soff.data(), slen.data(), doff.data(), dcap.data(), level, fmt, &pg.p);
+    if (st) return st;
+    if (crcs) zh_plan_request_crc32(pg.p, 1);
+    if ((st = zh_plan_run(pg.p, d_src, dst.p)) || (st = zh_plan_results(pg.p, clen.data(), cst.data())) ||
+        (crcs && (st = zh_plan_crc32(pg.p, crcs))))
+      return st;
+    if (std::find(cst.begin(), cst.end(), ZH_ERR_DST_TOO_SMALL) == cst.end()) break;
+  }
+  return ZH_OK;
 }

@@ -118,20 +118,11 @@ __global__ __launch_bounds__(256) void zh_tar_header_kernel(uint8_t* __restrict_
 
 extern "C" int zh_tar_create_batch(zh_ctx* ctx, const zh_tar_new_entry* entries, const size_t* first, size_t n_tar,
                                    int data_format, int level, void** dsts, size_t* dst_lens, int32_t* statuses) {
-  if (!ctx || (n_tar && (!first || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_tar; t++) {
-    dsts[t] = nullptr;
-    dst_lens[t] = 0;
-    statuses[t] = ZH_OK;
-  }
-  if (data_format != ZH_TAR_PLAIN && data_format != ZH_DF_GZIP) return ZH_ERR_INVALID_FORMAT;
-  if (data_format == ZH_DF_GZIP && (level < -2 || level > 9)) return ZH_ERR_INVALID_LEVEL;
-  if (!n_tar) return ZH_OK;
-  for (size_t t = 0; t < n_tar; t++)
-    if (first[t + 1] < first[t]) return ZH_ERR_ARGUMENT;
-  if (first[n_tar] > first[0] && !entries) return ZH_ERR_ARGUMENT;
-  for (size_t i = first[0]; i < first[n_tar]; i++)
-    if ((!entries[i].path && entries[i].path_len) || (!entries[i].contents && entries[i].len)) return ZH_ERR_ARGUMENT;
+  const int bad_call = data_format != ZH_TAR_PLAIN && data_format != ZH_DF_GZIP ? ZH_ERR_INVALID_FORMAT
+                       : data_format == ZH_DF_GZIP && (level < -2 || level > 9) ? ZH_ERR_INVALID_LEVEL
+                                                                                  : ZH_OK;
+  if (const int st = writer_checks(ctx, entries, first, n_tar, bad_call, dsts, dst_lens, statuses); st || !n_tar)
+    return st;
 
   // ---- checks and layout: tarball t's image is [img_off, + img_len) of one buffer, entries back to back ----
   std::vector<ZhTarHdrDesc> descs;
@@ -196,16 +187,13 @@ extern "C" int zh_tar_create_batch(zh_ctx* ctx, const zh_tar_new_entry* entries,
   Trace tr;
 
   // ---- descriptors, trailer offsets and names in one upload; the contents straight to their places ----
-  const size_t desc_bytes = descs.size() * sizeof(ZhTarHdrDesc), trail_bytes = trailers.size() * 8;
-  std::vector<uint8_t> meta(desc_bytes + trail_bytes + pool.size());
-  memcpy(meta.data(), descs.data(), desc_bytes);
-  memcpy(meta.data() + desc_bytes, trailers.data(), trail_bytes);
-  if (!pool.empty()) memcpy(meta.data() + desc_bytes + trail_bytes, pool.data(), pool.size());
-  const void* meta_src = meta.data();
-  const size_t meta_len = meta.size();
   DevBuf d_meta, d_img;
-  std::vector<uint64_t> moff, mlen;
-  int st = zhh_upload(ctx, &meta_src, &meta_len, 1, d_meta, moff, mlen);
+  std::vector<uint64_t> moff;
+  int st = zhh_upload_spans(ctx,
+                            {{descs.data(), descs.size() * sizeof(ZhTarHdrDesc)},
+                             {trailers.data(), trailers.size() * 8},
+                             {pool.data(), pool.size()}},
+                            d_meta, moff);
   if (st) return st;
   if (dev_alloc(ctx, d_img, o + 256) != hipSuccess) return ZH_ERR_NOMEM;
   if ((st = zhh_upload_slices(ctx, data_src.data(), data_off, data_len, o, d_img.p))) return st;
@@ -215,59 +203,24 @@ extern "C" int zh_tar_create_batch(zh_ctx* ctx, const zh_tar_new_entry* entries,
   uint8_t* const img = d_img.p;  // (plain pointers into the launch: a DevBuf is not to be copied)
   const uint8_t* const m = d_meta.p;
   hipLaunchKernelGGL(zh_tar_header_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, ctx->stream, img,
-                     reinterpret_cast<const ZhTarHdrDesc*>(m), (uint64_t)descs.size(),
-                     reinterpret_cast<const uint64_t*>(m + desc_bytes), (uint64_t)trailers.size(),
-                     m + desc_bytes + trail_bytes);
+                     reinterpret_cast<const ZhTarHdrDesc*>(m + moff[0]), (uint64_t)descs.size(),
+                     reinterpret_cast<const uint64_t*>(m + moff[1]), (uint64_t)trailers.size(), m + moff[2]);
   ZH_HIP(ctx, hipGetLastError());
   tr.mark(ctx, "tar: headers");
 
-  std::vector<void*> odst(n_ok, nullptr);
-  std::vector<size_t> olen_out(n_ok, 0);
-  std::vector<int32_t> ost_out(n_ok, ZH_OK);
   if (data_format == ZH_TAR_PLAIN) {
-    st = zhh_download(ctx, d_img.p, n_ok, img_off, img_len, std::vector<char>(n_ok, 1), odst.data(),
-                      olen_out.data(), ost_out.data());
-  } else {  // compress(data, level, dfGzip) of every image, one plan (the sizing of zh_compress_batch)
-    for (int attempt = 0; attempt < 2; attempt++) {
-      std::vector<uint64_t> doff(n_ok), dcap(n_ok);
-      uint64_t total = 0;
-      for (size_t k = 0; k < n_ok; k++) {
-        doff[k] = total;
-        dcap[k] = attempt == 0 ? typical_cap(img_len[k], ZH_DF_GZIP) : zh_compress_bound(img_len[k], ZH_DF_GZIP);
-        total += (dcap[k] + 255) & ~(uint64_t)255;
-      }
-      DevBuf d_dst;
-      if (dev_alloc(ctx, d_dst, total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-      PlanGuard pg;
-      if ((st = zh_plan_compress(ctx, n_ok, img_off.data(), img_len.data(), doff.data(), dcap.data(), level,
-                                 ZH_DF_GZIP, &pg.p)))
-        return st;
-      if ((st = zh_plan_run(pg.p, d_img.p, d_dst.p))) return st;
-      std::vector<uint64_t> clen(n_ok);
-      std::vector<int32_t> cst(n_ok);
-      if ((st = zh_plan_results(pg.p, clen.data(), cst.data()))) return st;
-      tr.mark(ctx, "tar: compress");
-      bool retry = false;
-      for (size_t k = 0; k < n_ok; k++) retry |= cst[k] == ZH_ERR_DST_TOO_SMALL;
-      if (retry && attempt == 0) continue;
-      std::vector<char> take(n_ok);
-      for (size_t k = 0; k < n_ok; k++) {
-        ost_out[k] = cst[k];
-        take[k] = cst[k] == ZH_OK;
-      }
-      st = zhh_download(ctx, d_dst.p, n_ok, doff, clen, take, odst.data(), olen_out.data(), ost_out.data());
-      break;
-    }
+    st = writer_hand_out(ctx, d_img.p, ok, img_off, img_len, std::vector<int32_t>(n_ok, ZH_OK), dsts, dst_lens,
+                         statuses);
+  } else {  // compress(data, level, dfGzip) of every image, one plan
+    DevBuf d_dst;
+    std::vector<uint64_t> doff, clen;
+    std::vector<int32_t> cst;
+    if ((st = zhh_compress(ctx, d_img.p, img_off, img_len, level, ZH_DF_GZIP, nullptr, d_dst, doff, clen, cst)))
+      return st;
+    tr.mark(ctx, "tar: compress");
+    st = writer_hand_out(ctx, d_dst.p, ok, doff, clen, cst, dsts, dst_lens, statuses);
   }
-  if (st) {
-    for (void* p : odst) free(p);
-    return st;
-  }
+  if (st) return st;
   tr.mark(ctx, "tar: download");
-  for (size_t k = 0; k < n_ok; k++) {
-    dsts[ok[k]] = odst[k];
-    dst_lens[ok[k]] = olen_out[k];
-    statuses[ok[k]] = ost_out[k];
-  }
   return ZH_OK;
 }

@@ -225,26 +225,16 @@ uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) & ~(a - 1); }
 
 extern "C" int zh_zip_write_batch(zh_ctx* ctx, const zh_zip_new_entry* entries, const size_t* first, size_t n_zip,
                                   int level, void** dsts, size_t* dst_lens, int32_t* statuses) {
-  if (!ctx || (n_zip && (!first || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_zip; t++) {
-    dsts[t] = nullptr;
-    dst_lens[t] = 0;
-    statuses[t] = ZH_OK;
-  }
-  if (level < -2 || level > 9) return ZH_ERR_INVALID_LEVEL;
-  if (!n_zip) return ZH_OK;
-  for (size_t t = 0; t < n_zip; t++)
-    if (first[t + 1] < first[t]) return ZH_ERR_ARGUMENT;
-  if (first[n_zip] > first[0] && !entries) return ZH_ERR_ARGUMENT;
-  for (size_t i = first[0]; i < first[n_zip]; i++)
-    if ((!entries[i].path && entries[i].path_len) || (!entries[i].contents && entries[i].len)) return ZH_ERR_ARGUMENT;
+  if (const int st = writer_checks(ctx, entries, first, n_zip, level < -2 || level > 9 ? ZH_ERR_INVALID_LEVEL : ZH_OK,
+                                   dsts, dst_lens, statuses);
+      st || !n_zip)
+    return st;
 
   // ---- steps 1-4; the non-empty contents of the archives that pass, 256-aligned in one device buffer ----
   std::vector<size_t> ok;                    // the archives still in the running, in order
   std::vector<const void*> csrc;
-  std::vector<uint64_t> soff, slen;
+  std::vector<size_t> clens;
   std::vector<uint32_t> slot_of(first[n_zip] - first[0], ~0u);  // entry -> its plan buffer
-  uint64_t src_total = 0;
   for (size_t t = 0; t < n_zip; t++) {
     if ((statuses[t] = check_archive(entries + first[t], first[t + 1] - first[t])) != ZH_OK) continue;
     ok.push_back(t);
@@ -252,52 +242,24 @@ extern "C" int zh_zip_write_batch(zh_ctx* ctx, const zh_zip_new_entry* entries, 
       if (!entries[i].len) continue;
       slot_of[i - first[0]] = (uint32_t)csrc.size();
       csrc.push_back(entries[i].contents);
-      soff.push_back(src_total);
-      slen.push_back(entries[i].len);
-      src_total += round_up(entries[i].len, 256);
+      clens.push_back(entries[i].len);
     }
   }
   if (ok.empty()) return ZH_OK;
   ZH_HIP(ctx, hipSetDevice(ctx->device));
   Trace tr;
-  const size_t m = csrc.size();
   DevBuf d_src, d_slots;
+  std::vector<uint64_t> soff, slen;
   int st = ZH_OK;
-  if (m) {
-    if (dev_alloc(ctx, d_src, src_total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    if ((st = zhh_upload_slices(ctx, csrc.data(), soff, slen, src_total, d_src.p))) return st;
-  }
+  if (!csrc.empty() && (st = zhh_upload(ctx, csrc.data(), clens.data(), csrc.size(), d_src, soff, slen))) return st;
   tr.mark(ctx, "zip: upload");
 
   // ---- compress(contents, level, dfDeflate) and crc32(contents) of every non-empty entry: one plan ----
-  std::vector<uint64_t> doff(m), clen(m);
-  std::vector<int32_t> cst(m, ZH_OK);
-  std::vector<uint32_t> crc(m, 0);
-  for (int attempt = 0; m && attempt < 2; attempt++) {
-    std::vector<uint64_t> dcap(m);
-    uint64_t total = 0;
-    for (size_t k = 0; k < m; k++) {
-      doff[k] = total;
-      dcap[k] = attempt == 0 ? typical_cap(slen[k], ZH_DF_DEFLATE) : zh_compress_bound(slen[k], ZH_DF_DEFLATE);
-      total += round_up(dcap[k], 256);
-    }
-    if (d_slots.p) {  // (the first attempt's slots: synchronised by zh_plan_results)
-      ctx_free(ctx, d_slots.p);
-      d_slots.p = nullptr;
-    }
-    if (dev_alloc(ctx, d_slots, total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    PlanGuard pg;
-    if ((st = zh_plan_compress(ctx, m, soff.data(), slen.data(), doff.data(), dcap.data(), level, ZH_DF_DEFLATE,
-                               &pg.p)))
-      return st;
-    zh_plan_request_crc32(pg.p, 1);
-    if ((st = zh_plan_run(pg.p, d_src.p, d_slots.p))) return st;
-    if ((st = zh_plan_results(pg.p, clen.data(), cst.data()))) return st;
-    if ((st = zh_plan_crc32(pg.p, crc.data()))) return st;
-    bool retry = false;
-    for (size_t k = 0; k < m; k++) retry |= cst[k] == ZH_ERR_DST_TOO_SMALL;
-    if (!(retry && attempt == 0)) break;
-  }
+  std::vector<uint64_t> doff, clen;
+  std::vector<int32_t> cst;
+  std::vector<uint32_t> crc(csrc.size(), 0);
+  if ((st = zhh_compress(ctx, d_src.p, soff, slen, level, ZH_DF_DEFLATE, crc.data(), d_slots, doff, clen, cst)))
+    return st;
   tr.mark(ctx, "zip: compress");
   if (d_src.p) {  // (back to the context's cache before the image is allocated)
     ctx_free(ctx, d_src.p);
@@ -377,19 +339,13 @@ extern "C" int zh_zip_write_batch(zh_ctx* ctx, const zh_zip_new_entry* entries, 
   if (!n_done) return ZH_OK;
 
   // ---- descriptors, tasks, end records and names in one upload ----
-  const size_t b_desc = round_up(descs.size() * sizeof(ZhZipEntryDesc), 16),
-               b_task = round_up(tasks.size() * sizeof(ZhZipTask), 16),
-               b_eocd = round_up(eocds.size() * sizeof(ZhZipEocdDesc), 16);
-  std::vector<uint8_t> meta(b_desc + b_task + b_eocd + pool.size());
-  memcpy(meta.data(), descs.data(), descs.size() * sizeof(ZhZipEntryDesc));
-  memcpy(meta.data() + b_desc, tasks.data(), tasks.size() * sizeof(ZhZipTask));
-  memcpy(meta.data() + b_desc + b_task, eocds.data(), eocds.size() * sizeof(ZhZipEocdDesc));
-  if (!pool.empty()) memcpy(meta.data() + b_desc + b_task + b_eocd, pool.data(), pool.size());
-  const void* meta_src = meta.data();
-  const size_t meta_len = meta.size();
   DevBuf d_meta, d_img;
-  std::vector<uint64_t> moff, mlen;
-  if ((st = zhh_upload(ctx, &meta_src, &meta_len, 1, d_meta, moff, mlen))) return st;
+  std::vector<uint64_t> moff;
+  if ((st = zhh_upload_spans(ctx, {{descs.data(), descs.size() * sizeof(ZhZipEntryDesc)},
+                                   {tasks.data(), tasks.size() * sizeof(ZhZipTask)},
+                                   {eocds.data(), eocds.size() * sizeof(ZhZipEocdDesc)}, {pool.data(), pool.size()}},
+                             d_meta, moff)))
+    return st;
   if (dev_alloc(ctx, d_img, o + 256) != hipSuccess) return ZH_ERR_NOMEM;
   tr.mark(ctx, "zip: layout");
 
@@ -399,26 +355,16 @@ extern "C" int zh_zip_write_batch(zh_ctx* ctx, const zh_zip_new_entry* entries, 
   for (uint64_t t0 = 0; t0 < tasks.size(); t0 += kGridTasks) {
     const uint64_t nt = std::min<uint64_t>(kGridTasks, tasks.size() - t0);
     hipLaunchKernelGGL(zh_zip_write_kernel, dim3((uint32_t)((nt + 3) / 4)), dim3(256), 0, ctx->stream, img,
-                       static_cast<const uint8_t*>(d_slots.p), reinterpret_cast<const ZhZipEntryDesc*>(mp),
-                       reinterpret_cast<const ZhZipTask*>(mp + b_desc) + t0, nt,
-                       reinterpret_cast<const ZhZipEocdDesc*>(mp + b_desc + b_task), mp + b_desc + b_task + b_eocd);
+                       static_cast<const uint8_t*>(d_slots.p), reinterpret_cast<const ZhZipEntryDesc*>(mp + moff[0]),
+                       reinterpret_cast<const ZhZipTask*>(mp + moff[1]) + t0, nt,
+                       reinterpret_cast<const ZhZipEocdDesc*>(mp + moff[2]), mp + moff[3]);
     ZH_HIP(ctx, hipGetLastError());
   }
   tr.mark(ctx, "zip: write");
 
-  std::vector<void*> odst(n_done, nullptr);
-  std::vector<size_t> olen_out(n_done, 0);
-  std::vector<int32_t> ost_out(n_done, ZH_OK);
-  if ((st = zhh_download(ctx, d_img.p, n_done, img_off, img_len, std::vector<char>(n_done, 1), odst.data(),
-                         olen_out.data(), ost_out.data()))) {
-    for (void* p : odst) free(p);
+  if ((st = writer_hand_out(ctx, d_img.p, done, img_off, img_len, std::vector<int32_t>(n_done, ZH_OK), dsts,
+                            dst_lens, statuses)))
     return st;
-  }
   tr.mark(ctx, "zip: download");
-  for (size_t k = 0; k < n_done; k++) {
-    dsts[done[k]] = odst[k];
-    dst_lens[done[k]] = olen_out[k];
-    statuses[done[k]] = ost_out[k];
-  }
   return ZH_OK;
 }

@@ -590,7 +590,7 @@ def check_ragged_staging(eng, scale):
         assert all(s == 0 for s in sts), sts
         assert back == bufs, level
         if fmt == oracle.dfGzip:
-            # the same batch as pipelined groups (uncompress_batch_pipelined: gzip members carry their
+            # the same batch as pipelined groups (batch_pipelined: gzip members carry their
             # size): identical results; then one member whose ISIZE promises too little -- the group it
             # is in outgrows its slot and the whole batch is sent down the plain path, which sizes and
             # retries: same bytes, that member's status from the ISIZE check like the plain path's

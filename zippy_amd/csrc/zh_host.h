@@ -1,9 +1,10 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in five files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in nine files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
-// zh_plan_run.hip (kernel sequencing, switches, results), zh_host_batch.hip (host-buffer batches: staging,
-// pipelined groups, sharding over contexts) and zh_host_calls.hip (single-buffer calls, the block-parallel
-// form, checksums, debug hooks).  No compute happens in any of them.
+// zh_plan_run.hip (kernel sequencing, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
+// wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
+// zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks) and the batch writers
+// zh_zip_write.hip / zh_tar_create.hip (whose kernels sit next to their host code).  No compute happens on the host.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -109,11 +110,6 @@ struct zh_ctx {
   // finder, joined in front of the layout; the events are the context's (runs of one context follow each other)
   hipStream_t aux_stream = nullptr;
   hipEvent_t aux_fork = nullptr, aux_join = nullptr;
-  // zh_*_batch_into: the caller's output buffers and their sizes for the call in progress
-  // (into_base: the dsts array the batch functions were handed, to find a buffer's index again)
-  void* const* into_ptrs = nullptr;
-  const size_t* into_caps = nullptr;
-  void** into_base = nullptr;
   uint64_t pipe_min = 0, pipe_group = 0;  // zh_set_host_pipeline (0: ZH_PIPE_MIN / ZH_PIPE_GROUP / default)
   // device memory the context has freed, kept for its next call (ctx_malloc / ctx_free)
   struct DevBlock {
@@ -311,6 +307,15 @@ struct Trace {
 };
 
 
+// a batch call's three output arrays as they are before anything is handed out
+static inline void clear_outputs(void** dsts, size_t* dst_lens, int32_t* statuses, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    dsts[i] = nullptr;
+    dst_lens[i] = 0;
+    statuses[i] = ZH_OK;
+  }
+}
+
 // (zh_host_batch.hip) pack host buffers into one device allocation / results into fresh host buffers
 ZH_INTERNAL int zhh_upload(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n, DevBuf& dev,
                            std::vector<uint64_t>& off, std::vector<uint64_t>& len64);
@@ -340,11 +345,7 @@ template <class Entry>
 static int writer_checks(zh_ctx* ctx, const Entry* entries, const size_t* first, size_t n, int bad_call, void** dsts,
                          size_t* dst_lens, int32_t* statuses) {
   if (!ctx || (n && (!first || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n; t++) {
-    dsts[t] = nullptr;
-    dst_lens[t] = 0;
-    statuses[t] = ZH_OK;
-  }
+  clear_outputs(dsts, dst_lens, statuses, n);
   if (bad_call || !n) return bad_call;
   for (size_t t = 0; t < n; t++)
     if (first[t + 1] < first[t]) return ZH_ERR_ARGUMENT;

@@ -162,18 +162,21 @@ void stage_chunk(uint8_t* stage, uint64_t lo, uint64_t hi, const std::vector<uin
   });
 }
 
-// 256-byte aligned slices of one linear range; returns its size
-uint64_t layout_slices(const size_t* lens, size_t n, std::vector<uint64_t>& off,
-                       std::vector<uint64_t>& len64) {
+// 256-byte aligned slots of size[0, n) bytes in one linear range: off; returns the range's size
+uint64_t layout_slots(const uint64_t* size, size_t n, std::vector<uint64_t>& off) {
   off.resize(n);
-  len64.resize(n);
   uint64_t total = 0;
   for (size_t i = 0; i < n; i++) {
     off[i] = total;
-    len64[i] = lens[i];
-    total += (lens[i] + 255) & ~(uint64_t)255;
+    total += (size[i] + 255) & ~(uint64_t)255;
   }
   return total;
+}
+// the source slices of a batch
+uint64_t layout_slices(const size_t* lens, size_t n, std::vector<uint64_t>& off,
+                       std::vector<uint64_t>& len64) {
+  len64.assign(lens, lens + n);
+  return layout_slots(len64.data(), n, off);
 }
 // host buffers -> dev[0, total) in that layout, chunk by chunk on `stream`
 int upload_slices(zh_ctx* ctx, hipStream_t stream, const void* const* srcs,
@@ -192,23 +195,19 @@ int upload_slices(zh_ctx* ctx, hipStream_t stream, const void* const* srcs,
   }
   return ZH_OK;
 }
-// Output slots of a compress plan over buffers of len[0, n) bytes, 256-aligned in one range: doff / dcap, returns its
-// size.  A retry's slot is zh_compress_bound; a first attempt's is typical_cap, or ZH_COMPRESS_FIRST_CAP bytes when
-// that is smaller (a test aid, read at each call, so that the tests reach the retry and the pipelined fallback).
+// Output slots of a compress plan over buffers of len[0, n) bytes: doff / dcap, returns their range's size.  A retry's
+// slot is zh_compress_bound; a first attempt's is typical_cap, or ZH_COMPRESS_FIRST_CAP bytes when that is smaller
+// (a test aid, read at each call, so that the tests reach the retry and the pipelined fallback).
 uint64_t layout_dst(const uint64_t* len, size_t n, int fmt, bool retry, std::vector<uint64_t>& doff,
                     std::vector<uint64_t>& dcap) {
   const char* e = getenv("ZH_COMPRESS_FIRST_CAP");
   const long long first_cap = e ? atoll(e) : 0;
-  doff.resize(n);
   dcap.resize(n);
-  uint64_t total = 0;
   for (size_t i = 0; i < n; i++) {
-    doff[i] = total;
     dcap[i] = retry ? zh_compress_bound(len[i], fmt) : typical_cap(len[i], fmt);
     if (!retry && first_cap > 0) dcap[i] = std::min<uint64_t>(dcap[i], (uint64_t)first_cap);
-    total += (dcap[i] + 255) & ~(uint64_t)255;
   }
-  return total;
+  return layout_slots(dcap.data(), n, doff);
 }
 // Pack host buffers into one device allocation.
 int upload(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n, DevBuf& dev,
@@ -240,8 +239,15 @@ __global__ __launch_bounds__(256) void zh_pack_kernel(const uint8_t* __restrict_
 }
 
 namespace {
-// Results of the buffers with status ZH_OK: `malloc`ed and filled from their device slots
-// d_dst + doff[i] (olen[i] bytes each), in two steps.
+// Where a call's results go: fresh `malloc`s (the default; they are the caller's to zh_free), or buffers the caller
+// owns -- ptrs[g] with room for caps[g] bytes, g the buffer's position in the whole batch (zh_*_batch_into).
+struct OutBufs {
+  void* const* ptrs = nullptr;
+  const size_t* caps = nullptr;
+  bool fresh() const { return !ptrs; }
+};
+// Results of the buffers with status ZH_OK: filled from their device slots d_dst + doff[i] (olen[i] bytes each), in
+// two steps.
 struct Download {
   std::vector<uint64_t> poff, plen;  // the dense layout the results are packed into
   uint64_t total = 0;
@@ -249,11 +255,12 @@ struct Download {
   uint8_t* pack = nullptr;
 };
 // step 1, on `stream`: allocate the results and pack them densely on the device (into `pack`,
-// at least as large as the output slots together, or into a buffer of the Download's own)
+// at least as large as the output slots together, or into a buffer of the Download's own).
+// The n buffers are positions [i0, i0 + n) of the batch `out` speaks of; dsts / dst_lens / statuses start at i0.
 int download_pack(zh_ctx* ctx, hipStream_t stream, Download& dl, const uint8_t* d_dst, size_t n,
                   const std::vector<uint64_t>& doff, const std::vector<uint64_t>& olen,
-                  const std::vector<char>& take, uint8_t* pack, void** dsts, size_t* dst_lens,
-                  int32_t* statuses) {
+                  const std::vector<char>& take, uint8_t* pack, const OutBufs& out, size_t i0, void** dsts,
+                  size_t* dst_lens, int32_t* statuses) {
   constexpr uint32_t kPiece = 1u << 18;
   dl.poff.assign(n, 0);
   dl.plen.assign(n, 0);
@@ -269,14 +276,13 @@ int download_pack(zh_ctx* ctx, hipStream_t stream, Download& dl, const uint8_t* 
   dl.total = total;
   for (size_t i = 0; i < n; i++) {
     if (!take[i]) continue;
-    if (ctx->into_ptrs) {  // the caller's buffer, if the result fits (its size is reported either way)
-      const size_t gi = (size_t)((dsts + i) - ctx->into_base);
+    if (!out.fresh()) {  // the caller's buffer, if the result fits (its size is reported either way)
       dst_lens[i] = olen[i];
-      if (olen[i] > ctx->into_caps[gi] || (!ctx->into_ptrs[gi] && olen[i])) {
+      if (olen[i] > out.caps[i0 + i] || (!out.ptrs[i0 + i] && olen[i])) {
         statuses[i] = ZH_ERR_DST_TOO_SMALL;
         continue;
       }
-      dsts[i] = ctx->into_ptrs[gi];
+      dsts[i] = out.ptrs[i0 + i];
       continue;
     }
     dsts[i] = malloc(olen[i] ? olen[i] : 1);
@@ -325,18 +331,19 @@ int download_fetch(zh_ctx* ctx, hipStream_t stream, const Download& dl, void** d
   }
   return ZH_OK;
 }
+// both steps for a whole batch on the context's stream
 int download(zh_ctx* ctx, const uint8_t* d_dst, size_t n, const std::vector<uint64_t>& doff,
-             const std::vector<uint64_t>& olen, const std::vector<char>& take, void** dsts,
+             const std::vector<uint64_t>& olen, const std::vector<char>& take, const OutBufs& out, void** dsts,
              size_t* dst_lens, int32_t* statuses) {
   Download dl;
-  int st = download_pack(ctx, ctx->stream, dl, d_dst, n, doff, olen, take, nullptr, dsts, dst_lens, statuses);
+  int st = download_pack(ctx, ctx->stream, dl, d_dst, n, doff, olen, take, nullptr, out, 0, dsts, dst_lens, statuses);
   if (st) return st;
   return download_fetch(ctx, ctx->stream, dl, dsts);
 }
 
-// Batches of a GiB and more: groups of buffers (ZH_PIPE_GROUP bytes of input each) take turns, so
-// that the kernels of one group run while the host threads and the DMA engine move the
-// previous group's results out and the next group's buffers in.  A group must fill the machine
+// Batches of a GiB and more: groups of buffers (ZH_PIPE_GROUP bytes each -- of input for compress, of promised
+// output for uncompress) take turns, so that the kernels of one group run while the host threads and the DMA engine
+// move the previous group's results out and the next group's buffers in.  A group must fill the machine
 // by itself, or splitting costs more than the overlap hides (ZH_PIPE_MIN: smallest batch that is
 // split).
 uint64_t env_bytes(const char* name, uint64_t dflt) {
@@ -367,20 +374,28 @@ struct PipeGroup {
   }
 };
 
-// ZH_OK: done.  kPipeFallback: the batch does not split, memory for the groups' second set of
-// buffers is not to be had, or some buffer outgrew its typical slot; nothing was returned, the
-// caller runs the batch the plain way.
-int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
-                             int level, int data_format, void** dsts, size_t* dst_lens,
-                             int32_t* statuses, uint32_t* crcs) {
+// What differs between the batches that run as pipelined groups.
+struct PipeJob {
+  const uint64_t* weight;                                // per buffer: the bytes the groups are cut by
+  std::function<void(PipeGroup&)> slots;                 // a group's output slots: doff / dcap / dst_total
+  std::function<int(PipeGroup&)> plan;                   // a group's plan: pg.p
+  std::function<void(std::vector<PipeGroup>&)> planned;  // (optional) once every group has its plan
+  const char* label;                                     // the trace line
+};
+
+// ZH_OK: done.  kPipeFallback: the batch does not split, memory for the groups' second set of buffers is not to be
+// had, or some buffer outgrew its slot (compress: the typical one; uncompress: its promise -- a member of 4 GiB and
+// more, or a damaged one); nothing was returned, the caller runs the batch the plain way, which knows how to retry.
+int batch_pipelined(zh_ctx* ctx, const PipeJob& job, const void* const* srcs, const size_t* lens, size_t n,
+                    const OutBufs& out, void** dsts, size_t* dst_lens, int32_t* statuses, uint32_t* crcs) {
   // at most 16 groups (each has its own plan scratch): very large batches get larger groups
-  uint64_t in_total = 0;
-  for (size_t i = 0; i < n; i++) in_total += lens[i];
-  const uint64_t group_bytes = std::max<uint64_t>(pipe_group_bytes(ctx), in_total / 16);
+  uint64_t w_total = 0;
+  for (size_t i = 0; i < n; i++) w_total += job.weight[i];
+  const uint64_t group_bytes = std::max<uint64_t>(pipe_group_bytes(ctx), w_total / 16);
   std::vector<size_t> cut{0};
   uint64_t acc = 0;
   for (size_t i = 0; i < n; i++) {
-    acc += lens[i];
+    acc += job.weight[i];
     if (acc >= group_bytes) {
       cut.push_back(i + 1);
       acc = 0;
@@ -394,18 +409,18 @@ int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t*
   Trace tr;
   std::vector<PipeGroup> gs(G);
   int st;
-  // The groups take turns in TWO sets of source / output / pack buffers (group g uses set g % 2: by
-  // the time group g + 2 touches a buffer of the set, group g's last use of it lies before it on the
-  // same stream or has been waited for on the host -- see the loop below); only the plans' own
-  // scratch (match lists, histograms) is per group.  Everything is allocated before the pipeline
-  // starts: hipMalloc / hipFree in the middle would serialise it.
+  // Device memory is bounded by two groups, not by the batch: the groups take turns in TWO sets of source / output /
+  // pack buffers (group g uses set g % 2: by the time group g + 2 touches a buffer of the set, group g's last use of
+  // it lies before it on the same stream or has been waited for on the host -- see the loop below); only the plans'
+  // own scratch (match lists, histograms) is per group.  Everything is allocated before the pipeline starts:
+  // hipMalloc / hipFree in the middle would serialise it.
   uint64_t set_src[2] = {0, 0}, set_dst[2] = {0, 0};
   for (size_t g = 0; g < G; g++) {
     PipeGroup& q = gs[g];
     q.i0 = cut[g];
     q.n = cut[g + 1] - cut[g];
     q.src_total = layout_slices(lens + q.i0, q.n, q.soff, q.slen);
-    q.dst_total = layout_dst(q.slen.data(), q.n, data_format, false, q.doff, q.dcap);
+    job.slots(q);
     set_src[g & 1] = std::max(set_src[g & 1], q.src_total);
     set_dst[g & 1] = std::max(set_dst[g & 1], q.dst_total);
   }
@@ -421,12 +436,12 @@ int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t*
     PipeGroup& q = gs[g];
     ZH_HIP(ctx, hipEventCreate(&q.uploaded));
     ZH_HIP(ctx, hipEventCreate(&q.packed));
-    st = zh_plan_compress(ctx, q.n, q.soff.data(), q.slen.data(), q.doff.data(), q.dcap.data(), level,
-                          data_format, &q.pg.p);
+    st = job.plan(q);
     if (st == ZH_ERR_NOMEM) return kPipeFallback;
     if (st) return st;
     if (crcs) zh_plan_request_crc32(q.pg.p, 1);
   }
+  if (job.planned) job.planned(gs);
   ZH_HIP(ctx, hipStreamSynchronize(ks));  // the plans' descriptors are in place
   auto up = [&](size_t g) -> int {
     PipeGroup& q = gs[g];
@@ -444,12 +459,9 @@ int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t*
     (void)hipStreamSynchronize(cs);
     (void)hipStreamSynchronize(ks);
     for (int k = 0; k < 2; k++) ctx->pin_busy[k] = false;
-    for (size_t i = 0; i < n; i++) {
-      if (!ctx->into_ptrs) free(dsts[i]);  // (zh_*_batch_into: the buffers are the caller's)
-      dsts[i] = nullptr;
-      dst_lens[i] = 0;
-      statuses[i] = ZH_OK;
-    }
+    if (out.fresh())  // (else the buffers are the caller's)
+      for (size_t i = 0; i < n; i++) free(dsts[i]);
+    clear_outputs(dsts, dst_lens, statuses, n);
     return code;
   };
   if ((st = up(0)) || (st = run(0))) return give_up(st);
@@ -466,8 +478,8 @@ int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t*
       statuses[q.i0 + i] = ost[i];
       take[i] = ost[i] == ZH_OK;
     }
-    st = download_pack(ctx, ks, q.dl, b_dst[g & 1].p, q.n, q.doff, olen, take, b_pack[g & 1].p, dsts + q.i0,
-                       dst_lens + q.i0, statuses + q.i0);
+    st = download_pack(ctx, ks, q.dl, b_dst[g & 1].p, q.n, q.doff, olen, take, b_pack[g & 1].p, out, q.i0,
+                       dsts + q.i0, dst_lens + q.i0, statuses + q.i0);
     if (st) return give_up(st);
     if (hipEventRecord(q.packed, ks) != hipSuccess) return give_up(ZH_ERR_DEVICE);
     if (g + 1 < G && (st = run(g + 1))) return give_up(st);  // next kernels behind the pack
@@ -475,20 +487,16 @@ int compress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t*
     if ((st = download_fetch(ctx, cs, q.dl, dsts + q.i0))) return give_up(st);
   }
   ZH_HIP(ctx, hipStreamSynchronize(cs));
-  tr.mark(ctx, "compress: pipelined groups");
+  tr.mark(ctx, job.label);
   return ZH_OK;
 }
 }  // namespace
 
 static int compress_batch_impl(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
-                               int level, int data_format, void** dsts, size_t* dst_lens,
+                               int level, int data_format, const OutBufs& out, void** dsts, size_t* dst_lens,
                                int32_t* statuses, uint32_t* crcs) {
   if (!ctx || (n && (!srcs || !lens || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t i = 0; i < n; i++) {
-    dsts[i] = nullptr;
-    dst_lens[i] = 0;
-    statuses[i] = ZH_OK;
-  }
+  clear_outputs(dsts, dst_lens, statuses, n);
   if (level < -2 || level > 9) {
     for (size_t i = 0; i < n; i++) statuses[i] = ZH_ERR_INVALID_LEVEL;
     return ZH_ERR_INVALID_LEVEL;
@@ -502,8 +510,18 @@ static int compress_batch_impl(zh_ctx* ctx, const void* const* srcs, const size_
   uint64_t in_total = 0;
   for (size_t i = 0; i < n; i++) in_total += lens[i];
   if (in_total >= pipe_min_bytes(ctx)) {
-    const int ps = compress_batch_pipelined(ctx, srcs, lens, n, level, data_format, dsts, dst_lens,
-                                            statuses, crcs);
+    const std::vector<uint64_t> len64(lens, lens + n);
+    PipeJob job;
+    job.weight = len64.data();
+    job.slots = [&](PipeGroup& q) {
+      q.dst_total = layout_dst(q.slen.data(), q.n, data_format, false, q.doff, q.dcap);
+    };
+    job.plan = [&](PipeGroup& q) {
+      return zh_plan_compress(ctx, q.n, q.soff.data(), q.slen.data(), q.doff.data(), q.dcap.data(), level,
+                              data_format, &q.pg.p);
+    };
+    job.label = "compress: pipelined groups";
+    const int ps = batch_pipelined(ctx, job, srcs, lens, n, out, dsts, dst_lens, statuses, crcs);
     if (ps != kPipeFallback) return ps;
   }
   DevBuf d_src;
@@ -523,7 +541,7 @@ static int compress_batch_impl(zh_ctx* ctx, const void* const* srcs, const size_
     statuses[i] = ost[i];
     take[i] = ost[i] == ZH_OK;
   }
-  if ((st = download(ctx, d_dst.p, n, doff, olen, take, dsts, dst_lens, statuses))) return st;
+  if ((st = download(ctx, d_dst.p, n, doff, olen, take, out, dsts, dst_lens, statuses))) return st;
   tr.mark(ctx, "compress: download");
   return ZH_OK;
 }
@@ -531,33 +549,24 @@ static int compress_batch_impl(zh_ctx* ctx, const void* const* srcs, const size_
 extern "C" int zh_compress_batch(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
                                  int level, int data_format, void** dsts, size_t* dst_lens,
                                  int32_t* statuses) {
-  return compress_batch_impl(ctx, srcs, lens, n, level, data_format, dsts, dst_lens, statuses, nullptr);
+  return compress_batch_impl(ctx, srcs, lens, n, level, data_format, OutBufs{}, dsts, dst_lens, statuses, nullptr);
 }
 // Results into buffers of the caller's: dsts[i] / caps[i] on entry.  A result that does not fit
 // gets ZH_ERR_DST_TOO_SMALL and its size in dst_lens[i]; on return dsts[i] is the caller's pointer
 // for every buffer that was filled and NULL otherwise.  Nothing here is to be given to zh_free.
-struct IntoScope {
-  zh_ctx* ctx;
-  std::vector<void*> ptrs;
-  IntoScope(zh_ctx* c, void** dsts, const size_t* caps, size_t n) : ctx(c), ptrs(dsts, dsts + n) {
-    ctx->into_ptrs = ptrs.data();
-    ctx->into_caps = caps;
-    ctx->into_base = dsts;
-  }
-  ~IntoScope() { ctx->into_ptrs = nullptr, ctx->into_caps = nullptr, ctx->into_base = nullptr; }
-};
 extern "C" int zh_compress_batch_into(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
                                       int level, int data_format, void** dsts, const size_t* caps,
                                       size_t* dst_lens, int32_t* statuses) {
   if (!ctx || (n && (!dsts || !caps))) return ZH_ERR_ARGUMENT;
-  IntoScope scope(ctx, dsts, caps, n);
-  return compress_batch_impl(ctx, srcs, lens, n, level, data_format, dsts, dst_lens, statuses, nullptr);
+  const std::vector<void*> ptrs(dsts, dsts + n);  // (dsts itself is cleared, then refilled)
+  return compress_batch_impl(ctx, srcs, lens, n, level, data_format, OutBufs{ptrs.data(), caps}, dsts, dst_lens,
+                             statuses, nullptr);
 }
 extern "C" int zh_compress_batch_crc32(zh_ctx* ctx, const void* const* srcs, const size_t* lens,
                                        size_t n, int level, int data_format, void** dsts,
                                        size_t* dst_lens, int32_t* statuses, uint32_t* crcs) {
   if (!crcs && n) return ZH_ERR_ARGUMENT;
-  return compress_batch_impl(ctx, srcs, lens, n, level, data_format, dsts, dst_lens, statuses, crcs);
+  return compress_batch_impl(ctx, srcs, lens, n, level, data_format, OutBufs{}, dsts, dst_lens, statuses, crcs);
 }
 
 // Which container will the device see?  (zippy.nim:108-125, sizing only)
@@ -572,150 +581,15 @@ static int host_detect(const uint8_t* s, size_t len, int fmt) {
 // size_hints: expected output sizes (ZIP central directory, gzip.nim:72-76 trustSize): they
 // replace the sizing pass of streams that carry no size; a stream that outgrows its hint falls
 // back to the deflate expansion bound.  crcs: CRC-32 of every output (whatever the container).
-// The uncompress counterpart of compress_batch_pipelined, for batches whose output sizes are all
-// known up front (gzip members: ISIZE; ZIP entries: the central directory): groups of about
-// ZH_PIPE_GROUP bytes of OUTPUT take turns, so that one group's kernels run while the group
-// before it goes home and the next one comes in.  kPipeFallback: run the batch the plain way
-// (does not split, no memory for the second set of buffers, or a stream outgrew its promise --
-// a member of 4 GiB and more, or a damaged one -- which the plain path knows how to retry).
-static int uncompress_batch_pipelined(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
-                                      int data_format, const std::vector<uint64_t>& cap, void** dsts,
-                                      size_t* dst_lens, int32_t* statuses, uint32_t* crcs) {
-  uint64_t out_total = 0;
-  for (size_t i = 0; i < n; i++) out_total += cap[i];
-  const uint64_t group_bytes = std::max<uint64_t>(pipe_group_bytes(ctx), out_total / 16);
-  std::vector<size_t> cut{0};
-  uint64_t acc = 0;
-  for (size_t i = 0; i < n; i++) {
-    acc += cap[i];
-    if (acc >= group_bytes) {
-      cut.push_back(i + 1);
-      acc = 0;
-    }
-  }
-  if (cut.back() != n) cut.push_back(n);
-  const size_t G = cut.size() - 1;
-  if (G < 2) return kPipeFallback;
-  if (!ctx->copy_stream) ZH_HIP(ctx, hipStreamCreate(&ctx->copy_stream));
-  hipStream_t cs = ctx->copy_stream, ks = ctx->stream;
-  Trace tr;
-  std::vector<PipeGroup> gs(G);
-  int st;
-  // Device memory is bounded by two groups, not by the batch: the groups take turns in TWO sets of
-  // source / output / pack buffers (group g uses set g % 2: by the time group g + 2 touches a buffer
-  // of the set, group g's last use of it lies before it on the same stream or has been waited for on
-  // the host -- see the loop below), and ONE token pool serves every group (scratch of a run, and the
-  // runs follow each other on `ks`).  Everything is allocated before the pipeline starts:
-  // hipMalloc / hipFree in the middle would serialise it.
-  uint64_t set_src[2] = {0, 0}, set_dst[2] = {0, 0};
-  for (size_t g = 0; g < G; g++) {
-    PipeGroup& q = gs[g];
-    q.i0 = cut[g];
-    q.n = cut[g + 1] - cut[g];
-    q.src_total = layout_slices(lens + q.i0, q.n, q.soff, q.slen);
-    q.doff.resize(q.n);
-    q.dcap.resize(q.n);
-    for (size_t i = 0; i < q.n; i++) {
-      q.doff[i] = q.dst_total;
-      q.dcap[i] = cap[q.i0 + i];
-      q.dst_total += (q.dcap[i] + 255) & ~(uint64_t)255;
-    }
-    set_src[g & 1] = std::max(set_src[g & 1], q.src_total);
-    set_dst[g & 1] = std::max(set_dst[g & 1], q.dst_total);
-  }
-  DevBuf b_src[2], b_dst[2], b_pack[2];
-  for (int k = 0; k < 2; k++)
-    if (dev_alloc(ctx, b_src[k], set_src[k] + 256) != hipSuccess ||
-        dev_alloc(ctx, b_dst[k], set_dst[k] + 256) != hipSuccess ||
-        dev_alloc(ctx, b_pack[k], set_dst[k] + 256) != hipSuccess) {
-      (void)hipGetLastError();
-      return kPipeFallback;
-    }
-  uint64_t tok_words = 0;
-  for (size_t g = 0; g < G; g++) {
-    PipeGroup& q = gs[g];
-    ZH_HIP(ctx, hipEventCreate(&q.uploaded));
-    ZH_HIP(ctx, hipEventCreate(&q.packed));
-    st = zh_plan_uncompress(ctx, q.n, q.soff.data(), q.slen.data(), q.doff.data(), q.dcap.data(), data_format,
-                            &q.pg.p);
-    if (st == ZH_ERR_NOMEM) return kPipeFallback;
-    if (st) return st;
-    tok_words = std::max(tok_words, q.pg.p->tok_words);
-    if (crcs) zh_plan_request_crc32(q.pg.p, 1);
-  }
-  DevBuf b_tok;
-  if (inflate_split_enabled(ctx) && tok_words) {
-    // (a pool that cannot be had leaves the plans to their own devices: plan_token_pool notes the fallback)
-    if (dev_alloc(ctx, b_tok, tok_words * 4) != hipSuccess) (void)hipGetLastError();
-    for (size_t g = 0; g < G; g++) {
-      if (b_tok.p) plan_lend_token_pool(gs[g].pg.p, (uint32_t*)b_tok.p, tok_words);
-      (void)plan_token_pool(gs[g].pg.p);  // (now, not in the middle of the pipeline)
-    }
-  }
-  ZH_HIP(ctx, hipStreamSynchronize(ks));  // the plans' descriptors are in place
-  auto up = [&](size_t g) -> int {
-    PipeGroup& q = gs[g];
-    int e = upload_slices(ctx, cs, srcs + q.i0, q.soff, q.slen, q.src_total, b_src[g & 1].p);
-    if (e) return e;
-    ZH_HIP(ctx, hipEventRecord(q.uploaded, cs));
-    return ZH_OK;
-  };
-  auto run = [&](size_t g) -> int {
-    PipeGroup& q = gs[g];
-    ZH_HIP(ctx, hipStreamWaitEvent(ks, q.uploaded, 0));
-    return zh_plan_run(q.pg.p, b_src[g & 1].p, b_dst[g & 1].p);
-  };
-  auto give_up = [&](int code) -> int {  // nothing is handed out from a failed call
-    (void)hipStreamSynchronize(cs);
-    (void)hipStreamSynchronize(ks);
-    for (int k = 0; k < 2; k++) ctx->pin_busy[k] = false;
-    for (size_t i = 0; i < n; i++) {
-      if (!ctx->into_ptrs) free(dsts[i]);  // (zh_*_batch_into: the buffers are the caller's)
-      dsts[i] = nullptr;
-      dst_lens[i] = 0;
-      statuses[i] = ZH_OK;
-    }
-    return code;
-  };
-  if ((st = up(0)) || (st = run(0))) return give_up(st);
-  for (size_t g = 0; g < G; g++) {
-    PipeGroup& q = gs[g];
-    if (g + 1 < G && (st = up(g + 1))) return give_up(st);  // while group g's kernels run
-    std::vector<uint64_t> olen(q.n);
-    std::vector<int32_t> ost(q.n);
-    if ((st = zh_plan_results(q.pg.p, olen.data(), ost.data()))) return give_up(st);
-    if (crcs && (st = zh_plan_crc32(q.pg.p, crcs + q.i0))) return give_up(st);
-    std::vector<char> take(q.n);
-    for (size_t i = 0; i < q.n; i++) {
-      if (ost[i] == ZH_ERR_DST_TOO_SMALL) return give_up(kPipeFallback);
-      statuses[q.i0 + i] = ost[i];
-      take[i] = ost[i] == ZH_OK;
-    }
-    st = download_pack(ctx, ks, q.dl, b_dst[g & 1].p, q.n, q.doff, olen, take, b_pack[g & 1].p, dsts + q.i0,
-                       dst_lens + q.i0, statuses + q.i0);
-    if (st) return give_up(st);
-    if (hipEventRecord(q.packed, ks) != hipSuccess) return give_up(ZH_ERR_DEVICE);
-    if (g + 1 < G && (st = run(g + 1))) return give_up(st);  // next kernels behind the pack
-    if (hipStreamWaitEvent(cs, q.packed, 0) != hipSuccess) return give_up(ZH_ERR_DEVICE);
-    if ((st = download_fetch(ctx, cs, q.dl, dsts + q.i0))) return give_up(st);
-  }
-  ZH_HIP(ctx, hipStreamSynchronize(cs));
-  tr.mark(ctx, "uncompress: pipelined groups");
-  return ZH_OK;
-}
-
-// hints_are_caps: the hints are capacities of buffers of the caller's (zh_uncompress_batch_into), not promised
-// sizes: a stream that outgrows its hint takes the sizing pass (its size is all that is reported then) instead of
-// a second decode at the 1032 x expansion bound.
+// Results into buffers of the caller's (zh_uncompress_batch_into): the hints are their capacities, not promised
+// sizes (hints_are_caps): a stream that outgrows its hint takes the sizing pass (its size is all that is reported
+// then) instead of a second decode at the 1032 x expansion bound.
 static int uncompress_batch_impl(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
-                                 int data_format, const uint64_t* size_hints, void** dsts,
-                                 size_t* dst_lens, int32_t* statuses, uint32_t* crcs, bool hints_are_caps = false) {
+                                 int data_format, const uint64_t* size_hints, const OutBufs& out, void** dsts,
+                                 size_t* dst_lens, int32_t* statuses, uint32_t* crcs) {
   if (!ctx || (n && (!srcs || !lens || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t i = 0; i < n; i++) {
-    dsts[i] = nullptr;
-    dst_lens[i] = 0;
-    statuses[i] = ZH_OK;
-  }
+  clear_outputs(dsts, dst_lens, statuses, n);
+  const bool hints_are_caps = !out.fresh();
   if (data_format < ZH_DF_DETECT || data_format > ZH_DF_DEFLATE) {
     for (size_t i = 0; i < n; i++) statuses[i] = ZH_ERR_INVALID_FORMAT;
     return ZH_ERR_INVALID_FORMAT;
@@ -759,7 +633,31 @@ static int uncompress_batch_impl(zh_ctx* ctx, const void* const* srcs, const siz
       out_total += cap[i];
     }
     if (known && out_total >= pipe_min_bytes(ctx)) {
-      const int ps = uncompress_batch_pipelined(ctx, srcs, lens, n, data_format, cap, dsts, dst_lens, statuses, crcs);
+      PipeJob job;
+      job.weight = cap.data();
+      job.slots = [&](PipeGroup& q) {
+        q.dcap.assign(cap.begin() + q.i0, cap.begin() + q.i0 + q.n);
+        q.dst_total = layout_slots(q.dcap.data(), q.n, q.doff);
+      };
+      job.plan = [&](PipeGroup& q) {
+        return zh_plan_uncompress(ctx, q.n, q.soff.data(), q.slen.data(), q.doff.data(), q.dcap.data(), data_format,
+                                  &q.pg.p);
+      };
+      // ONE token pool serves every group (scratch of a run, and the runs follow each other on the context's stream)
+      DevBuf b_tok;
+      job.planned = [&](std::vector<PipeGroup>& gs) {
+        uint64_t tok_words = 0;
+        for (const PipeGroup& q : gs) tok_words = std::max(tok_words, q.pg.p->tok_words);
+        if (!inflate_split_enabled(ctx) || !tok_words) return;
+        // (a pool that cannot be had leaves the plans to their own devices: plan_token_pool notes the fallback)
+        if (dev_alloc(ctx, b_tok, tok_words * 4) != hipSuccess) (void)hipGetLastError();
+        for (PipeGroup& q : gs) {
+          if (b_tok.p) plan_lend_token_pool(q.pg.p, (uint32_t*)b_tok.p, tok_words);
+          (void)plan_token_pool(q.pg.p);  // (now, not in the middle of the pipeline)
+        }
+      };
+      job.label = "uncompress: pipelined groups";
+      const int ps = batch_pipelined(ctx, job, srcs, lens, n, out, dsts, dst_lens, statuses, crcs);
       if (ps != kPipeFallback) return ps;
     }
   }
@@ -771,15 +669,13 @@ static int uncompress_batch_impl(zh_ctx* ctx, const void* const* srcs, const siz
   // A stream whose outcome is final is handed to later passes with length 0: it costs nothing.
   int pass = 1;
   for (int turn = 0; turn < 3; turn++) {
-    std::vector<uint64_t> doff(n), dcap(n), slen_now(n);
-    uint64_t total = 0;
+    std::vector<uint64_t> doff, dcap(n), slen_now(n);
     for (size_t i = 0; i < n; i++) {
       const bool runs = active[i] && (pass != 0 || guessed[i]);
       slen_now[i] = runs ? slen[i] : 0;
-      doff[i] = total;
       dcap[i] = pass == 0 || !runs ? 0 : cap[i];
-      total += (dcap[i] + 255) & ~(uint64_t)255;
     }
+    const uint64_t total = layout_slots(dcap.data(), n, doff);
     DevBuf d_dst;
     if (dev_alloc(ctx, d_dst, total + 256) != hipSuccess) return ZH_ERR_NOMEM;
     PlanGuard pg;
@@ -826,7 +722,7 @@ static int uncompress_batch_impl(zh_ctx* ctx, const void* const* srcs, const siz
       take[i] = 1;
       if (crcs) crcs[i] = ocrc[i];
     }
-    if ((st = download(ctx, d_dst.p, n, doff, olen, take, dsts, dst_lens, statuses))) return st;
+    if ((st = download(ctx, d_dst.p, n, doff, olen, take, out, dsts, dst_lens, statuses))) return st;
     tr.mark(ctx, "uncompress: download");
     if (!again || pass == 2) break;
     pass = size_first ? 0 : 2;
@@ -837,22 +733,23 @@ static int uncompress_batch_impl(zh_ctx* ctx, const void* const* srcs, const siz
 extern "C" int zh_uncompress_batch(zh_ctx* ctx, const void* const* srcs, const size_t* lens,
                                    size_t n, int data_format, void** dsts, size_t* dst_lens,
                                    int32_t* statuses) {
-  return uncompress_batch_impl(ctx, srcs, lens, n, data_format, nullptr, dsts, dst_lens, statuses, nullptr);
+  return uncompress_batch_impl(ctx, srcs, lens, n, data_format, nullptr, OutBufs{}, dsts, dst_lens, statuses, nullptr);
 }
 extern "C" int zh_uncompress_batch_into(zh_ctx* ctx, const void* const* srcs, const size_t* lens, size_t n,
                                         int data_format, void** dsts, const size_t* caps, size_t* dst_lens,
                                         int32_t* statuses) {
   if (!ctx || (n && (!dsts || !caps))) return ZH_ERR_ARGUMENT;
-  IntoScope scope(ctx, dsts, caps, n);
+  const std::vector<void*> ptrs(dsts, dsts + n);  // (dsts itself is cleared, then refilled)
   // (the capacities double as size hints: a stream without a size field is decoded into as much)
-  std::vector<uint64_t> hints(caps, caps + n);
-  return uncompress_batch_impl(ctx, srcs, lens, n, data_format, hints.data(), dsts, dst_lens, statuses, nullptr, true);
+  const std::vector<uint64_t> hints(caps, caps + n);
+  return uncompress_batch_impl(ctx, srcs, lens, n, data_format, hints.data(), OutBufs{ptrs.data(), caps}, dsts, dst_lens,
+                               statuses, nullptr);
 }
 extern "C" int zh_uncompress_batch_sized(zh_ctx* ctx, const void* const* srcs, const size_t* lens,
                                          size_t n, int data_format, const uint64_t* size_hints,
                                          void** dsts, size_t* dst_lens, int32_t* statuses,
                                          uint32_t* crcs) {
-  return uncompress_batch_impl(ctx, srcs, lens, n, data_format, size_hints, dsts, dst_lens, statuses, crcs);
+  return uncompress_batch_impl(ctx, srcs, lens, n, data_format, size_hints, OutBufs{}, dsts, dst_lens, statuses, crcs);
 }
 
 // ---- one batch over several contexts (= several GPUs): contiguous index ranges, one host
@@ -923,7 +820,7 @@ int zhh_upload_slices(zh_ctx* ctx, const void* const* srcs, const std::vector<ui
 int zhh_download(zh_ctx* ctx, const uint8_t* d_dst, size_t n, const std::vector<uint64_t>& doff,
                  const std::vector<uint64_t>& olen, const std::vector<char>& take, void** dsts, size_t* dst_lens,
                  int32_t* statuses) {
-  return download(ctx, d_dst, n, doff, olen, take, dsts, dst_lens, statuses);
+  return download(ctx, d_dst, n, doff, olen, take, OutBufs{}, dsts, dst_lens, statuses);
 }
 int zhh_upload_spans(zh_ctx* ctx, std::initializer_list<std::pair<const void*, size_t>> spans, DevBuf& dev,
                      std::vector<uint64_t>& off) {

@@ -254,3 +254,37 @@ proc hipWriteZipArchive*[ZipArchive](archive: ZipArchive): string {.raises: [Zip
   let rc = zh_zip_write_batch(engine(), (if es.len > 0: es[0].addr else: nil), first[0].addr, 1,
                               DefaultCompression.cint, p.addr, n.addr, st.addr)
   take(p, n, if rc != 0: rc else: st.cint)
+
+# ---- createZipArchive for many tables per call (src/zippy/ziparchives.nim:455-634) ----
+proc zh_zip_create_batch(ctx: ZhCtx, entries: ptr ZhZipNewEntry, first: ptr csize_t, nZip: csize_t,
+                         level: cint, dsts: ptr pointer, dstLens: ptr csize_t,
+                         statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc createZipArchives*(tables: seq[OrderedTable[string, string]]): seq[string] {.raises: [ZippyError].} =
+  ## createZipArchive(entries) (ziparchives.nim:625-634) of every table in ONE call: all entries' compress(contents,
+  ## BestSpeed, dfDeflate) and crc32 in one plan, every record of every archive written on the device.  One
+  ## msdos(getTime()) stamps all entries, as the reference stamps those of one call (:475-493).  Raises on the first
+  ## archive that failed.
+  if tables.len == 0: return
+  let (t, d) = msdos(getTime())
+  var es: seq[ZhZipNewEntry]
+  var first = @[0.csize_t]
+  for table in tables:
+    for k, v in table:                 # insertion order; the library lists them last to first
+      es.add ZhZipNewEntry(path: k.cstring, pathLen: k.len.csize_t,
+                           contents: (if v.len > 0: v[0].unsafeAddr else: nil), len: v.len.csize_t,
+                           isDirectory: 0, dosTime: t, dosDate: d)   # isDirectory is not read
+    first.add es.len.csize_t
+  var ps = newSeq[pointer](tables.len); var ns = newSeq[csize_t](tables.len); var sts = newSeq[int32](tables.len)
+  let rc = zh_zip_create_batch(engine(), (if es.len > 0: es[0].addr else: nil), first[0].addr, tables.len.csize_t,
+                               BestSpeed.cint, ps[0].addr, ns[0].addr, sts[0].addr)
+  var firstBad = rc
+  for i in 0 ..< tables.len:           # copy what came back, free everything, then raise
+    if firstBad == 0 and sts[i] != 0: firstBad = sts[i].cint
+  for i in 0 ..< tables.len:
+    if firstBad != 0:
+      if ps[i] != nil: zh_free(ps[i])
+    else:
+      result.add take(ps[i], ns[i], 0)
+  if firstBad != 0:
+    raise newException(ZippyError, $zh_strerror(firstBad))

@@ -448,8 +448,9 @@ typedef struct zh_zip_new_entry { /* one (path, ArchiveEntry) of ZipArchive.cont
   size_t path_len;
   const void *contents;           /* may be NULL when len == 0 */
   size_t len;
-  int is_directory;               /* ekDirectory: external attributes 0x10, else 0x20 */
+  int is_directory;               /* ekDirectory: external attributes 0x10, else 0x20 (zh_zip_create_batch: not read) */
   uint16_t dos_time, dos_date;    /* toMsDos(lastModified) (:356-369), from the caller: the call stays pure */
+                                  /* (zh_zip_create_batch: msdos(getTime()), the same pair for a whole archive) */
 } zh_zip_new_entry;
 /* Archive t is entries[first[t] .. first[t+1]) in insertion order (first has n_zip + 1 elements, non-decreasing).
  * level: -2..9 (ZH_DEFAULT_COMPRESSION gives the reference's bytes; other levels and contract mode give valid
@@ -479,6 +480,44 @@ typedef struct zh_zip_new_entry { /* one (path, ArchiveEntry) of ZipArchive.cont
  *    comment length 0. */
 int zh_zip_write_batch(zh_ctx *ctx, const zh_zip_new_entry *entries, const size_t *first, size_t n_zip,
                        int level, void **dsts, size_t *dst_lens, int32_t *statuses);
+
+/* createZipArchive(entries: OrderedTable[string, string]) -- ziparchives.nim:455-634 -- for n_zip in-memory archives
+ * at once: zh_zip_create's archives through zh_zip_write_batch's pipeline (one compress plan with CRC-32 over every
+ * non-empty entry of the call, the layout on the host from the compressed lengths, one kernel that writes every
+ * byte of every image, one download).  The shape, the ownership and the split of the errors are those of
+ * zh_zip_write_batch: archive t is entries[first[t] .. first[t+1]) in insertion order; dsts[t] is library-allocated
+ * (zh_free), NULL for an archive that failed; the return value is a call-level error (NULL pointers, also an entry's
+ * path or contents that is NULL with a non-zero length; bad first[]; a level outside -2..9, ZH_ERR_INVALID_LEVEL,
+ * checked before the table; more than 2^32 - 2 entries or archives in the call, ZH_ERR_ARGUMENT; allocation;
+ * device); everything about an archive's own entries is statuses[t], and a bad archive never changes the bytes of
+ * the others.  n_zip == 0 returns ZH_OK.
+ * Entries: zh_zip_new_entry, of which `is_directory` is NOT read (createZipArchive writes external attributes 0).
+ * dos_time / dos_date are written per entry; the reference stamps every entry of a call with one msdos(getTime())
+ * (:475-493), so a caller gets the reference's bytes by giving all entries of an archive the same pair.
+ * level: ZH_BEST_SPEED gives the reference's bytes (:530); other levels and contract mode (zh_set_l1_parse(ctx, 1))
+ * give valid archives with other deflate streams.
+ * Statuses: entry by entry in PROCESSING order, which is last to first (the reference pops keys off the table's end,
+ * :503-505), the first failure wins; within one entry, in zh_zip_create's order:
+ *  1. ZH_ERR_ZIP_NAME: an empty path;
+ *  2. ZH_ERR_ZIP_NAME: a path that starts with '/';
+ *  3. ZH_ERR_ZIP_NAME: a path longer than 65535 bytes;
+ *  4. ZH_ERR_ZIP_DUPLICATE: a path equal to that of an entry checked before it (a table key cannot repeat);
+ * after compression, the first entry's compress status (same order) that is not ZH_OK.
+ * An archive without entries is valid: its three end records, 98 bytes.  There are no 32-bit limits: every length
+ * and offset is 64-bit (an entry of 4 GiB and more is legal), the entry count too; ZH_ZIP32_LIMIT is not read.
+ * Bytes (all little-endian, :541-624):
+ *  - each entry, LAST TO FIRST: local header 50 4b 03 04, version 45, flags 0x0800, method, dos_time, dos_date,
+ *    crc32(contents), ff ff ff ff twice, path length, extra length 20; the path; the zip64 extra (id 1, size 16,
+ *    u64 length, u64 compressed length); the stream.  Method 0, no stream and CRC 0 when the contents are empty,
+ *    else method 8 and compress(contents, level, dfDeflate);
+ *  - the central directory in the same order: 50 4b 01 02, made-by 45, needed 45, flags 0x0800, method, time, date,
+ *    CRC, ff ff ff ff twice, path length, extra length 28, comment length / disk / internal / external attributes 0,
+ *    offset ff ff ff ff; the path; the zip64 extra (id 1, size 24, length, compressed length, local header offset);
+ *  - the zip64 end of central directory record (56 bytes: 50 4b 06 06, 44, 45, 45, disks 0 0, the entry count twice,
+ *    the directory's size and offset), its locator (20 bytes: 50 4b 06 07, 0, the zip64 end record's offset, 1) and
+ *    the end of central directory record (22 bytes: 50 4b 05 06, 0, 0, counts, size and offset ff-filled, 0). */
+int zh_zip_create_batch(zh_ctx *ctx, const zh_zip_new_entry *entries, const size_t *first, size_t n_zip,
+                        int level, void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
  * Introspection for parity tests (not part of the drop-in surface).   *

@@ -8,7 +8,7 @@ without a GPU.  There is no fallback between the two.
 import ctypes
 import os
 
-from .common import ZippyError, dfDetect, dfGzip, DefaultCompression
+from .common import ZippyError, dfDetect, dfGzip, BestSpeed, DefaultCompression
 
 _c = ctypes
 _SIGS = {
@@ -125,6 +125,8 @@ _SIGS = {
                                        _c.POINTER(_c.c_int32)]),
     "zh_zip_write_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
+    "zh_zip_create_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
+                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
     "zh_debug_tokens": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int,
                                    _c.POINTER(_c.POINTER(_c.c_uint16)), _c.POINTER(_c.c_size_t)]),
     "zh_debug_huffman": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.c_int, _c.c_int, _c.c_int, _c.c_int,
@@ -366,6 +368,35 @@ def _zip_entries(entries):
     return out
 
 
+def _zip_tables(tables, dos_time, dos_date):
+    """createZipArchive's tables (ziparchives.nim:455) as lists of _zip_entries tuples: ordered mappings or (path,
+    contents) pairs, every entry stamped with the call's dos_time / dos_date as the reference stamps them with one
+    msdos(getTime()); a value may also be (contents, dos_time, dos_date) with a pair of its own.  is_directory stays
+    False: zh_zip_create_batch does not read it."""
+    out = []
+    for table in tables:
+        group = []
+        for path, v in (table.items() if hasattr(table, "items") else table):
+            contents, t, d = v if isinstance(v, tuple) else (v, dos_time, dos_date)
+            p = path.encode("utf-8", "surrogateescape") if isinstance(path, str) else bytes(path)
+            group.append((p, contents, False, int(t), int(d)))
+        out.append(group)
+    return out
+
+
+def _zip_table(groups):
+    """The C arrays of the zip writers for lists of _zip_entries tuples (kept alive by the returned tuple)."""
+    keep = []
+
+    def fill(e, p, c, is_dir, t, d):
+        addr, n, k = _buffer_address(c)
+        keep.append(k)
+        e.path, e.path_len, e.contents, e.len = p, len(p), addr, n
+        e.is_directory, e.dos_time, e.dos_date = int(is_dir), t & 0xFFFF, d & 0xFFFF
+    arr, first, n, flat = _writer_table(ZipNewEntry, groups, fill)
+    return arr, first, n, (flat, keep)
+
+
 def _writer_table(entry_type, groups, fill):
     """groups: lists of entry tuples -> (entry array, first[], number of groups, the entry tuples); fill(entry, *tuple)
     sets one entry"""
@@ -576,15 +607,7 @@ class Engine:
     @staticmethod
     def prepare_zips(archives):
         """The C arrays of zh_zip_write_batch for `archives` (kept alive by the returned tuple)."""
-        keep = []
-
-        def fill(e, p, c, is_dir, t, d):
-            addr, n, k = _buffer_address(c)
-            keep.append(k)
-            e.path, e.path_len, e.contents, e.len = p, len(p), addr, n
-            e.is_directory, e.dos_time, e.dos_date = int(is_dir), t & 0xFFFF, d & 0xFFFF
-        arr, first, n, flat = _writer_table(ZipNewEntry, [_zip_entries(a) for a in archives], fill)
-        return arr, first, n, (flat, keep)
+        return _zip_table([_zip_entries(a) for a in archives])
 
     def write_zips_prepared(self, prepared, level=DefaultCompression):
         return self._run_writer(self.lib.zh_zip_write_batch, prepared, level)
@@ -608,6 +631,25 @@ class Engine:
     def write_zip(self, entries, level=DefaultCompression):
         """One archive's bytes; raises ZippyError on failure."""
         outs, sts = self.write_zips([entries], level)
+        return self._raise_first(outs, sts)[0]
+
+    def create_zips(self, tables, dos_time=0, dos_date=0, level=BestSpeed):
+        """createZipArchive (ziparchives.nim:455-634) of every table in one call (zh_zip_create_batch).
+        tables: a list of ordered mappings / (path, contents) pairs (see _zip_tables); BestSpeed is the reference's
+        level.  -> (list of bytes | None, statuses)"""
+        return self.create_zips_prepared(self.prepare_zips_v2(tables, dos_time, dos_date), level)
+
+    @staticmethod
+    def prepare_zips_v2(tables, dos_time=0, dos_date=0):
+        """The C arrays of zh_zip_create_batch for `tables` (kept alive by the returned tuple)."""
+        return _zip_table(_zip_tables(tables, dos_time, dos_date))
+
+    def create_zips_prepared(self, prepared, level=BestSpeed):
+        return self._run_writer(self.lib.zh_zip_create_batch, prepared, level)
+
+    def create_zips_one(self, entries, dos_time=0, dos_date=0, level=BestSpeed):
+        """One archive's bytes through the batch call; raises ZippyError on failure."""
+        outs, sts = self.create_zips([entries], dos_time, dos_date, level)
         return self._raise_first(outs, sts)[0]
 
     def crc32_batch(self, bufs):

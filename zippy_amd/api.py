@@ -68,6 +68,14 @@ def createZipArchive(entries, dos_time=0, dos_date=0):
     return engine().create_zip(entries, dos_time, dos_date)
 
 
+def createZipArchives(tables, dos_time=0, dos_date=0, level=BestSpeed):
+    """createZipArchive(OrderedTable) for many tables in one call (zh_zip_create_batch) -> a list of bytes, in order.
+    Raises ZippyError on the first archive that failed.  BestSpeed is the reference's level (ziparchives.nim:530)."""
+    eng = engine()
+    outs, sts = eng.create_zips(tables, dos_time, dos_date, level)
+    return eng._raise_first(outs, sts)
+
+
 def openTarball(image):
     """tarballs.nim:26-124 on the bytes of a .tar.gz / .tar -> reader with .entries, .contents(i)."""
     return engine().open_tar(image)

@@ -1147,3 +1147,353 @@ def check_segmented(eng, scale, monkeypatch, seg_bytes):
         assert w[1] == g_[1], (len(b), w[1], g_[1])
         if w[1] == [0]:
             assert w[0] == g_[0]
+
+
+# ---- the checksum kernels (csrc/zh_checksum.hip) against zlib.crc32 / zlib.adler32, which are exact: every length,
+# alignment and piece count at which the kernels take another path.  The borders below are the row sizes of the three
+# lane widths the kernel can be built with (1024 / 2048 / 4096), their neighbours, and the 32 KiB piece: written out,
+# not derived from the kernel's constants. ----
+CK_BORDERS = (512, 1024, 2048, 4096, 6144, 30720, 32768, 34816, 65536)
+ZH_ERR_CHECKSUM, ZH_ERR_DST_TOO_SMALL = 8, 21
+
+
+def checksum_lengths():
+    """L: 0..130, every border -17..+17, three pieces plus a byte"""
+    out = set(range(131))
+    for b in CK_BORDERS:
+        out.update(range(b - 17, b + 18))
+    out.add(98305)
+    return sorted(out)
+
+
+def checksum_lengths_aligned(small=False):
+    """L_a: 0..48, B-1, B, B+1, B+15, B+16, B+17 of every border, 98305.  small: the lengths up to 6200 and 32768,
+    32769, 65537."""
+    out = set(range(49))
+    for b in CK_BORDERS:
+        out.update((b - 1, b, b + 1, b + 15, b + 16, b + 17))
+    out.add(98305)
+    if small:
+        out = {n for n in out if n <= 6200 or n in (32768, 32769, 65537)}
+    return sorted(out)
+
+
+_ck_pools = {}
+
+
+def checksum_fill(kind, n):
+    """n bytes of a fill: 'rand' (seeded), 'ff' (the largest Adler sums), 'zero' (a CRC that depends on the length
+    alone: the conditioning terms), 'text' (corpus text for the matcher)"""
+    if kind not in _ck_pools:
+        if kind == "rand":
+            _ck_pools[kind] = np.random.default_rng(20260).integers(0, 256, 12 << 20, dtype=np.uint8).tobytes()
+        elif kind == "text":
+            _ck_pools[kind] = synth.corpus_file("alice29.txt")
+        else:
+            _ck_pools[kind] = {"ff": b"\xff", "zero": b"\x00"}[kind] * (12 << 20)
+    pool = _ck_pools[kind]
+    assert n <= len(pool)
+    return pool[:n]
+
+
+def check_checksum_lengths(eng, small=False):
+    """Host path (zh_crc32_batch, zh_adler32; every buffer at a 256-byte aligned address: head 0): every length of L,
+    one zh_crc32_batch call a fill with empty buffers first, last and in between; zh_adler32 a call a length.
+    small: the random fill only."""
+    lens = checksum_lengths()
+    for kind in ("rand",) if small else ("rand", "ff", "zero"):
+        bufs = [b""]
+        for k, n in enumerate(lens):
+            bufs.append(checksum_fill(kind, n))
+            if k % 40 == 7:
+                bufs.append(b"")
+        bufs.append(b"")
+        got = eng.crc32_batch(bufs)
+        bad = [(len(b), hex(g)) for b, g in zip(bufs, got) if g != zlib.crc32(b)]
+        assert not bad, ("crc32_batch", kind, bad[:8])
+    for kind in ("rand",) if small else ("rand", "ff"):
+        bad = []
+        for n in lens:
+            b = checksum_fill(kind, n)
+            g = eng.adler32(b)
+            if g != zlib.adler32(b):
+                bad.append((n, hex(g)))
+        assert not bad, ("adler32", kind, bad[:8])
+
+
+def _ck_pack_sources(srcs, aligns, pad=0xA7):
+    """One blob with srcs[i] at an offset that is aligns[i] (mod 16), 16 spare bytes in front and 64 behind (the plans
+    read whole words around a source) -> (blob, offsets)"""
+    blob = bytearray(bytes([pad]) * 16)
+    offs = []
+    for s, a in zip(srcs, aligns):
+        blob += bytes([pad]) * ((a - len(blob)) % 16)
+        offs.append(len(blob))
+        blob += s
+    blob += bytes([pad]) * 64
+    return bytes(blob), offs
+
+
+def _ck_compress_plan(eng, d_src, soff, srcs, level, fmt, alloc, download, want_crcs=True):
+    """One compress plan over srcs -> (streams, statuses, crcs)"""
+    caps = [eng.compress_bound(len(s), fmt) for s in srcs]
+    doff, pos = [], 4
+    for c in caps:
+        doff.append(pos)
+        pos += c + 5
+    d_dst, keep = alloc(pos + 64, 0x5A)
+    plan = eng.plan_compress(soff, [len(s) for s in srcs], doff, caps, level, fmt)
+    if want_crcs:
+        plan.request_crc32()
+    plan.run(d_src, d_dst)
+    lens, sts = plan.results()
+    crcs = plan.crc32() if want_crcs else None
+    got = download(keep)
+    plan.close()
+    return [got[o:o + n] for o, n in zip(doff, lens)], sts, crcs
+
+
+def check_checksum_alignment(eng, upload, download, alloc, small=False):
+    """Compress plans whose sources start at every address mod 16 (the kernel's head of 0..15 bytes, taken by one lane;
+    the host calls only ever give it head 0): level 0, one dfGzip and one dfZlib plan over every length of L_a at every
+    alignment -- trailer CRC-32 / ISIZE / Adler-32 against zlib, zh_plan_crc32 of both plans (the zlib plan then makes
+    both checksums in one launch), the whole stream against the oracle; then alignments 0, 5, 15 at level 1 on text,
+    the checksum beside the matcher.  small: alignments 0, 1, 15 and checksum_lengths_aligned(small=True)."""
+    eng.set_gzip_fname_len(0)
+    lens = checksum_lengths_aligned(small)
+    for kind, level, aligns in (("rand", 0, (0, 1, 15) if small else range(16)), ("ff", 0, (0, 1, 15) if small else range(16)),
+                                ("text", 1, (0, 5, 15))):
+        srcs = [checksum_fill(kind, n) for a in aligns for n in lens]
+        want_a = [a for a in aligns for n in lens]
+        blob, soff = _ck_pack_sources(srcs, want_a)
+        d_src, keep_src = upload(blob)
+        assert [(d_src + o) % 16 for o in soff] == want_a, "a source is not at the address (mod 16) it is meant to test"
+        for fmt in (oracle.dfGzip, oracle.dfZlib) if level == 0 else (oracle.dfGzip,):
+            outs, sts, crcs = _ck_compress_plan(eng, d_src, soff, srcs, level, fmt, alloc, download)
+            for i, (s, out) in enumerate(zip(srcs, outs)):
+                at = (kind, level, fmt, "align", want_a[i], "len", len(s))
+                assert sts[i] == 0, at + (sts[i],)
+                if fmt == oracle.dfGzip:
+                    assert struct.unpack("<II", out[-8:]) == (zlib.crc32(s), len(s)), at + ("gzip trailer",)
+                else:
+                    assert struct.unpack(">I", out[-4:])[0] == zlib.adler32(s), at + ("zlib trailer",)
+                assert crcs[i] == zlib.crc32(s), at + ("zh_plan_crc32",)
+                assert out == oracle.compress(s, level, fmt, fname_len=0), at + ("stream",)
+                if level != 0:
+                    assert zlib.decompress(out, WBITS[fmt]) == s, at
+
+
+def _ck_streams(data, wbits):
+    c = zlib.compressobj(1, zlib.DEFLATED, wbits)
+    return c.compress(data) + c.flush()
+
+
+def check_checksum_uncompress(eng, upload, download, alloc, small=False):
+    """Uncompress plans: the piece length comes from the device (dyn_len) and is clamped to the piece's share of the
+    slot, and the verify step compares with the stored checksum.  zlib-made gzip and zlib streams of every length of
+    L_a, each OUTPUT at every address mod 16, capacities of len + 0 / 1 / 40000 (clamped, empty and short last pieces),
+    in memory filled with a pattern; a dfGzip, a dfZlib and a dfDetect plan (both kinds interleaved), zh_plan_crc32 on
+    each.  Then: a bit of the stored checksum flipped in every third stream (status 8, the oracle rejects them too);
+    every fifth slot one byte short (status 21; neighbours and guard bytes untouched); the statuses from
+    zh_plan_device_statuses; and the first run as two halves (ZH_INFLATE_HALVES: the first half's checksum launch).
+    small: alignments 0, 1, 15, checksum_lengths_aligned(small=True), one fill a stream in turn (the full case runs
+    the random and the 0xFF fill whole)."""
+    import ctypes
+    PAT = 0xC3
+    lens = checksum_lengths_aligned(small)
+    aligns = (0, 1, 15) if small else range(16)
+    want_a = [a for a in aligns for n in lens]
+    n = len(want_a)
+    for kinds in (("rand", "ff", "zero"),) if small else (("rand",), ("ff",)):
+        datas = [checksum_fill(kinds[i % len(kinds)], ln) for i, ln in enumerate(lens * len(aligns))]
+        per_kind = {wb: [_ck_streams(d, wb) for d in datas] for wb in (31, 15)}
+        for d, g, z in zip(datas[::7], per_kind[31][::7], per_kind[15][::7]):  # (the premise: what zlib made, zlib reads)
+            assert zlib.decompress(g, 31) == d and zlib.decompress(z, 15) == d
+
+        def flipped(blob, wb, i):
+            b = bytearray(blob)
+            b[len(b) - (8 if wb == 31 else 4) + i % 4] ^= 1 << (i % 8)  # the CRC-32 / Adler-32 field, not ISIZE
+            return bytes(b)
+        bad_kind = {wb: [flipped(b, wb, i) if i % 3 == 0 else b for i, b in enumerate(per_kind[wb])] for wb in (31, 15)}
+        for wb, fmt in ((31, oracle.dfGzip), (15, oracle.dfZlib)):
+            for i in range(0, n, 3):
+                try:
+                    oracle.uncompress(bad_kind[wb][i], fmt)
+                    assert False, ("the oracle accepts a stream with a flipped checksum", wb, len(datas[i]))
+                except oracle.ZippyError:
+                    pass
+        # sources: gzip streams, zlib streams, and both with the flipped ones, in one blob
+        groups = [per_kind[31], per_kind[15], bad_kind[31], bad_kind[15]]
+        flat = [b for g in groups for b in g]
+        blob, soff = _ck_pack_sources(flat, [(5 * i) % 16 for i in range(len(flat))])
+        d_src, keep_src = upload(blob)
+        goff = [soff[k * n:(k + 1) * n] for k in range(4)]
+
+        def layout(caps):  # (for memory that starts at a multiple of 16: checked against the pointer below)
+            off, pos = [], 16
+            for a, c in zip(want_a, caps):
+                pos += (a - pos) % 16
+                off.append(pos)
+                pos += c + 3
+            return off, pos + 64
+
+        def run(plan_fmt, pick, caps, bad_every=0):
+            """pick(i) -> index of the source group of stream i; -> (lens, sts, crcs, device statuses, output memory, offsets)"""
+            off, total = layout(caps)
+            d_dst, keep = alloc(total, PAT)
+            assert [(d_dst + o) % 16 for o in off] == want_a, "an output is not at the address (mod 16) it is meant to test"
+            plan = eng.plan_uncompress([goff[pick(i)][i] for i in range(n)], [len(groups[pick(i)][i]) for i in range(n)],
+                                       off, caps, plan_fmt)
+            plan.request_crc32()
+            plan.run(d_src, d_dst)
+            olens, sts = plan.results()
+            crcs = plan.crc32()
+            host = (ctypes.c_int32 * n)()
+            eng._check(eng.lib.zh_device_download(eng._h, host, plan.device_statuses(), n * 4))
+            got = np.frombuffer(download(keep), np.uint8)
+            plan.close()
+            return olens, sts, crcs, list(host), got, off
+
+        def expect(plan_name, res, caps, failing, status):
+            """streams in `failing` end with `status`, all others with 0, their bytes and CRC-32; nothing outside the
+            slots of the failing ones and the outputs of the others differs from the pattern"""
+            olens, sts, crcs, dev_sts, got, off = res
+            assert dev_sts == sts, (plan_name, "zh_plan_device_statuses differs from zh_plan_results")
+            want = np.full(len(got), PAT, np.uint8)
+            care = np.ones(len(got), bool)
+            for i, d in enumerate(datas):
+                at = (plan_name, kinds[i % len(kinds)], "align", want_a[i], "len", len(d), "cap", caps[i])
+                if i in failing:
+                    assert sts[i] == status, at + (sts[i],)
+                    care[off[i]:off[i] + caps[i]] = False  # (the slot of a failed stream is its own to scribble in)
+                    continue
+                assert sts[i] == 0, at + (sts[i],)
+                assert olens[i] == len(d), at + (olens[i],)
+                assert crcs[i] == zlib.crc32(d), at + ("zh_plan_crc32", hex(crcs[i]))
+                want[off[i]:off[i] + len(d)] = np.frombuffer(d, np.uint8)
+            diff = np.nonzero((got != want) & care)[0]
+            if len(diff):
+                k = max(i for i in range(n) if off[i] <= diff[0]) if diff[0] >= off[0] else -1
+                assert False, (plan_name, "memory differs at", int(diff[0]), "stream", k, "at", off[k], "len", len(datas[k]))
+
+        plans = (("gzip", oracle.dfGzip, lambda i: 0), ("zlib", oracle.dfZlib, lambda i: 1),
+                 ("detect", oracle.dfDetect, lambda i: i % 2))
+        caps = [len(d) + (0, 1, 40000)[i % 3] for i, d in enumerate(datas)]
+        short = {i for i, d in enumerate(datas) if i % 5 == 0 and len(d) >= 1}
+        caps_short = [len(d) - 1 if i in short else c for i, (d, c) in enumerate(zip(datas, caps))]
+        for name, fmt, pick in plans:
+            expect(name, run(fmt, pick, caps), caps, (), 0)
+            expect(name + ", flipped checksums", run(fmt, lambda i: pick(i) + 2, caps), caps, set(range(0, n, 3)), ZH_ERR_CHECKSUM)
+            expect(name + ", slots one byte short", run(fmt, pick, caps_short), caps_short, short, ZH_ERR_DST_TOO_SMALL)
+        old = os.environ.get("ZH_INFLATE_HALVES")
+        os.environ["ZH_INFLATE_HALVES"] = "4"  # (read when a plan is made)
+        try:
+            for name, fmt, pick in plans:
+                expect(name + ", two halves", run(fmt, pick, caps), caps, (), 0)
+        finally:
+            if old is None:
+                del os.environ["ZH_INFLATE_HALVES"]
+            else:
+                os.environ["ZH_INFLATE_HALVES"] = old
+
+
+CK_PIECE_COUNTS = (1, 2, 63, 64, 65, 66, 127, 128, 129, 191, 192, 193, 256, 257, 258, 319, 320, 321)
+
+
+def checksum_piece_count_sizes(small=False):
+    """(np - 1) * 32768 + last bytes: last in turn 1, 32767, 32768, all three for np = 65, 129, 257, 321 (shares of 1
+    to 6 pieces a lane, the table in LDS from 257 pieces on, lanes with a partial share, an empty one, and right-hand
+    sides of exactly whole pieces).  small: np up to 258."""
+    sizes, turn = [], 0
+    for npieces in CK_PIECE_COUNTS:
+        if small and npieces > 258:
+            break
+        if npieces in (65, 129, 257, 321):
+            lasts = (1, 32767, 32768)
+        else:
+            lasts = ((1, 32767, 32768)[turn % 3],)
+            turn += 1
+        sizes += [(npieces - 1) * 32768 + last for last in lasts]
+    return sizes
+
+
+def check_checksum_piece_counts(eng, upload, download, alloc, small=False):
+    """The combine kernel: buffers of checksum_piece_count_sizes() -- CRC-32 of all of them in ONE zh_crc32_batch call
+    (first_piece indexing across buffers), Adler-32 a buffer a call (random bytes; 0xFF for the four largest); then
+    65 and 257 pieces through a level 0 gzip plan with the source at an address of 7 (mod 16): a head and a ragged
+    share in one run.  small: np up to 258, and 65 pieces alone through the plan."""
+    sizes = checksum_piece_count_sizes(small)
+    bufs = [checksum_fill("rand", n) for n in sizes]
+    want = [zlib.crc32(b) for b in bufs]
+    got = eng.crc32_batch(bufs)
+    bad = [(n, -(-n // 32768), hex(g)) for n, g, w in zip(sizes, got, want) if g != w]
+    assert not bad, ("crc32_batch: (bytes, pieces, got)", bad)
+    bad = []
+    for kind, some in (("rand", sizes), ("ff", sorted(sizes)[-4:])):
+        for n in some:
+            b = checksum_fill(kind, n)
+            g = eng.adler32(b)
+            if g != zlib.adler32(b):
+                bad.append((kind, n, -(-n // 32768), hex(g)))
+    assert not bad, ("adler32: (fill, bytes, pieces, got)", bad)
+    eng.set_gzip_fname_len(0)
+    srcs = [checksum_fill("rand", 64 * 32768 + 1)] + ([] if small else [checksum_fill("rand", 256 * 32768 + 32767)])
+    blob, soff = _ck_pack_sources(srcs, [7] * len(srcs))
+    d_src, keep_src = upload(blob)
+    assert [(d_src + o) % 16 for o in soff] == [7] * len(srcs)
+    outs, sts, crcs = _ck_compress_plan(eng, d_src, soff, srcs, 0, oracle.dfGzip, alloc, download)
+    for s, out, st, crc in zip(srcs, outs, sts, crcs):
+        assert st == 0
+        assert struct.unpack("<II", out[-8:]) == (zlib.crc32(s), len(s) & 0xffffffff), ("gzip trailer", len(s))
+        assert crc == zlib.crc32(s), ("zh_plan_crc32", len(s))
+        assert zlib.decompress(out, 31) == s
+
+
+def check_checksum_entry_points(eng, small=False):
+    """zh_compress_batch_crc32 (dfDeflate, levels 1 and 0): the CRC-32s are zlib's, streams and statuses those of
+    zh_compress_batch -- as one plan and as pipelined groups.  zh_uncompress_batch_sized with CRCs over the same inputs
+    as raw deflate and zlib streams (Python's zlib), the hints in turn exact, 0, half the size (the retry pass, which
+    fetches the CRCs of the streams it decodes again separately) and four times the size: outputs and statuses are
+    zh_uncompress_batch's, the CRC-32s zlib's; a truncated stream in the middle fails alone.  small: inputs of at
+    most 40 KB."""
+    inputs = checksum_entry_point_inputs(small)
+    want_crc = [zlib.crc32(b) for b in inputs]
+    for pipe in ((1 << 60, 0), (1, 150000)):
+        try:
+            eng.set_host_pipeline(*pipe)
+            for level in (1, 0):
+                outs, sts, crcs = eng.compress_batch_crc32(inputs, level, oracle.dfDeflate)
+                assert crcs == want_crc, (pipe, level, [len(b) for b, c, w in zip(inputs, crcs, want_crc) if c != w])
+                assert (outs, sts) == eng.compress_batch(inputs, level, oracle.dfDeflate), (pipe, level)
+                assert all(s == 0 for s in sts)
+                for b, out in zip(inputs[::5], outs[::5]):
+                    assert zlib.decompress(out, -15) == b
+            for fmt, wb in ((oracle.dfDeflate, -15), (oracle.dfZlib, 15)):
+                blobs = []
+                for k, b in enumerate(inputs):
+                    c = zlib.compressobj((1, 6, 9)[k % 3], zlib.DEFLATED, wb)
+                    blobs.append(c.compress(b) + c.flush())
+                cut = len(blobs) // 2
+                blobs[cut] = blobs[cut][:len(blobs[cut]) * 2 // 3]  # truncated
+                hints = [(len(b), 0, len(b) // 2, 4 * len(b))[k % 4] for k, b in enumerate(inputs)]
+                outs, sts, crcs = eng.uncompress_batch_sized(blobs, fmt, hints)
+                assert (outs, sts) == eng.uncompress_batch(blobs, fmt), (pipe, fmt)
+                for k, b in enumerate(inputs):
+                    if k == cut:
+                        assert sts[k] != 0 and outs[k] is None, (pipe, fmt, sts[k])
+                    else:
+                        assert sts[k] == 0 and outs[k] == b, (pipe, fmt, k, len(b), sts[k])
+                        assert crcs[k] == want_crc[k], (pipe, fmt, k, len(b), hints[k], hex(crcs[k]))
+                outs2, sts2, none = eng.uncompress_batch_sized(blobs, fmt, hints, want_crcs=False)
+                assert (outs2, sts2, none) == (outs, sts, None)
+        finally:
+            eng.set_host_pipeline(0, 0)
+
+
+def checksum_entry_point_inputs(small=False):
+    """edge_inputs() and three corpus slices of 70-200 KB (small: everything of at most 40 KB, the slices cut to it)"""
+    inputs = edge_inputs() + [synth.corpus_file("alice29.txt")[:70001], synth.corpus_file("html")[1000:101000],
+                              synth.corpus_file("kppkn.gtb")[:180000]]
+    if small:
+        inputs = [b for b in inputs[:-3] if len(b) <= 40000] + [b[:40000 - 777 * k] for k, b in enumerate(inputs[-3:])]
+    return inputs

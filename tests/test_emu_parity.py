@@ -41,21 +41,6 @@ def _first_cap_batches():
             "pipelined": [synth.corpus_file("alice29.txt")[:100000], synth.corpus_file("geo.protodata")[:70000]] + edge}
 
 
-def _compress_batch_crc32(eng, bufs, level, fmt):
-    import ctypes as c
-    n = len(bufs)
-    srcs = (c.c_void_p * n)(*[c.cast(c.c_char_p(b), c.c_void_p) for b in bufs])
-    lens = (c.c_size_t * n)(*[len(b) for b in bufs])
-    dsts, dlens, sts, crcs = (c.c_void_p * n)(), (c.c_size_t * n)(), (c.c_int32 * n)(), (c.c_uint32 * n)()
-    rc = eng.lib.zh_compress_batch_crc32(eng._h, srcs, lens, n, level, fmt, dsts, dlens, sts, crcs)
-    outs = [c.string_at(dsts[i], dlens[i]) if dsts[i] else None for i in range(n)]
-    for i in range(n):
-        if dsts[i]:
-            eng.lib.zh_free(dsts[i])
-    eng._check(rc)
-    return outs, list(sts), list(crcs)
-
-
 @pytest.mark.parametrize("kind", ["plain", "pipelined"])
 def test_emu_compress_first_cap_retry(eng, monkeypatch, kind):
     """ZH_COMPRESS_FIRST_CAP=64: most outputs outgrow their first slots, so the plain path runs its plan a second time
@@ -63,11 +48,11 @@ def test_emu_compress_first_cap_retry(eng, monkeypatch, kind):
     import zlib
     batch = _first_cap_batches()[kind]
     want = eng.compress_batch(batch, 1, oracle.dfGzip)
-    want_crc = _compress_batch_crc32(eng, batch, 1, oracle.dfDeflate)
+    want_crc = eng.compress_batch_crc32(batch, 1, oracle.dfDeflate)
     assert want_crc[2] == [zlib.crc32(b) for b in batch]
     monkeypatch.setenv("ZH_COMPRESS_FIRST_CAP", "64")
     assert eng.compress_batch(batch, 1, oracle.dfGzip) == want
-    assert _compress_batch_crc32(eng, batch, 1, oracle.dfDeflate) == want_crc
+    assert eng.compress_batch_crc32(batch, 1, oracle.dfDeflate) == want_crc
     pc.check_compress_identical(eng, batch, levels=(1,), formats=(oracle.dfGzip, oracle.dfDeflate))
 
 

@@ -183,6 +183,21 @@ class Plan:
     def device_lens(self):
         return self.engine.lib.zh_plan_device_lens(self._h)
 
+    def device_statuses(self):
+        """Device pointer of the n int32 statuses (zh_plan_device_statuses); valid after run."""
+        return self.engine.lib.zh_plan_device_statuses(self._h)
+
+    def request_crc32(self, on=True):
+        """CRC-32 of the uncompressed side of every buffer, whatever the container: before run (zh_plan_request_crc32)."""
+        self.engine._check(self.engine.lib.zh_plan_request_crc32(self._h, 1 if on else 0))
+
+    def crc32(self):
+        """The n CRC-32s requested with request_crc32, after run (zh_plan_crc32)."""
+        crcs = (_c.c_uint32 * max(1, self.n))()
+        if self.n:
+            self.engine._check(self.engine.lib.zh_plan_crc32(self._h, crcs))
+        return list(crcs)[:self.n]
+
     def set_src_lens_device(self, d_lens):
         self.engine._check(self.engine.lib.zh_plan_set_src_lens_device(self._h, d_lens))
 
@@ -494,6 +509,24 @@ class Engine:
 
     def uncompress_batch(self, bufs, data_format=dfDetect):
         return self._batch(self.lib.zh_uncompress_batch, bufs, data_format)
+
+    def compress_batch_crc32(self, bufs, level=DefaultCompression, data_format=dfGzip):
+        """compress_batch that also returns crc32(bufs[i]) (zh_compress_batch_crc32) -> (outs, statuses, crcs)"""
+        crcs = (_c.c_uint32 * max(1, len(bufs)))()
+        outs, sts = self._batch(lambda *a: self.lib.zh_compress_batch_crc32(*a, crcs), bufs, level, data_format)
+        return outs, sts, list(crcs)[:len(bufs)]
+
+    def uncompress_batch_sized(self, bufs, data_format=dfDetect, size_hints=None, want_crcs=True):
+        """uncompress_batch with the output sizes known up front (zh_uncompress_batch_sized): size_hints[i] replaces
+        the guess for streams without a size field (None: no hints).  -> (outs, statuses, crcs); crcs[i] is the
+        CRC-32 of output i where its status is 0 (None without want_crcs)."""
+        n = len(bufs)
+        hints = _u64(size_hints) if size_hints is not None else None
+        if hints is not None and len(hints) != n:
+            raise ValueError("size_hints: one per buffer")
+        crcs = (_c.c_uint32 * max(1, n))() if want_crcs else None
+        outs, sts = self._batch(lambda *a: self.lib.zh_uncompress_batch_sized(*a, crcs), bufs, data_format, hints)
+        return outs, sts, (list(crcs)[:n] if want_crcs else None)
 
     def _batch_into(self, fn, bufs, outs, *mid):
         """`outs`: writable buffers (bytearray / ctypes arrays) the library fills.

@@ -211,6 +211,68 @@ proc hipTarballImage*(entries: openArray[tuple[path, contents: string, kind: cha
                                p.addr, n.addr, st.addr)
   take(p, n, if rc != 0: rc else: st.cint)
 
+# ---- reading tarballs in batches (src/zippy/tarballs.nim extractAll) ----
+type
+  ZhTarEntry {.bycopy.} = object
+    path: cstring                       # not NUL-terminated: use pathLen
+    pathLen: csize_t
+    linkname: cstring                   # symlinks (typeflag '2'); not NUL-terminated: use linknameLen
+    linknameLen: csize_t
+    typeflag: char                      # '0' or '\0' file, '5' directory, '2' symlink
+    mode: uint32
+    mtime: int64
+    offset, size: uint64                # the entry's bytes inside zh_tar_data()
+  HipTarEntry* = object
+    path*, linkname*, contents*: string
+    typeflag*: char
+    mode*: uint32
+    mtime*: int64
+
+proc zh_tar_open_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, nTar: csize_t,
+                       readers: ptr pointer, statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_tar_close(reader: pointer) {.importc, cdecl, dynlib: zhLib.}
+proc zh_tar_num_entries(reader: pointer): csize_t {.importc, cdecl, dynlib: zhLib.}
+proc zh_tar_entry_at(reader: pointer, i: csize_t, e: ptr ZhTarEntry): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_tar_data(reader: pointer, len: ptr csize_t): pointer {.importc, cdecl, dynlib: zhLib.}
+
+proc hipOpenTarballs*(images: openArray[string]): seq[seq[HipTarEntry]] {.raises: [ZippyError].} =
+  ## the loop body of extractAll (tarballs.nim:40-124) for many tarballs in one call: every .tar.gz gunzipped
+  ## (trustSize) in one batch, every header walk on the device; raises on the first image that failed, as the
+  ## reference would on that file.  The caller keeps createDir / writeFile / permissions / mtimes (:98-131).
+  let n = images.len
+  if n == 0: return
+  var
+    ptrs = newSeq[pointer](n)
+    lens = newSeq[csize_t](n)
+    readers = newSeq[pointer](n)
+    sts = newSeq[int32](n)
+  for i, s in images:
+    ptrs[i] = if s.len > 0: s[0].unsafeAddr else: nil
+    lens[i] = s.len.csize_t
+  let rc = zh_tar_open_batch(engine(), ptrs[0].addr, lens[0].addr, n.csize_t, readers[0].addr, sts[0].addr)
+  try:
+    if rc != 0: raise newException(ZippyError, $zh_strerror(rc))
+    for st in sts:
+      if st != 0: raise newException(ZippyError, $zh_strerror(st.cint))
+    result = newSeq[seq[HipTarEntry]](n)
+    for t in 0 ..< n:
+      var dataLen: csize_t
+      let data = cast[ptr UncheckedArray[char]](zh_tar_data(readers[t], dataLen.addr))
+      for i in 0 ..< zh_tar_num_entries(readers[t]).int:
+        var e: ZhTarEntry
+        discard zh_tar_entry_at(readers[t], i.csize_t, e.addr)
+        var item = HipTarEntry(typeflag: e.typeflag, mode: e.mode, mtime: e.mtime)
+        item.path = newString(e.pathLen.int)
+        if e.pathLen > 0: copyMem(item.path[0].addr, e.path, e.pathLen.int)
+        item.linkname = newString(e.linknameLen.int)
+        if e.linknameLen > 0: copyMem(item.linkname[0].addr, e.linkname, e.linknameLen.int)
+        item.contents = newString(e.size.int)
+        if e.size > 0: copyMem(item.contents[0].addr, data[e.offset.int].addr, e.size.int)
+        result[t].add item
+  finally:
+    for r in readers:
+      if r != nil: zh_tar_close(r)
+
 # ---- writing zip archives (src/zippy/ziparchives_v1.nim) ----
 import std/times
 

@@ -404,6 +404,21 @@ size_t zh_tar_num_entries(const zh_tar_reader *reader);
 int zh_tar_entry_at(const zh_tar_reader *reader, size_t i, zh_tar_entry *out);
 const void *zh_tar_data(const zh_tar_reader *reader, size_t *len);
 
+/* extractAll of tarballs.nim:26-124 (without the file system) for n_tar images per call.
+ * readers[t]: an ordinary reader -- zh_tar_num_entries / zh_tar_entry_at / zh_tar_data / zh_tar_close --, NULL when
+ * statuses[t] != 0.  statuses[t] is exactly what zh_tar_open(ctx, images[t], lens[t], ..) returns for
+ * that image alone; a bad image never changes the others.  The return value is a call-level error only:
+ * NULL arrays, an image that is NULL with a non-zero length, allocation, device.
+ * A plain .tar image is borrowed until its reader is closed; the uncompressed image of a .tar.gz is owned by its
+ * reader.  ctx is required (the header walk runs on the device for plain images too); n_tar == 0 launches nothing.
+ * Every gzip member of the call is decoded by one uncompress plan, with ISIZE as the output size; the header walk
+ * of tarballs.nim:61-124 runs for all images at once: every 512-byte block is read as if it were a header, the
+ * blocks reachable from an image's first block -- its headers -- are found by pointer doubling, and one wave per
+ * header parses it and checks it (csrc/zh_tar_open_batch.hip).  The host parses no header byte.
+ * More than 2^32 - 2 blocks of 512 bytes in one call (2 TiB of uncompressed images): ZH_ERR_ARGUMENT. */
+int zh_tar_open_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n_tar,
+                      zh_tar_reader **readers, int32_t *statuses);
+
 /* Writing tarballs: writeTarball(tarball, path) -- tarballs_v1.nim:203-270 -- for n_tar in-memory
  * tarballs at once, without the file write.  The host lays the images out and sends every entry's
  * contents straight to its place in HBM; one kernel writes the 512-byte ustar headers, the zero

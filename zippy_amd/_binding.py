@@ -120,6 +120,8 @@ _SIGS = {
     "zh_tar_num_entries": (_c.c_size_t, [_c.c_void_p]),
     "zh_tar_entry_at": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "zh_tar_data": (_c.c_void_p, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "zh_tar_open_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                     _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int32)]),
     "zh_tar_create_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
                                        _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
                                        _c.POINTER(_c.c_int32)]),
@@ -309,11 +311,15 @@ class TarEntry(_c.Structure):
 class TarReader:
     """zh_tar_reader: the entries of a .tar.gz / .tar image (tarballs.nim:61-124)."""
 
-    def __init__(self, engine, image):
+    def __init__(self, engine, image, handle=None):
+        """handle: a reader zh_tar_open_batch made of `image` (Engine.open_tars); None: zh_tar_open"""
         self.engine = engine
         self._image = bytes(image)  # an uncompressed tarball stays borrowed until close
         h = _c.c_void_p()
-        engine._check(engine.lib.zh_tar_open(engine._h, self._image, len(self._image), _c.byref(h)))
+        if handle is None:
+            engine._check(engine.lib.zh_tar_open(engine._h, self._image, len(self._image), _c.byref(h)))
+        else:
+            h = _c.c_void_p(handle)
         self._h = h
         n = _c.c_size_t()
         base = engine.lib.zh_tar_data(h, _c.byref(n))
@@ -608,6 +614,17 @@ class Engine:
 
     def open_tar(self, image):
         return TarReader(self, image)
+
+    def open_tars(self, images):
+        """zh_tar_open_batch: the images of many .tar.gz / .tar files opened in one call -> (readers, statuses);
+        readers[t] is a TarReader, or None where statuses[t] != 0."""
+        images = [bytes(b) for b in images]
+        n = len(images)
+        srcs = (_c.c_void_p * n)(*[_c.cast(_c.c_char_p(b), _c.c_void_p) if b else None for b in images])
+        lens = (_c.c_size_t * n)(*[len(b) for b in images])
+        handles, sts = (_c.c_void_p * n)(), (_c.c_int32 * n)()
+        self._check(self.lib.zh_tar_open_batch(self._h, srcs, lens, n, handles, sts))
+        return [TarReader(self, b, h) if h else None for b, h in zip(images, handles)], list(sts)
 
     def create_tars(self, tarballs, data_format=dfGzip, level=DefaultCompression):
         """writeTarball (tarballs_v1.nim:203-270) of every tarball in one call (zh_tar_create_batch).

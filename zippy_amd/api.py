@@ -81,6 +81,14 @@ def openTarball(image):
     return engine().open_tar(image)
 
 
+def openTarballs(images):
+    """openTarball for many images in one call (zh_tar_open_batch): every .tar.gz decoded in one batch, every header
+    walk on the device -> a list of readers, in order.  Raises ZippyError on the first image that failed."""
+    eng = engine()
+    readers, sts = eng.open_tars(images)
+    return eng._raise_first(readers, sts)
+
+
 def writeTarball(entries, dataFormat=dfGzip, level=DefaultCompression):
     """tarballs_v1.nim:203-270 writeTarball without the file write -> the bytes of the .tar.gz (dfGzip) or .tar
     (TAR_PLAIN).  entries: ordered mapping / (path, value) pairs; a value is the contents, or (contents, kind, mtime)

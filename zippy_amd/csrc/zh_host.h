@@ -1,10 +1,11 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in nine files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in ten files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
 // wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
-// zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks) and the batch writers
-// zh_zip_write.hip / zh_tar_create.hip (whose kernels sit next to their host code).  No compute happens on the host.
+// zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks) the batch writers
+// zh_zip_write.hip / zh_tar_create.hip and the batch reader zh_tar_open_batch.hip (whose kernels sit next to their host
+// code).  No compute happens on the host.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -336,6 +337,15 @@ ZH_INTERNAL int zhh_upload_spans(zh_ctx* ctx, std::initializer_list<std::pair<co
 ZH_INTERNAL int zhh_compress(zh_ctx* ctx, const uint8_t* d_src, const std::vector<uint64_t>& soff,
                              const std::vector<uint64_t>& slen, int level, int fmt, uint32_t* crcs, DevBuf& dst,
                              std::vector<uint64_t>& doff, std::vector<uint64_t>& clen, std::vector<int32_t>& cst);
+
+// (zh_tar.hip) the readers zh_tar_open_batch builds from its kernels' records: an empty reader over `data` (owned: the
+// reader's to release, or NULL for a borrowed image), then its entries in walk order
+extern "C" {
+ZH_INTERNAL zh_tar_reader* zh_tar_reader_new(void* owned, const void* data, size_t len);
+ZH_INTERNAL int zh_tar_reader_add(zh_tar_reader* r, const char* path, size_t path_len, const char* linkname,
+                                  size_t linkname_len, char typeflag, uint32_t mode, int64_t mtime, uint64_t offset,
+                                  uint64_t size);
+}
 
 // ---- the batch writers (zh_tar_create_batch, zh_zip_write_batch) ----
 // Their call-level checks, in this order: the pointers; dsts / dst_lens / statuses cleared; `bad_call` (the code of a

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <new>
 #include <string>
 #include <vector>
 
@@ -178,5 +179,30 @@ extern "C" int zh_tar_entry_at(const zh_tar_reader* r, size_t i, zh_tar_entry* o
   out->mtime = e.mtime;
   out->offset = e.offset;
   out->size = e.size;
+  return ZH_OK;
+}
+
+// zh_tar_open_batch (zh_tar_open_batch.hip) builds its readers from the records its kernels made: an empty reader over
+// `data` (owned: released by zh_tar_close, or NULL for a borrowed image), then its entries in walk order.
+extern "C" __attribute__((visibility("hidden"))) zh_tar_reader* zh_tar_reader_new(void* owned, const void* data,
+                                                                                 size_t len) {
+  zh_tar_reader* r = new (std::nothrow) zh_tar_reader;
+  if (!r) return nullptr;
+  r->owned = owned;
+  r->data = (const uint8_t*)data;
+  r->len = len;
+  return r;
+}
+extern "C" __attribute__((visibility("hidden"))) int zh_tar_reader_add(zh_tar_reader* r, const char* path,
+                                                                       size_t path_len, const char* linkname,
+                                                                       size_t linkname_len, char typeflag,
+                                                                       uint32_t mode, int64_t mtime, uint64_t offset,
+                                                                       uint64_t size) {
+  try {
+    r->entries.push_back(Entry{std::string(path, path_len), std::string(linkname, linkname_len), typeflag, mode, mtime,
+                               offset, size});
+  } catch (...) {
+    return ZH_ERR_NOMEM;
+  }
   return ZH_OK;
 }

@@ -1,0 +1,639 @@
+// Reading tarballs: extractAll (src/zippy/tarballs.nim:26-124) without its file-system half, for many images a call.
+// The host classifies the images by length and magic bytes; every gzip member of the call is decoded by ONE sized
+// uncompress plan whose outputs stay in HBM, the plain images are uploaded next to them.  The ustar header walk of
+// tarballs.nim:61-124 -- serial by nature: a header's position is the sum of the sizes before it -- runs in parallel:
+//   zh_tar_next_kernel    every 512-byte block of every image is read as if it were a header: next[b]
+//   zh_tar_double_kernel  the blocks reachable from an image's block 0 ARE its headers: pointer doubling
+//   zh_tar_scan_*         a prefix sum over the marks: every header's ordinal in walk order, the list of headers
+//   zh_tar_parse_kernel   one wave per header: fields, the joined path, the checks, one fixed-size record
+//   zh_tar_reduce_kernel  per tarball: the first header in walk order that failed is the tarball's status
+// The host builds the zh_tar_readers from the records; it parses no header byte itself.
+#include "zh_host.h"
+
+namespace {
+
+// One tarball of the walk.  All tarballs of a call share one index space of 512-byte blocks ("nodes"): this one's
+// are [blk0, blk0 + nblk), nblk = ceil(len / 512), followed by its END node blk0 + nblk, which points to itself.
+struct ZhTarImg {
+  const uint8_t* data;  // device address of the uncompressed image, 8-byte aligned, readable up to len + 16
+  uint64_t len;
+  uint32_t blk0, nblk;
+};
+
+// One header that tarballs.nim:61-124 looks at (48 bytes).  `reported`: an entry of the reader (typeflags 0, \0, 5,
+// 2 of an active header); the other fields mean something only then.  The path is the 256-byte pool slot of the
+// header's ordinal (path_off = 256 * ordinal), or -- a pending long name -- image bytes [path_off, + path_len).
+struct ZhTarRec {
+  uint64_t offset, size, path_off, path_len;
+  int64_t mtime;
+  uint32_t mode;
+  uint8_t typeflag, link_len, reported, path_in_image;
+};
+
+constexpr uint32_t kScanItems = 1024;  // nodes a workgroup of the scan covers
+
+__device__ __forceinline__ uint32_t find_img(const ZhTarImg* __restrict__ imgs, uint32_t n_img, uint32_t node) {
+  uint32_t lo = 0, hi = n_img;  // the last image whose blk0 <= node
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (imgs[mid].blk0 <= node)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// tarballs.nim:5-23 parseTarOctInt over the n bytes that start `shift` bytes into the 16 bytes (lo, hi): the first
+// run of decimal digits, read as octal; a digit 8 or 9 in it is an error (-> false)
+__device__ __forceinline__ bool tar_octal(uint64_t lo, uint64_t hi, uint32_t shift, uint32_t n, uint64_t* out) {
+  uint64_t v = 0;
+  uint32_t state = 0;  // 0 before the run, 1 inside, 2 behind it
+  bool ok = true;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t at = shift + k;
+    const uint32_t c = (uint32_t)((at < 8 ? lo >> (8 * at) : hi >> (8 * (at - 8))) & 0xffu);
+    const bool digit = c >= '0' && c <= '9';
+    if (state == 0 && digit) state = 1;
+    if (state == 1) {
+      if (digit) {
+        ok = ok && c <= '7';
+        v = v * 8 + (c - '0');
+      } else {
+        state = 2;
+      }
+    }
+  }
+  *out = v;
+  return ok;
+}
+
+// the size field (bytes 124-134) of the header at h, read with three aligned 32-bit loads
+__device__ __forceinline__ bool header_size(const uint8_t* __restrict__ h, uint64_t* size) {
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(h + 124);
+  return tar_octal((uint64_t)w[0] | ((uint64_t)w[1] << 32), (uint64_t)w[2], 0, 11, size);
+}
+
+// exclusive prefix sum of v over the 256 threads of the workgroup, *total = the sum
+__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
+  __shared__ uint32_t wave_sum[4];
+  const uint32_t incl = zh_wave_scan(v), wave = threadIdx.x >> 6;
+  __syncthreads();  // (the previous call's reads of wave_sum are over)
+  if (zh_lane() == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) {
+    before += k < wave ? wave_sum[k] : 0u;
+    all += wave_sum[k];
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+}  // namespace
+
+// next[b] for every node b: the node of the header that follows if block b is a header -- END when the size field
+// does not parse, when the entry runs past the image, when b is a trailing partial block, and for END itself.
+// mark[b] = 1 for the first block of every tarball.  Of a block, one 128-byte line in four is touched.
+__global__ __launch_bounds__(256) void zh_tar_next_kernel(const ZhTarImg* __restrict__ imgs, uint32_t n_img,
+                                                          uint32_t n_nodes, uint32_t* __restrict__ jump,
+                                                          uint32_t* __restrict__ mark) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= n_nodes) return;
+  const ZhTarImg g = imgs[find_img(imgs, n_img, b)];
+  const uint32_t end = g.blk0 + g.nblk;
+  uint32_t nx = end;
+  if (b != end) {
+    const uint64_t pos = (uint64_t)(b - g.blk0) * 512;
+    uint64_t size;
+    if (pos + 512 <= g.len && header_size(g.data + pos, &size) && pos + 512 + size <= g.len) {
+      const uint64_t nk = (uint64_t)(b - g.blk0) + 1 + ((size + 511) >> 9);
+      if (nk < g.nblk) nx = g.blk0 + (uint32_t)nk;
+    }
+  }
+  jump[b] = nx;
+  mark[b] = b == g.blk0 && b != end ? 1u : 0u;
+}
+
+// One round of pointer doubling: every marked node marks the node its jump points to, then jump = jump o jump (from
+// jin into jout).  Entering round r, jump is next^(2^r) and every node up to 2^r - 1 steps from a start is marked; a
+// node marked early by a neighbour of the same round only marks other reachable nodes early.  END, the only fixed
+// point, is never marked.  The marks are plain stores of the same value.
+__global__ __launch_bounds__(256) void zh_tar_double_kernel(const uint32_t* __restrict__ jin,
+                                                            uint32_t* __restrict__ jout, uint32_t* mark,
+                                                            uint32_t n_nodes) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= n_nodes) return;
+  const uint32_t t = jin[b], tt = jin[t];
+  if (mark[b] && tt != t) mark[t] = 1u;
+  jout[b] = tt;
+}
+
+// The prefix sum over the marks, in three launches.  sums: marks per workgroup of kScanItems nodes.
+__global__ __launch_bounds__(256) void zh_tar_scan_sums_kernel(const uint32_t* __restrict__ mark, uint32_t n_nodes,
+                                                               uint32_t* __restrict__ sums) {
+  const uint32_t base = blockIdx.x * kScanItems;
+  uint32_t v = 0;
+  for (uint32_t j = 0; j < kScanItems; j += 256) {
+    const uint32_t b = base + j + threadIdx.x;
+    v += b < n_nodes ? mark[b] : 0u;
+  }
+  uint32_t total;
+  (void)block_scan(v, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+// ... one workgroup turns them into the marks before each workgroup's nodes; sums[n_sums] = all marks (the headers)
+__global__ __launch_bounds__(256) void zh_tar_scan_offsets_kernel(uint32_t* sums, uint32_t n_sums) {
+  uint32_t carry = 0;
+  for (uint32_t j = 0; j < n_sums; j += 256) {
+    const uint32_t i = j + threadIdx.x;
+    const uint32_t v = i < n_sums ? sums[i] : 0u;
+    uint32_t total;
+    const uint32_t excl = block_scan(v, &total);
+    if (i < n_sums) sums[i] = carry + excl;
+    carry += total;
+  }
+  if (threadIdx.x == 0) sums[n_sums] = carry;
+}
+// ... ord[b] = marks before node b, in walk order across the whole call; list[ord[b]] = b for every header
+__global__ __launch_bounds__(256) void zh_tar_scan_write_kernel(const uint32_t* __restrict__ mark, uint32_t n_nodes,
+                                                                const uint32_t* __restrict__ sums,
+                                                                uint32_t* __restrict__ ord,
+                                                                uint32_t* __restrict__ list) {
+  const uint32_t base = blockIdx.x * kScanItems;
+  uint32_t carry = sums[blockIdx.x];
+  for (uint32_t j = 0; j < kScanItems; j += 256) {
+    const uint32_t b = base + j + threadIdx.x;
+    const uint32_t v = b < n_nodes ? mark[b] : 0u;
+    uint32_t total;
+    const uint32_t at = carry + block_scan(v, &total);
+    if (b < n_nodes) {
+      ord[b] = at;
+      if (v) list[at] = b;
+    }
+    carry += total;
+  }
+}
+
+namespace {
+
+// bits [a, a + n) of the header as a mask over this lane's eight bytes [8 * lane, + 8)
+__device__ __forceinline__ uint32_t lane_span(uint32_t lane, uint32_t a, uint32_t n) {
+  const uint32_t lo = lane * 8, hi = lo + 8;
+  const uint32_t s = a > lo ? a - lo : 0u, e = a + n < hi ? (a + n > lo ? a + n - lo : 0u) : 8u;
+  return e > s ? ((1u << e) - 1u) & ~((1u << s) - 1u) : 0u;
+}
+// $(slice).cstring: the length of the NUL-terminated field [a, a + n); zm = this lane's zero-byte mask
+__device__ __forceinline__ uint32_t field_len(uint32_t zm, uint32_t lane, uint32_t a, uint32_t n) {
+  const uint32_t m = zm & lane_span(lane, a, n);
+  const uint64_t hit = __ballot(m != 0);
+  const uint32_t src = hit ? (uint32_t)__ffsll((unsigned long long)hit) - 1u : 0u;
+  const uint32_t mm = __shfl(m, (int)src);
+  return hit ? src * 8 + (uint32_t)__ffs(mm) - 1u - a : n;
+}
+
+// internal.nim:294-302 verifyPathIsSafeToExtract on the four bytes x of a path that start at position `at`
+__device__ __forceinline__ bool unsafe_at(uint32_t x, uint64_t at) {
+  if (x == 0x2f2e2e2fu || x == 0x5c2e2e5cu) return true;  // "/../", "\..\"
+  if (at != 0) return false;
+  return (x & 0xffu) == '/' || (x & 0xffffffu) == 0x2f2e2eu || (x & 0xffffffu) == 0x5c2e2eu;  // "/", "../", "..\"
+}
+
+}  // namespace
+
+// One wave per header, in walk order (h = its ordinal in the call, list[h] its node).  The lanes load the header 8
+// bytes each; string fields end at the first zero byte of their range (ballot + shuffle), the octal fields are read
+// from the two lanes that hold them.  The header's own status follows the reference's order: the block is whole
+// (tarballs.nim:62-63), mode / size / mtime parse (:65-67), the contents are there (:77-78), then -- for a header
+// that has a name or a pending long name (:80) -- the path is safe (:87) and the type is known (:89-119).
+// A long name is pending for header i when header i - 1 is an 'L' block of size > 0 that was itself active: that has
+// a name, or -- the look-back along a run of 'L' blocks with empty names -- a pending long name of its own.
+__global__ __launch_bounds__(256) void zh_tar_parse_kernel(const ZhTarImg* __restrict__ imgs, uint32_t n_img,
+                                                           const uint32_t* __restrict__ ord,
+                                                           const uint32_t* __restrict__ list, uint32_t n_hdr,
+                                                           ZhTarRec* __restrict__ recs, uint32_t* __restrict__ pool,
+                                                           int32_t* __restrict__ hstat) {
+  const uint32_t h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = zh_lane();
+  if (h >= n_hdr) return;
+  const uint32_t node = list[h];
+  const ZhTarImg g = imgs[find_img(imgs, n_img, node)];
+  const uint32_t first = ord[g.blk0];  // the ordinal of the tarball's first header
+  const uint64_t pos = (uint64_t)(node - g.blk0) * 512;
+  ZhTarRec rec{};
+  int32_t status = ZH_OK;
+  if (pos + 512 > g.len) {  // a trailing partial block
+    status = ZH_ERR_ARCHIVE_EOF;
+  } else {
+    const uint8_t* __restrict__ hdr = g.data + pos;
+    const uint64_t w = reinterpret_cast<const uint64_t*>(hdr)[lane];
+    uint32_t zm = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) zm |= ((w >> (8 * k)) & 0xffu) == 0 ? 1u << k : 0u;
+    const uint32_t name_len = field_len(zm, lane, 0, 100), link_len = field_len(zm, lane, 157, 100);
+    const uint32_t magic_len = field_len(zm, lane, 257, 6);
+    uint32_t prefix_len = field_len(zm, lane, 345, 155);
+    const bool ustar = magic_len == 5 && ((__shfl(w, 32) >> 8) & 0xffffffffffull) == 0x7261747375ull;
+    if (!ustar) prefix_len = 0;
+    uint64_t mode, size, mtime;
+    const bool ok_mode = tar_octal(__shfl(w, 12), __shfl(w, 13), 4, 7, &mode);
+    const bool ok_size = tar_octal(__shfl(w, 15), __shfl(w, 16), 4, 11, &size);
+    const bool ok_mtime = tar_octal(__shfl(w, 17), __shfl(w, 18), 0, 11, &mtime);
+    const uint32_t typeflag = (uint32_t)(__shfl(w, 19) >> 32) & 0xffu;
+
+    // is a long name pending?  (every lane reads the same bytes: the loop is uniform)
+    bool pending = false;
+    uint64_t long_at = 0, long_len = 0;
+    for (uint32_t i = h; i > first; i--) {
+      const uint64_t p = (uint64_t)(list[i - 1] - g.blk0) * 512;
+      uint64_t psize = 0;
+      if (g.data[p + 156] != 'L' || !header_size(g.data + p, &psize) || psize == 0) break;
+      if (i == h) {
+        long_at = p + 512;
+        long_len = psize;
+      }
+      if (g.data[p] != 0) {
+        pending = true;
+        break;
+      }
+    }
+
+    if (!ok_mode || !ok_size || !ok_mtime) {
+      status = ZH_ERR_TAR_NUMBER;
+    } else if (pos + 512 + size > g.len) {
+      status = ZH_ERR_ARCHIVE_EOF;
+    } else if (name_len || pending) {
+      bool unsafe = false;
+      if (pending) {  // the long name, 512 bytes a step; a lane looks at the 8 positions of its bytes
+        const uint8_t* __restrict__ q = g.data + long_at;
+        for (uint64_t c = 0; c < long_len && !unsafe; c += 512) {
+          const uint64_t o = c + lane * 8;
+          uint64_t lo = o < long_len ? *reinterpret_cast<const uint64_t*>(q + o) : 0ull;
+          uint64_t hi = o + 8 < long_len ? (uint64_t) * reinterpret_cast<const uint32_t*>(q + o + 8) : 0ull;
+          const uint64_t left = o < long_len ? long_len - o : 0;  // bytes of the name from o on; the rest reads as 0
+          if (left < 8) lo &= (1ull << (8 * left)) - 1ull;
+          if (left < 12) hi &= left > 8 ? (1ull << (8 * (left - 8))) - 1ull : 0ull;
+          bool bad = false;
+#pragma unroll
+          for (uint32_t k = 0; k < 8; k++) {
+            const uint32_t x = (uint32_t)(k ? (lo >> (8 * k)) | (hi << (64 - 8 * k)) : lo);
+            bad = bad || (k < left && unsafe_at(x, o + k));
+          }
+          unsafe = __ballot(bad) != 0;
+        }
+        rec.path_off = long_at;
+        rec.path_len = long_len;
+        rec.path_in_image = 1;
+      } else {  // prefix / name with the rules of std/os `/`; a lane makes 4 bytes of the joined path
+        const bool hs = prefix_len && hdr[345 + prefix_len - 1] == '/', ts = hdr[0] == '/';
+        const uint32_t sep = prefix_len && !hs && !ts ? 1u : 0u, skip = hs && ts ? 1u : 0u;
+        const uint32_t total = prefix_len + sep + name_len - skip;
+        auto at = [&](uint32_t j) -> uint32_t {
+          if (j >= total) return 0u;
+          if (j < prefix_len) return hdr[345 + j];
+          j -= prefix_len;
+          if (sep) {
+            if (j == 0) return '/';
+            j--;
+          }
+          return hdr[skip + j];
+        };
+        uint32_t c[7];
+#pragma unroll
+        for (uint32_t k = 0; k < 7; k++) c[k] = at(lane * 4 + k);
+        bool bad = false;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+          bad = bad || (lane * 4 + k < total &&
+                        unsafe_at(c[k] | (c[k + 1] << 8) | (c[k + 2] << 16) | (c[k + 3] << 24), lane * 4 + k));
+        unsafe = __ballot(bad) != 0;
+        pool[(uint64_t)h * 64 + lane] = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+        rec.path_off = (uint64_t)h * 256;
+        rec.path_len = total;
+      }
+      if (unsafe) {
+        status = ZH_ERR_UNSAFE_PATH;
+      } else if (typeflag == '0' || typeflag == 0 || typeflag == '5' || typeflag == '2') {
+        rec.reported = 1;
+        rec.offset = pos + 512;
+        rec.size = size;
+        rec.mtime = (int64_t)mtime;
+        rec.mode = (uint32_t)mode;
+        rec.typeflag = (uint8_t)typeflag;
+        rec.link_len = (uint8_t)link_len;
+      } else if (typeflag == 'g' || typeflag == 'x' || (typeflag >= 'A' && typeflag <= 'Z')) {
+        // a long name ('L'), extended headers and vendor types: nothing to report
+      } else {
+        status = ZH_ERR_TAR_HEADER_TYPE;
+      }
+    }
+  }
+  if (lane == 0) {
+    recs[h] = rec;
+    hstat[h] = status;
+  }
+}
+
+// One workgroup per tarball: its headers are the ordinals [ord[blk0], ord[END]); the first of them whose status is
+// not ZH_OK gives the tarball's status, as the serial loop stops there.
+__global__ __launch_bounds__(256) void zh_tar_reduce_kernel(const ZhTarImg* __restrict__ imgs,
+                                                            const uint32_t* __restrict__ ord,
+                                                            const int32_t* __restrict__ hstat,
+                                                            uint32_t* __restrict__ ranges,
+                                                            int32_t* __restrict__ tstat) {
+  __shared__ uint32_t wave_min[4];
+  const ZhTarImg g = imgs[blockIdx.x];
+  const uint32_t first = ord[g.blk0], end = ord[g.blk0 + g.nblk];
+  uint32_t best = 0xffffffffu;
+  for (uint32_t i = first + threadIdx.x; i < end && best == 0xffffffffu; i += 256)
+    if (hstat[i] != ZH_OK) best = i;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) best = min(best, (uint32_t)__shfl_xor(best, m));
+  if (zh_lane() == 0) wave_min[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    best = min(min(wave_min[0], wave_min[1]), min(wave_min[2], wave_min[3]));
+    tstat[blockIdx.x] = best == 0xffffffffu ? ZH_OK : hstat[best];
+    ranges[2 * blockIdx.x] = first;
+    ranges[2 * blockIdx.x + 1] = end;
+  }
+}
+
+namespace {
+
+struct HostBufs {  // host buffers of the call that no reader owns yet
+  std::vector<void*> p;
+  ~HostBufs() {
+    for (void* q : p) free(q);
+  }
+};
+
+uint32_t gzip_isize(const uint8_t* src, size_t len) {
+  const uint8_t* t = src + len - 4;
+  return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+}
+
+}  // namespace
+
+extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n_tar,
+                                 zh_tar_reader** readers, int32_t* statuses) {
+  if (!ctx || (n_tar && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
+  for (size_t t = 0; t < n_tar; t++) {
+    readers[t] = nullptr;
+    statuses[t] = ZH_OK;
+  }
+  for (size_t t = 0; t < n_tar; t++)
+    if (!images[t] && lens[t]) return ZH_ERR_ARGUMENT;
+  if (!n_tar) return ZH_OK;
+
+  // ---- classify: lengths and magic bytes only (tarballs.nim:43-54, gzip.nim:10-11) ----
+  std::vector<size_t> gz, plain;
+  for (size_t t = 0; t < n_tar; t++) {
+    const uint8_t* s = (const uint8_t*)images[t];
+    if (lens[t] < 2 || (s[0] == 31 && s[1] == 139 && lens[t] < 18))
+      statuses[t] = ZH_ERR_INVALID_BUFFER;
+    else if (s[0] == 31 && s[1] == 139)
+      gz.push_back(t);
+    else
+      plain.push_back(t);
+  }
+  if (gz.empty() && plain.empty()) return ZH_OK;
+  ZH_HIP(ctx, hipSetDevice(ctx->device));
+  Trace tr;
+  int st;
+
+  // ---- one upload: the plain images at 512-byte aligned offsets, the gzip members behind them ----
+  std::vector<const void*> up_src;
+  std::vector<uint64_t> up_off, up_len;
+  uint64_t o = 0;
+  for (size_t t : plain) {
+    up_src.push_back(images[t]);
+    up_off.push_back(o);
+    up_len.push_back(lens[t]);
+    o += (lens[t] + 511) & ~(uint64_t)511;
+  }
+  for (size_t t : gz) {
+    up_src.push_back(images[t]);
+    up_off.push_back(o);
+    up_len.push_back(lens[t]);
+    o += (lens[t] + 255) & ~(uint64_t)255;
+  }
+  DevBuf d_in, d_dec, d_redo;
+  if (dev_alloc(ctx, d_in, o + 512) != hipSuccess) return ZH_ERR_NOMEM;
+  if ((st = zhh_upload_slices(ctx, up_src.data(), up_off, up_len, o, d_in.p))) return st;
+  tr.mark(ctx, "tar open: upload");
+
+  // the tarballs of the walk: where their bytes are on the device, who owns them on the host
+  struct Walk {
+    size_t t;
+    const uint8_t* d_data;
+    uint64_t len;
+    int host = -1;  // index into `own` of the host copy a .tar.gz's reader will own
+    int slot = -1;  // ... or the decode slot it is still to be fetched from
+  };
+  std::vector<Walk> walk;
+  for (size_t k = 0; k < plain.size(); k++) walk.push_back({plain[k], d_in.p + up_off[k], lens[plain[k]]});
+  HostBufs own;
+
+  // ---- one decode: every gzip member through one sized plan, ISIZE as the slot (gzip.nim:72-76 trustSize) ----
+  const size_t n_gz = gz.size();
+  std::vector<uint64_t> doff(n_gz), dcap(n_gz), olen(n_gz);
+  if (n_gz) {
+    std::vector<uint64_t> soff(up_off.begin() + plain.size(), up_off.end()),
+        slen(up_len.begin() + plain.size(), up_len.end());
+    uint64_t total = 0;
+    for (size_t k = 0; k < n_gz; k++) {
+      const size_t t = gz[k];
+      dcap[k] = std::min<uint64_t>(gzip_isize((const uint8_t*)images[t], lens[t]), (uint64_t)lens[t] * 1032 + 64);
+      doff[k] = total;
+      total += (dcap[k] + 511) & ~(uint64_t)511;
+    }
+    if (dev_alloc(ctx, d_dec, total + 512) != hipSuccess) return ZH_ERR_NOMEM;
+    PlanGuard pg;
+    std::vector<int32_t> ost(n_gz);
+    if ((st = zh_plan_uncompress(ctx, n_gz, soff.data(), slen.data(), doff.data(), dcap.data(), ZH_DF_GZIP, &pg.p)) ||
+        (st = zh_plan_run(pg.p, d_in.p, d_dec.p)) || (st = zh_plan_results(pg.p, olen.data(), ost.data())))
+      return st;
+    tr.mark(ctx, "tar open: decode");
+    // A member that outgrew its ISIZE (4 GiB and more, or damaged) takes zh_tar_open's own route, the host call that
+    // retries at the expansion bound: its status is that call's, its image comes back to the device for the walk.
+    std::vector<size_t> redo;
+    for (size_t k = 0; k < n_gz; k++) {
+      if (ost[k] == ZH_ERR_DST_TOO_SMALL)
+        redo.push_back(k);
+      else if (ost[k] != ZH_OK)
+        statuses[gz[k]] = ost[k];
+      else
+        walk.push_back({gz[k], d_dec.p + doff[k], olen[k], -1, (int)k});
+    }
+    if (!redo.empty()) {
+      const size_t nr = redo.size();
+      std::vector<const void*> rsrc(nr);
+      std::vector<size_t> rlen(nr), rout(nr);
+      std::vector<uint64_t> rhint(nr);
+      std::vector<void*> rdst(nr, nullptr);
+      std::vector<int32_t> rst(nr);
+      for (size_t j = 0; j < nr; j++) {
+        rsrc[j] = images[gz[redo[j]]];
+        rlen[j] = lens[gz[redo[j]]];
+        rhint[j] = gzip_isize((const uint8_t*)rsrc[j], rlen[j]);
+      }
+      st = zh_uncompress_batch_sized(ctx, rsrc.data(), rlen.data(), nr, ZH_DF_GZIP, rhint.data(), rdst.data(),
+                                     rout.data(), rst.data(), nullptr);
+      own.p = rdst;
+      if (st) return st;
+      std::vector<const void*> hsrc;
+      std::vector<size_t> hlen, hwalk;
+      for (size_t j = 0; j < nr; j++) {
+        if (rst[j] != ZH_OK) {
+          statuses[gz[redo[j]]] = rst[j];
+          continue;
+        }
+        hwalk.push_back(walk.size());
+        walk.push_back({gz[redo[j]], nullptr, rout[j], (int)j, -1});
+        hsrc.push_back(rdst[j]);
+        hlen.push_back(rout[j]);
+      }
+      if (!hsrc.empty()) {
+        std::vector<uint64_t> hoff, hlen64;
+        if ((st = zhh_upload(ctx, hsrc.data(), hlen.data(), hsrc.size(), d_redo, hoff, hlen64))) return st;
+        for (size_t j = 0; j < hwalk.size(); j++) walk[hwalk[j]].d_data = d_redo.p + hoff[j];
+      }
+    }
+  }
+  const size_t n_walk = walk.size();
+  if (!n_walk) return ZH_OK;
+
+  // ---- the walk ----
+  std::vector<ZhTarImg> imgs(n_walk);
+  uint64_t n_nodes = 0, max_blk = 0;
+  for (size_t k = 0; k < n_walk; k++) {
+    const uint64_t nblk = (walk[k].len + 511) >> 9;
+    if (n_nodes + nblk + 1 >= 0xffffffffull) return ZH_ERR_ARGUMENT;  // (2 TiB of images in one call)
+    imgs[k] = ZhTarImg{walk[k].d_data, walk[k].len, (uint32_t)n_nodes, (uint32_t)nblk};
+    n_nodes += nblk + 1;
+    max_blk = std::max(max_blk, nblk);
+  }
+  // after `rounds` rounds every node up to 2^rounds - 1 steps from a start is marked; a chain has at most max_blk
+  uint32_t rounds = 0;
+  while ((1ull << rounds) < max_blk + 1) rounds++;
+  const uint32_t N = (uint32_t)n_nodes, n_sums = (N + kScanItems - 1) / kScanItems;
+  DevBuf d_imgs, d_scr;
+  std::vector<uint64_t> ioff;
+  if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_walk * sizeof(ZhTarImg)}}, d_imgs, ioff))) return st;
+  // scratch: two jump arrays, the marks, the ordinals -- 4 bytes a node each -- and the scan's workgroup sums
+  Arena ar;
+  const size_t o_j0 = ar.reserve((size_t)N * 4), o_j1 = ar.reserve((size_t)N * 4), o_mark = ar.reserve((size_t)N * 4),
+               o_ord = ar.reserve((size_t)N * 4), o_sums = ar.reserve(((size_t)n_sums + 1) * 4);
+  if (dev_alloc(ctx, d_scr, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
+  uint32_t* const j0 = carve<uint32_t>(d_scr.p, o_j0);
+  uint32_t* const j1 = carve<uint32_t>(d_scr.p, o_j1);
+  uint32_t* const mark = carve<uint32_t>(d_scr.p, o_mark);
+  uint32_t* const ord = carve<uint32_t>(d_scr.p, o_ord);
+  uint32_t* const sums = carve<uint32_t>(d_scr.p, o_sums);
+  const ZhTarImg* const dimgs = reinterpret_cast<const ZhTarImg*>(d_imgs.p);
+  const dim3 node_grid((N + 255) / 256), wg(256);
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(zh_tar_next_kernel, node_grid, wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark);
+  uint32_t *jin = j0, *jout = j1;
+  for (uint32_t r = 0; r < rounds; r++) {
+    hipLaunchKernelGGL(zh_tar_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
+    std::swap(jin, jout);
+  }
+  // (the jump arrays are dead from here on: the list of headers takes the place of the first)
+  uint32_t* const list = j0;
+  hipLaunchKernelGGL(zh_tar_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
+  hipLaunchKernelGGL(zh_tar_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
+  hipLaunchKernelGGL(zh_tar_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
+                     (const uint32_t*)sums, ord, list);
+  ZH_HIP(ctx, hipGetLastError());
+  uint32_t n_hdr = 0;  // the records are sized by the headers there are, not by the blocks
+  ZH_HIP(ctx, hipMemcpyAsync(&n_hdr, sums + n_sums, 4, hipMemcpyDeviceToHost, s));
+  ZH_HIP(ctx, hipStreamSynchronize(s));
+  tr.mark(ctx, "tar open: reach + scan");
+
+  // results: records, path pool, the tarballs' header ranges and statuses come back; the headers' statuses stay
+  Arena out;
+  const size_t o_recs = out.reserve((size_t)n_hdr * sizeof(ZhTarRec)), o_pool = out.reserve((size_t)n_hdr * 256),
+               o_ranges = out.reserve(n_walk * 8), o_tstat = out.reserve(n_walk * 4);
+  const size_t out_bytes = out.size;
+  const size_t o_hstat = out.reserve((size_t)n_hdr * 4);
+  DevBuf d_out;
+  if (dev_alloc(ctx, d_out, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  if (n_hdr)
+    hipLaunchKernelGGL(zh_tar_parse_kernel, dim3((n_hdr + 3) / 4), wg, 0, s, dimgs, (uint32_t)n_walk,
+                       (const uint32_t*)ord, (const uint32_t*)list, n_hdr, carve<ZhTarRec>(d_out.p, o_recs),
+                       carve<uint32_t>(d_out.p, o_pool), carve<int32_t>(d_out.p, o_hstat));
+  hipLaunchKernelGGL(zh_tar_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s, dimgs, (const uint32_t*)ord,
+                     (const int32_t*)carve<int32_t>(d_out.p, o_hstat), carve<uint32_t>(d_out.p, o_ranges),
+                     carve<int32_t>(d_out.p, o_tstat));
+  ZH_HIP(ctx, hipGetLastError());
+  void* h_out = nullptr;
+  {
+    size_t got = 0;
+    int32_t dst_st = ZH_OK;
+    if ((st = zhh_download(ctx, d_out.p, 1, {0}, {out_bytes}, {1}, &h_out, &got, &dst_st))) {
+      free(h_out);
+      return st;
+    }
+    own.p.push_back(h_out);
+    if (dst_st) return dst_st;
+  }
+  const uint8_t* const ho = (const uint8_t*)h_out;
+  const ZhTarRec* const recs = reinterpret_cast<const ZhTarRec*>(ho + o_recs);
+  const uint32_t* const ranges = reinterpret_cast<const uint32_t*>(ho + o_ranges);
+  const int32_t* const tstat = reinterpret_cast<const int32_t*>(ho + o_tstat);
+  tr.mark(ctx, "tar open: parse + reduce");
+
+  // ---- the decoded images of the tarballs that opened ----
+  {
+    std::vector<char> take(n_gz, 0);
+    for (size_t k = 0; k < n_walk; k++)
+      if (walk[k].slot >= 0 && tstat[k] == ZH_OK) take[(size_t)walk[k].slot] = 1;
+    std::vector<void*> idst(n_gz, nullptr);
+    std::vector<size_t> ilen(n_gz, 0);
+    std::vector<int32_t> ist(n_gz, ZH_OK);
+    st = n_gz ? zhh_download(ctx, d_dec.p, n_gz, doff, olen, take, idst.data(), ilen.data(), ist.data()) : ZH_OK;
+    const size_t base = own.p.size();
+    own.p.insert(own.p.end(), idst.begin(), idst.end());
+    if (st) return st;
+    for (size_t k = 0; k < n_walk; k++)
+      if (walk[k].slot >= 0 && tstat[k] == ZH_OK) {
+        if (ist[(size_t)walk[k].slot]) return ist[(size_t)walk[k].slot];  // (allocation)
+        walk[k].host = (int)(base + (size_t)walk[k].slot);
+      }
+  }
+  tr.mark(ctx, "tar open: download");
+
+  // ---- the readers, from the records ----
+  std::vector<zh_tar_reader*> made(n_walk, nullptr);
+  bool nomem = false;
+  for (size_t k = 0; k < n_walk && !nomem; k++) {
+    if (tstat[k] != ZH_OK) continue;
+    const bool borrowed = walk[k].host < 0;
+    const uint8_t* data = borrowed ? (const uint8_t*)images[walk[k].t] : (const uint8_t*)own.p[(size_t)walk[k].host];
+    zh_tar_reader* r = zh_tar_reader_new(borrowed ? nullptr : own.p[(size_t)walk[k].host], data, (size_t)walk[k].len);
+    if (!r) {
+      nomem = true;
+      break;
+    }
+    if (!borrowed) own.p[(size_t)walk[k].host] = nullptr;  // the reader's from here on
+    made[k] = r;
+    for (uint32_t i = ranges[2 * k]; i < ranges[2 * k + 1] && !nomem; i++) {
+      const ZhTarRec& e = recs[i];
+      if (!e.reported) continue;
+      const char* path = (const char*)(e.path_in_image ? data : ho + o_pool) + e.path_off;
+      nomem = zh_tar_reader_add(r, path, (size_t)e.path_len, (const char*)data + e.offset - 512 + 157, e.link_len,
+                                (char)e.typeflag, e.mode, e.mtime, e.offset, e.size) != ZH_OK;
+    }
+  }
+  if (nomem) {
+    for (zh_tar_reader* r : made) zh_tar_close(r);
+    return ZH_ERR_NOMEM;
+  }
+  for (size_t k = 0; k < n_walk; k++) {
+    readers[walk[k].t] = made[k];
+    statuses[walk[k].t] = tstat[k];
+  }
+  return ZH_OK;
+}

@@ -273,6 +273,58 @@ proc hipOpenTarballs*(images: openArray[string]): seq[seq[HipTarEntry]] {.raises
     for r in readers:
       if r != nil: zh_tar_close(r)
 
+# ---- reading zip archives in batches (src/zippy/ziparchives.nim openZipArchive + extractAll) ----
+# (ZhZipEntry, zh_zip_close, zh_zip_num_entries and zh_zip_entry_at are the archive layer's, above)
+type
+  HipZipEntry* = object
+    path*, contents*: string
+    isDirectory*: bool
+    unixMode*: uint32
+
+proc zh_zip_open_all_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, nZip: csize_t,
+                           readers: ptr pointer, statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_zip_entry_data(reader: pointer, i: csize_t, data: ptr pointer, len: ptr csize_t,
+                       status: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipOpenZipArchives*(images: openArray[string]): seq[seq[HipZipEntry]] {.raises: [ZippyError].} =
+  ## openZipArchive (ziparchives.nim:183-372) and the extraction loop of extractAll (:417-429) for many archives in
+  ## one call: the directories walked, every entry decoded and its CRC-32 verified on the device; raises on the first
+  ## archive whose status is not zero, as the reference would on that file.  The caller keeps createDir / writeFile /
+  ## permissions / mtimes (:421-453).
+  let n = images.len
+  if n == 0: return
+  var
+    ptrs = newSeq[pointer](n)
+    lens = newSeq[csize_t](n)
+    readers = newSeq[pointer](n)
+    sts = newSeq[int32](n)
+  for i, s in images:
+    ptrs[i] = if s.len > 0: s[0].unsafeAddr else: nil
+    lens[i] = s.len.csize_t
+  let rc = zh_zip_open_all_batch(engine(), ptrs[0].addr, lens[0].addr, n.csize_t, readers[0].addr, sts[0].addr)
+  try:
+    if rc != 0: raise newException(ZippyError, $zh_strerror(rc))
+    for st in sts:
+      if st != 0: raise newException(ZippyError, $zh_strerror(st.cint))
+    result = newSeq[seq[HipZipEntry]](n)
+    for t in 0 ..< n:
+      for i in 0 ..< zh_zip_num_entries(readers[t]).int:
+        var e: ZhZipEntry
+        var data: pointer
+        var len: csize_t
+        var st: int32
+        discard zh_zip_entry_at(readers[t], i.csize_t, e.addr)
+        discard zh_zip_entry_data(readers[t], i.csize_t, data.addr, len.addr, st.addr)
+        var item = HipZipEntry(isDirectory: e.isDirectory != 0, unixMode: e.unixMode)
+        item.path = newString(e.pathLen.int)
+        if e.pathLen > 0: copyMem(item.path[0].addr, e.path, e.pathLen.int)
+        item.contents = newString(len.int)
+        if len > 0: copyMem(item.contents[0].addr, data, len.int)
+        result[t].add item
+  finally:
+    for r in readers:
+      if r != nil: zh_zip_close(r)
+
 # ---- writing zip archives (src/zippy/ziparchives_v1.nim) ----
 import std/times
 

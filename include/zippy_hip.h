@@ -378,6 +378,37 @@ int zh_zip_create(zh_ctx *ctx, const char *const *paths, const size_t *path_lens
                   const void *const *contents, const size_t *content_lens, size_t n,
                   uint16_t dos_time, uint16_t dos_date, void **archive, size_t *archive_len);
 
+/* openZipArchive + the extraction loop of extractAll (ziparchives.nim:183-372, :374-453 without the file system) for
+ * n_zip images per call.  readers[t] is an ordinary reader -- zh_zip_num_entries / zh_zip_entry_at / zh_zip_find /
+ * zh_zip_extract_batch / zh_zip_close --, NULL when archive t did not open; the image stays borrowed until close, the
+ * extracted bytes are the reader's.  statuses[t] is the first of:
+ *  1. what zh_zip_open(images[t], lens[t], ..) returns for that image alone (the reader is NULL then);
+ *  2. ZH_ERR_UNSAFE_PATH if any record's path is absolute, starts with ../ or ..\ or contains /../ or \..\
+ *     (verifyPathIsSafeToExtract; extractAll checks every path before it extracts anything): the reader is returned,
+ *     nothing was extracted, and zh_zip_entry_data reports ZH_ERR_UNSAFE_PATH for every file record;
+ *  3. the status of the first FILE record, in directory order, whose extraction failed: the reader and every other
+ *     entry's data are returned.
+ * The return value is a call-level error only: NULL arrays, an image that is NULL with a non-zero length, a missing
+ * ctx, allocation, device; more than 2^32 - 2 walk nodes (directory bytes) or records in one call: ZH_ERR_ARGUMENT
+ * before anything is launched.  A bad archive never changes another archive's reader, statuses or bytes; n_zip == 0
+ * launches nothing.
+ * The host only finds each directory (the end records); the images are uploaded once, the directory walk (pointer
+ * doubling over the directory's bytes), every check of openZipArchive's loop body and of extractFile's local header,
+ * the copies of stored entries and every CRC-32 verdict run on the device, and ONE uncompress plan decodes every
+ * deflated entry of the call from its place in the uploaded image (csrc/zh_zip_open_batch.hip). */
+int zh_zip_open_all_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n_zip,
+                          zh_zip_reader **readers, int32_t *statuses);
+/* Contents of a reader made by the call above: all extracted files of the archive in one block owned by the reader,
+ * every entry 8-byte aligned, in directory order (NULL / 0 for a zh_zip_open reader, and when nothing was extracted). */
+const void *zh_zip_data(const zh_zip_reader *reader, size_t *len);
+/* Entry i of such a reader: *status is, for a file record, exactly what zh_zip_extract_batch reports for that index
+ * (ZH_ERR_ARCHIVE_EOF, ZH_ERR_ZIP_FILE_HEADER, ZH_ERR_ZIP_METHOD, ZH_ERR_ZIP_CRC or a decoder status) and data / len
+ * byte-identical to its output (NULL / 0 unless ZH_OK); for a directory record ZH_OK with length 0 (extractAll only
+ * calls createDir for them: their local headers are not read).  The data lie inside zh_zip_data()'s block, except for
+ * an entry whose directory understated its size: that one was decoded again on its own and has a buffer of its own
+ * (the reader's as well).  A reader made by zh_zip_open, a NULL pointer or an index out of range: ZH_ERR_ARGUMENT. */
+int zh_zip_entry_data(const zh_zip_reader *reader, size_t i, const void **data, size_t *len, int32_t *status);
+
 /* ------------------------------------------------------------------ *
  * Tarballs: extractAll of src/zippy/tarballs.nim *
  * without its file-system half.  A .tar.gz is ONE foreign gzip member *

@@ -111,6 +111,11 @@ _SIGS = {
     "zh_zip_extract_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t,
                                         _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
                                         _c.POINTER(_c.c_int32)]),
+    "zh_zip_open_all_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                         _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int32)]),
+    "zh_zip_data": (_c.c_void_p, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "zh_zip_entry_data": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                     _c.POINTER(_c.c_int32)]),
     "zh_zip_create": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_char_p), _c.POINTER(_c.c_size_t),
                                  _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                  _c.c_uint16, _c.c_uint16, _c.POINTER(_c.c_void_p),
@@ -241,11 +246,15 @@ class ZipEntry(_c.Structure):
 class ZipReader:
     """zh_zip_reader over a bytes image: the ZipArchiveReader of ziparchives.nim:27-29."""
 
-    def __init__(self, engine, image):
+    def __init__(self, engine, image, handle=None):
+        """handle: a reader zh_zip_open_all_batch made of `image` (Engine.open_zips); None: zh_zip_open"""
         self.engine = engine
         self._image = bytes(image)  # borrowed by the library until close
         h = _c.c_void_p()
-        engine._check(engine.lib.zh_zip_open(self._image, len(self._image), _c.byref(h)))
+        if handle is None:
+            engine._check(engine.lib.zh_zip_open(self._image, len(self._image), _c.byref(h)))
+        else:
+            h = _c.c_void_p(handle)
         self._h = h
         self.entries = []
         for i in range(engine.lib.zh_zip_num_entries(h)):
@@ -259,6 +268,29 @@ class ZipReader:
 
     def walk_files(self):
         return [e["path"] for e in self.entries if not e["is_directory"]]
+
+    @property
+    def data(self):
+        """zh_zip_data: the block of extracted files of a reader made by Engine.open_zips (b"" otherwise)"""
+        n = _c.c_size_t()
+        base = self.engine.lib.zh_zip_data(self._h, _c.byref(n))
+        return _c.string_at(base, n.value) if base and n.value else b""
+
+    def _entry_data(self, i):
+        data, n, st = _c.c_void_p(), _c.c_size_t(), _c.c_int32()
+        self.engine._check(self.engine.lib.zh_zip_entry_data(self._h, i, _c.byref(data), _c.byref(n), _c.byref(st)))
+        return data.value, n.value, st.value
+
+    def entry_status(self, i):
+        """zh_zip_entry_data's status of record i (a reader made by Engine.open_zips)"""
+        return self._entry_data(i)[2]
+
+    def contents(self, i):
+        """the extracted bytes of record i, None unless its status is 0"""
+        data, n, st = self._entry_data(i)
+        if st:
+            return None
+        return _c.string_at(data, n) if n else b""
 
     def find(self, path):
         raw = path.encode("utf-8", "surrogateescape")
@@ -593,6 +625,17 @@ class Engine:
     # ---- ZIP archives (ziparchives.nim) ----
     def open_zip(self, image):
         return ZipReader(self, image)
+
+    def open_zips(self, images):
+        """zh_zip_open_all_batch: many archives opened and extracted in one call -> (readers, statuses); readers[t]
+        is a ZipReader with .data / .entry_status(i) / .contents(i), or None where the archive did not open."""
+        images = [bytes(b) for b in images]
+        n = len(images)
+        srcs = (_c.c_void_p * n)(*[_c.cast(_c.c_char_p(b), _c.c_void_p) if b else None for b in images])
+        lens = (_c.c_size_t * n)(*[len(b) for b in images])
+        handles, sts = (_c.c_void_p * n)(), (_c.c_int32 * n)()
+        self._check(self.lib.zh_zip_open_all_batch(self._h, srcs, lens, n, handles, sts))
+        return [ZipReader(self, b, h) if h else None for b, h in zip(images, handles)], list(sts)
 
     def create_zip(self, entries, dos_time=0, dos_date=0):
         """entries: ordered (path, contents) pairs -> archive bytes (createZipArchive)."""

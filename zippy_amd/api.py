@@ -63,6 +63,15 @@ def openZipArchive(image):
     return engine().open_zip(image)
 
 
+def openZipArchives(images):
+    """openZipArchive + the extraction of extractAll for many archives in one call (zh_zip_open_all_batch): every
+    directory walked, every entry decoded and verified on the device -> a list of readers, in order, with
+    .entries, .contents(i), .entry_status(i).  Raises ZippyError on the first archive whose status is not zero."""
+    eng = engine()
+    readers, sts = eng.open_zips(images)
+    return eng._raise_first(readers, sts)
+
+
 def createZipArchive(entries, dos_time=0, dos_date=0):
     """ziparchives.nim:625-634 createZipArchive(OrderedTable): entries = ordered mapping / pairs."""
     return engine().create_zip(entries, dos_time, dos_date)

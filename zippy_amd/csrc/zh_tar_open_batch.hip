@@ -3,12 +3,13 @@
 // uncompress plan whose outputs stay in HBM, the plain images are uploaded next to them.  The ustar header walk of
 // tarballs.nim:61-124 -- serial by nature: a header's position is the sum of the sizes before it -- runs in parallel:
 //   zh_tar_next_kernel    every 512-byte block of every image is read as if it were a header: next[b]
-//   zh_tar_double_kernel  the blocks reachable from an image's block 0 ARE its headers: pointer doubling
-//   zh_tar_scan_*         a prefix sum over the marks: every header's ordinal in walk order, the list of headers
+//   zh_walk_double_kernel the blocks reachable from an image's block 0 ARE its headers: pointer doubling (zh_walk.h)
+//   zh_walk_scan_*        a prefix sum over the marks: every header's ordinal in walk order, the list of headers
 //   zh_tar_parse_kernel   one wave per header: fields, the joined path, the checks, one fixed-size record
 //   zh_tar_reduce_kernel  per tarball: the first header in walk order that failed is the tarball's status
 // The host builds the zh_tar_readers from the records; it parses no header byte itself.
 #include "zh_host.h"
+#include "zh_walk.h"
 
 namespace {
 
@@ -29,8 +30,6 @@ struct ZhTarRec {
   uint32_t mode;
   uint8_t typeflag, link_len, reported, path_in_image;
 };
-
-constexpr uint32_t kScanItems = 1024;  // nodes a workgroup of the scan covers
 
 __device__ __forceinline__ uint32_t find_img(const ZhTarImg* __restrict__ imgs, uint32_t n_img, uint32_t node) {
   uint32_t lo = 0, hi = n_img;  // the last image whose blk0 <= node
@@ -74,23 +73,6 @@ __device__ __forceinline__ bool header_size(const uint8_t* __restrict__ h, uint6
   return tar_octal((uint64_t)w[0] | ((uint64_t)w[1] << 32), (uint64_t)w[2], 0, 11, size);
 }
 
-// exclusive prefix sum of v over the 256 threads of the workgroup, *total = the sum
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wave_sum[4];
-  const uint32_t incl = zh_wave_scan(v), wave = threadIdx.x >> 6;
-  __syncthreads();  // (the previous call's reads of wave_sum are over)
-  if (zh_lane() == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < 4; k++) {
-    before += k < wave ? wave_sum[k] : 0u;
-    all += wave_sum[k];
-  }
-  *total = all;
-  return before + incl - v;
-}
-
 }  // namespace
 
 // next[b] for every node b: the node of the header that follows if block b is a header -- END when the size field
@@ -114,66 +96,6 @@ __global__ __launch_bounds__(256) void zh_tar_next_kernel(const ZhTarImg* __rest
   }
   jump[b] = nx;
   mark[b] = b == g.blk0 && b != end ? 1u : 0u;
-}
-
-// One round of pointer doubling: every marked node marks the node its jump points to, then jump = jump o jump (from
-// jin into jout).  Entering round r, jump is next^(2^r) and every node up to 2^r - 1 steps from a start is marked; a
-// node marked early by a neighbour of the same round only marks other reachable nodes early.  END, the only fixed
-// point, is never marked.  The marks are plain stores of the same value.
-__global__ __launch_bounds__(256) void zh_tar_double_kernel(const uint32_t* __restrict__ jin,
-                                                            uint32_t* __restrict__ jout, uint32_t* mark,
-                                                            uint32_t n_nodes) {
-  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= n_nodes) return;
-  const uint32_t t = jin[b], tt = jin[t];
-  if (mark[b] && tt != t) mark[t] = 1u;
-  jout[b] = tt;
-}
-
-// The prefix sum over the marks, in three launches.  sums: marks per workgroup of kScanItems nodes.
-__global__ __launch_bounds__(256) void zh_tar_scan_sums_kernel(const uint32_t* __restrict__ mark, uint32_t n_nodes,
-                                                               uint32_t* __restrict__ sums) {
-  const uint32_t base = blockIdx.x * kScanItems;
-  uint32_t v = 0;
-  for (uint32_t j = 0; j < kScanItems; j += 256) {
-    const uint32_t b = base + j + threadIdx.x;
-    v += b < n_nodes ? mark[b] : 0u;
-  }
-  uint32_t total;
-  (void)block_scan(v, &total);
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-// ... one workgroup turns them into the marks before each workgroup's nodes; sums[n_sums] = all marks (the headers)
-__global__ __launch_bounds__(256) void zh_tar_scan_offsets_kernel(uint32_t* sums, uint32_t n_sums) {
-  uint32_t carry = 0;
-  for (uint32_t j = 0; j < n_sums; j += 256) {
-    const uint32_t i = j + threadIdx.x;
-    const uint32_t v = i < n_sums ? sums[i] : 0u;
-    uint32_t total;
-    const uint32_t excl = block_scan(v, &total);
-    if (i < n_sums) sums[i] = carry + excl;
-    carry += total;
-  }
-  if (threadIdx.x == 0) sums[n_sums] = carry;
-}
-// ... ord[b] = marks before node b, in walk order across the whole call; list[ord[b]] = b for every header
-__global__ __launch_bounds__(256) void zh_tar_scan_write_kernel(const uint32_t* __restrict__ mark, uint32_t n_nodes,
-                                                                const uint32_t* __restrict__ sums,
-                                                                uint32_t* __restrict__ ord,
-                                                                uint32_t* __restrict__ list) {
-  const uint32_t base = blockIdx.x * kScanItems;
-  uint32_t carry = sums[blockIdx.x];
-  for (uint32_t j = 0; j < kScanItems; j += 256) {
-    const uint32_t b = base + j + threadIdx.x;
-    const uint32_t v = b < n_nodes ? mark[b] : 0u;
-    uint32_t total;
-    const uint32_t at = carry + block_scan(v, &total);
-    if (b < n_nodes) {
-      ord[b] = at;
-      if (v) list[at] = b;
-    }
-    carry += total;
-  }
 }
 
 namespace {
@@ -537,14 +459,14 @@ extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const s
   hipLaunchKernelGGL(zh_tar_next_kernel, node_grid, wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark);
   uint32_t *jin = j0, *jout = j1;
   for (uint32_t r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(zh_tar_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
+    hipLaunchKernelGGL(zh_walk_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
     std::swap(jin, jout);
   }
   // (the jump arrays are dead from here on: the list of headers takes the place of the first)
   uint32_t* const list = j0;
-  hipLaunchKernelGGL(zh_tar_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
-  hipLaunchKernelGGL(zh_tar_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
-  hipLaunchKernelGGL(zh_tar_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
+  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
+  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
+  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
                      (const uint32_t*)sums, ord, list);
   ZH_HIP(ctx, hipGetLastError());
   uint32_t n_hdr = 0;  // the records are sized by the headers there are, not by the blocks

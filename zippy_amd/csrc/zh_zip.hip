@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/zippy_hip.h"
+#include "zh_zip_reader.h"
 
 namespace {
 
@@ -96,8 +97,34 @@ int64_t validate_utf8(const std::string& s) {
 
 std::string utf8ify(const std::string& name) {  // ziparchives.nim:108-160
   if (validate_utf8(name) == -1) return name;
+  return zh_zip_from_cp437(name.data(), name.size());
+}
+
+bool ends_with_slash(const std::string& s) { return !s.empty() && s.back() == '/'; }
+
+}  // namespace
+
+struct zh_zip_reader {
+  Image img;
+  std::vector<Record> records;  // central directory order (an OrderedTable in the reference)
+  // a reader made by zh_zip_open_all_batch: every file record's extracted bytes, in one block of the reader's
+  bool extracted = false;
+  void* block = nullptr;
+  size_t block_len = 0;
+  std::vector<const void*> e_data;
+  std::vector<size_t> e_len;
+  std::vector<int32_t> e_status;
+  std::vector<void*> redone;  // entries decoded on their own (a directory that understates a size)
+  ~zh_zip_reader() {
+    free(block);
+    for (void* p : redone) free(p);
+  }
+};
+
+std::string zh_zip_from_cp437(const char* name, size_t len) {
   std::string out;
-  for (unsigned char c : name) {
+  for (size_t i = 0; i < len; i++) {
+    const unsigned char c = (unsigned char)name[i];
     const uint32_t cp = c > 0x7f ? kCp437High[c - 0x80] : c;
     if (cp < 0x80) {
       out.push_back((char)cp);
@@ -113,19 +140,61 @@ std::string utf8ify(const std::string& name) {  // ziparchives.nim:108-160
   return out;
 }
 
-bool ends_with_slash(const std::string& s) { return !s.empty() && s.back() == '/'; }
+zh_zip_reader* zh_zip_reader_new(const void* image, size_t len) {
+  zh_zip_reader* r = new zh_zip_reader;
+  r->img = Image{(const uint8_t*)image, (int64_t)len};
+  return r;
+}
+void zh_zip_reader_add(zh_zip_reader* r, std::string path, bool directory, int64_t header_offset, uint32_t crc,
+                       int64_t compressed_size, int64_t uncompressed_size, uint32_t unix_mode) {
+  Record rec;
+  rec.path = std::move(path);
+  rec.directory = directory;
+  rec.header_offset = header_offset;
+  rec.crc = crc;
+  rec.compressed_size = compressed_size;
+  rec.uncompressed_size = uncompressed_size;
+  rec.unix_mode = unix_mode;
+  r->records.push_back(std::move(rec));
+}
+void zh_zip_reader_set_data(zh_zip_reader* r, void* block, size_t block_len, const uint64_t* off, const uint64_t* len,
+                            const int32_t* status, void* const* redone) {
+  const size_t n = r->records.size();
+  r->extracted = true;
+  r->block = block;
+  r->block_len = block ? block_len : 0;
+  r->e_data.assign(n, nullptr);
+  r->e_len.assign(n, 0);
+  r->e_status.assign(status, status + n);
+  for (size_t i = 0; i < n; i++) {
+    if (status[i] != ZH_OK) continue;
+    r->e_len[i] = (size_t)len[i];
+    if (redone[i]) {
+      r->e_data[i] = redone[i];
+      r->redone.push_back(redone[i]);
+    } else {
+      r->e_data[i] = block ? (const uint8_t*)block + off[i] : nullptr;
+    }
+  }
+}
 
-}  // namespace
+extern "C" const void* zh_zip_data(const zh_zip_reader* r, size_t* len) {
+  if (len) *len = r && r->extracted ? r->block_len : 0;
+  return r && r->extracted ? r->block : nullptr;
+}
+extern "C" int zh_zip_entry_data(const zh_zip_reader* r, size_t i, const void** data, size_t* len, int32_t* status) {
+  if (data) *data = nullptr;
+  if (len) *len = 0;
+  if (status) *status = ZH_ERR_ARGUMENT;
+  if (!r || !data || !len || !status || i >= r->records.size() || !r->extracted) return ZH_ERR_ARGUMENT;
+  *data = r->e_data[i];
+  *len = r->e_len[i];
+  *status = r->e_status[i];
+  return ZH_OK;
+}
 
-struct zh_zip_reader {
-  Image img;
-  std::vector<Record> records;  // central directory order (an OrderedTable in the reference)
-};
-
-// openZipArchive, ziparchives.nim:183-372
-extern "C" int zh_zip_open(const void* archive, size_t len, zh_zip_reader** out) {
-  if (!out || (len && !archive)) return ZH_ERR_ARGUMENT;
-  *out = nullptr;
+// openZipArchive up to its record loop, ziparchives.nim:162-268
+int zh_zip_locate(const void* archive, size_t len, ZhZipDirectory* dir) {
   const Image im{(const uint8_t*)archive, (int64_t)len};
 
   // :162-173 the end-of-central-directory record, searched backwards from the shortest possible
@@ -175,6 +244,18 @@ extern "C" int zh_zip_open(const void* archive, size_t len, zh_zip_reader** out)
     }
     if (at >= 0) socd = at;
   }
+  *dir = ZhZipDirectory{num_records, cd_size, cd_start, socd};
+  return ZH_OK;
+}
+
+// openZipArchive, ziparchives.nim:183-372
+extern "C" int zh_zip_open(const void* archive, size_t len, zh_zip_reader** out) {
+  if (!out || (len && !archive)) return ZH_ERR_ARGUMENT;
+  *out = nullptr;
+  const Image im{(const uint8_t*)archive, (int64_t)len};
+  ZhZipDirectory dir;
+  if (const int st = zh_zip_locate(archive, len, &dir)) return st;
+  const int64_t num_records = dir.num_records, cd_size = dir.cd_size, cd_start = dir.cd_start, socd = dir.socd;
   const int64_t socd_offset = socd - cd_start;
   int64_t pos = socd_offset + cd_start;
 

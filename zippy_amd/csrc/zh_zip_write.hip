@@ -10,6 +10,7 @@
 #include <unordered_set>
 
 #include "zh_host.h"
+#include "zh_gather.h"
 
 namespace {
 
@@ -39,10 +40,6 @@ struct ZhZipTask {
 
 constexpr uint64_t kSlice = 32768;  // stream bytes a wave copies at most
 constexpr uint32_t kLocalSig = 0x04034b50u, kCentralSig = 0x02014b50u, kEocdSig = 0x06054b50u;
-
-struct alignas(16) Chunk16 {
-  uint32_t w[4];
-};
 
 // byte j of the little-endian field x that starts at byte `at`
 __device__ __forceinline__ uint32_t le(uint32_t x, uint32_t j, uint32_t at) { return (x >> (8 * (j - at))) & 0xffu; }
@@ -118,33 +115,6 @@ __device__ __forceinline__ Chunk16 bytes16(const Gen& g, uint64_t c) {
 #pragma unroll
   for (uint32_t k = 0; k < 16; k++) v.w[k >> 2] |= g.byte(c + k) << (8 * (k & 3));
   return v;
-}
-
-// out word k = bytes [4 * (W0 + k) + b, + 4) of w: one alignbyte a word
-template <int W0>
-__device__ __forceinline__ Chunk16 funnel(const uint32_t (&w)[8], uint32_t b) {
-  Chunk16 r;
-#pragma unroll
-  for (int k = 0; k < 4; k++) r.w[k] = __builtin_amdgcn_alignbyte(w[W0 + k + 1], w[W0 + k], b);
-  return r;
-}
-
-// Sixteen source bytes at s (any alignment) from two aligned 16-byte loads, recombined.  s & 15 is the same for every
-// chunk of a range (source and destination advance together), so the branches are uniform across the wave.  The
-// second load reads at most 31 bytes past s: inside the output slot's 256-byte rounding or the buffer's 256 spare.
-__device__ __forceinline__ Chunk16 gather16(const uint8_t* __restrict__ base, uint64_t s) {
-  const Chunk16* p = reinterpret_cast<const Chunk16*>(base + (s & ~(uint64_t)15));
-  const uint32_t sh = (uint32_t)(s & 15);
-  const Chunk16 x = p[0];
-  if (sh == 0) return x;
-  const Chunk16 y = p[1];
-  const uint32_t w[8] = {x.w[0], x.w[1], x.w[2], x.w[3], y.w[0], y.w[1], y.w[2], y.w[3]};
-  switch (sh >> 2) {
-    case 0: return funnel<0>(w, sh & 3);
-    case 1: return funnel<1>(w, sh & 3);
-    case 2: return funnel<2>(w, sh & 3);
-    default: return funnel<3>(w, sh & 3);
-  }
 }
 
 // One wave writes the image range [a, b): the bytes in front of the first and behind the last aligned 16-byte chunk

@@ -10,6 +10,7 @@ import zlib
 
 import numpy as np
 
+import deflate_craft as dc
 import oracle
 import synth
 
@@ -1497,3 +1498,702 @@ def checksum_entry_point_inputs(small=False):
     if small:
         inputs = [b for b in inputs[:-3] if len(b) <= 40000] + [b[:40000 - 777 * k] for k, b in enumerate(inputs[-3:])]
     return inputs
+
+
+# ---- hand-built deflate streams (tests/deflate_craft.py): what no encoder emits.  Every case is
+# (name, raw deflate, plain or None, status or None); the name's part before the "/" is its family. ----
+def _t1_code():
+    """Codes that reach 15 bits in both alphabets, both complete: literals 0..253 and the end of block at 8 bits,
+    254 at 9, 255 at 10, lengths 257 / 258 / 259 at 11 / 12 / 13, 281..284 (five extra bits) at 15; distances
+    0..13 at 1..14 bits, 28 and 29 (thirteen extra bits) at 15.  281..284 with 28 / 29 is a 48-bit token."""
+    lit = [0] * 286
+    for i in range(254):
+        lit[i] = 8
+    lit[254], lit[255], lit[256], lit[257], lit[258], lit[259] = 9, 10, 8, 11, 12, 13
+    for i in range(281, 285):
+        lit[i] = 15
+    dist = [0] * 30
+    for k in range(14):
+        dist[k] = k + 1
+    dist[28] = dist[29] = 15
+    assert dc.kraft(lit) == 32768 and dc.kraft(dist) == 32768
+    return lit, dist
+
+
+def _craft_t1(s, ntokens, final, rnd):
+    """A stored preamble of 32 KiB, then one dynamic block of ntokens tokens: runs of 32 back-to-back 48-bit tokens
+    with a 9-bit literal between the runs (48 * 32 = 3 * 512 and 9 is a unit mod 16: 16 runs start a 48-bit token at
+    every residue mod 512), then pairs and single ones between literals of 8, 9 and 10 bits."""
+    s.stored(rnd.randbytes(32768), False)
+    lit, dist = _t1_code()
+    s.dynamic_block(lit, dist, final)
+    n = [0]
+
+    def tok():
+        j = n[0]
+        n[0] += 1
+        sym = 281 + j % 4
+        extra = 31 if j % 8 == 3 else (j * 7) % 32   # (284 with 31: length 258 without symbol 285)
+        e = 8191 if j % 16 == 0 else 0 if j % 16 == 1 else (j * 2731) % 8192
+        s.match(dc.LEN_BASE[sym - 257] + extra, (16385, 24577)[j % 2] + e, length_symbol=sym)
+
+    def lit8():
+        s.lit(n[0] % 250)
+        n[0] += 1
+
+    def lit9():
+        s.lit(254)
+        n[0] += 1
+
+    def lit10():
+        s.lit(255)
+        n[0] += 1
+    for _ in range(16):
+        for _ in range(32):
+            tok()
+        lit9()
+    while n[0] + 3 <= min(ntokens, 600):
+        tok(), lit8(), lit10()
+    while n[0] + 3 <= min(ntokens, 1110):
+        tok(), tok(), lit9()
+    while n[0] + 6 <= ntokens:
+        tok(), lit8(), tok(), lit10(), tok(), lit9()
+    s.eob()
+
+
+def _craft_w1(s, dist, final, rnd):
+    """dist non-periodic bytes stored, then a match of every length 3..258 at that distance, a literal behind every
+    third: 33 408 bytes of matches whose starts and sources drift through every phase of the writer's rounds"""
+    s.stored(rnd.randbytes(dist), False)
+    s.fixed_block(final)
+    for k, length in enumerate(range(3, 259)):
+        s.match(length, dist)
+        if k % 3 == 2:
+            s.lit((k * 37 + 11) & 0xff)
+    s.eob()
+
+
+def _craft_chain(s, length, dist, n, final):
+    """n matches, each one's source the match before it"""
+    s.fixed_block(final)
+    for i in range(dist):
+        s.lit(0x41 + i)
+    for _ in range(n):
+        s.match(length, dist)
+    s.eob()
+
+
+def _craft_w3(s, nblocks, npairs, final):
+    """rounds that run out of records before they run out of bytes: blocks of one literal, (literal, short match)
+    pairs, and k = 0..5 literals before a match, before an end of block and before a stored block"""
+    for i in range(nblocks):
+        s.fixed_block(False)
+        s.lit((i * 131 + 7) & 0xff)
+        s.eob()
+    s.fixed_block(False)
+    for b in b"xyz":
+        s.lit(b)
+    for i in range(npairs):
+        s.lit(i & 0xff)
+        s.match(3, 3 + i % 2)
+    s.eob()
+    s.fixed_block(False)
+    for rep in range(3):
+        for k in range(6):
+            for j in range(k):
+                s.lit(0x30 + j + rep)
+            s.match(4, 5)
+    s.eob()
+    for rep in range(3):
+        for k in range(6):
+            s.fixed_block(False)
+            for j in range(k):
+                s.lit(0x61 + j + rep)
+            s.eob()
+    for rep in range(3):
+        for k in range(6):
+            s.fixed_block(False)
+            for j in range(k):
+                s.lit(0x41 + j + rep)
+            s.eob()
+            s.stored(bytes([0x80 + k, 0x90 + rep, 0xa0]), False)
+    s.fixed_block(final)
+    s.lit(0x2e)
+    s.eob()
+
+
+def _craft_w4(op, kind, ok, variant, rnd):
+    """op bytes in an earlier stored / fixed / dynamic block, then a match at distance op (ok) or op + 1"""
+    s = dc.Stream()
+    data = rnd.randbytes(op)
+    if kind == "stored":
+        s.stored(data, False)
+    else:
+        if kind == "fixed":
+            s.fixed_block(False)
+        else:
+            s.dynamic_block(*_t1_code(), False)
+        for b in data:
+            s.lit(b)
+        s.eob()
+    s.fixed_block(True)
+    length, sym = ((258, 285), (258, 284), (3, None))[variant]
+    s.match(length, op if ok else op + 1, length_symbol=sym)
+    s.lit(0x21)
+    s.eob()
+    return s
+
+
+def _craft_data_block(s, final):
+    s.fixed_block(final)
+    for b in b"hello, hello":
+        s.lit(b)
+    s.match(5, 7)
+    s.eob()
+
+
+def _craft_b1(s, kind, n, final):
+    """n empty blocks, then data.  Empty stored blocks: each behind a fixed block of 0..7 nine-bit literals, so that
+    its header follows each of the 8 bit phases; the bits skipped up to the byte boundary are ones."""
+    for i in range(n):
+        if kind == "fixed":
+            s.fixed_block(False)
+            s.eob()
+        elif kind == "dynamic":
+            s.dynamic_block([0] * 256 + [1], [0], False)
+            s.eob()
+        else:
+            s.fixed_block(False)
+            for j in range((i - 2) % 8):
+                s.lit(200 + j)
+            s.eob()
+            s.stored(b"", False, pad_bits=0xff)
+    _craft_data_block(s, final)
+
+
+def _craft_b2(s, final):
+    """1024 blocks, alternately fixed and dynamic, a pair an odd number of bits long: 512 pairs put a header of either
+    kind at every residue mod 512"""
+    lit = [0] * 257
+    lit[97] = lit[256] = 1
+
+    def pair(t, extra):
+        t.fixed_block(False)
+        t.lit(200)
+        if extra:
+            t.lit(201)
+        t.eob()
+        t.dynamic_block(lit, [0], False)
+        t.lit(97)
+        t.eob()
+    probe = dc.Stream()
+    pair(probe, False)
+    extra = probe.bitpos % 2 == 0
+    for _ in range(512):
+        pair(s, extra)
+    _craft_data_block(s, final)
+
+
+def _small_dyn(s, final, lit=None, dist=None, **plan):
+    """a small complete code: literals a, b, c at 2 bits, end of block and length symbol 257 at 3; distances 1 and 2"""
+    if lit is None:
+        lit = [0] * 258
+        lit[97] = lit[98] = lit[99] = 2
+        lit[256] = lit[257] = 3
+    if dist is None:
+        dist = [1, 1]
+    s.dynamic_block(lit, dist, final, plan or None)
+
+
+def _craft_headers():
+    """-> [(name, Stream)]: H1..H4"""
+    out = []
+
+    def new(name):
+        s = dc.Stream()
+        out.append((name, s))
+        return s
+
+    def abc(s, with_match=True):
+        for b in b"abcabc":
+            s.lit(b)
+        if with_match:
+            s.match(3, 2)
+        s.eob()
+
+    def garbage(s, status):
+        s.raw_bits(0x2d5a, 16)
+        s.raw_bits(0x1234, 16)
+        s.expect_fail(status)
+    # H1: field limits
+    s = new("H1/hlit257")
+    lit = [0] * 257
+    lit[97] = lit[98] = lit[99] = lit[256] = 2
+    s.dynamic_block(lit, [0], True)
+    abc(s, False)
+    s = new("H1/hlit286")
+    lit = [0] * 286
+    lit[97] = lit[98] = lit[99] = 2
+    lit[256] = lit[285] = 3
+    s.dynamic_block(lit, [1, 1], True)
+    s.lit(97), s.lit(98), s.match(258, 1), s.match(258, 2), s.eob()
+    for n in (287, 288):
+        s = new("H1/hlit%d" % n)
+        s.dynamic_block(lit + [0] * (n - 286), [1, 1], True)
+        garbage(s, dc.INVALID_BUFFER)
+    s = new("H1/hdist1")
+    _small_dyn(s, True, dist=[1])
+    s.lit(97), s.match(3, 1), s.eob()
+    s = new("H1/hdist30")
+    s.stored(bytes(range(256)) * 128, False)
+    _small_dyn(s, True, dist=[1] + [0] * 28 + [1])
+    s.lit(97), s.match(3, 32768), s.match(3, 1), s.match(3, 24577), s.eob()
+    for n in (31, 32):
+        s = new("H1/hdist%d" % n)
+        _small_dyn(s, True, dist=[1] + [0] * (n - 2) + [1])
+        garbage(s, dc.INVALID_BUFFER)
+    s = new("H1/hclen4")   # only 16, 17, 18 and 0 can have a code: every length is zero, the first token has no code
+    cl = [0] * 19
+    cl[18] = cl[0] = 1
+    s.dynamic_block([0] * 257, [0], True, {"symbols": [(18, 127), (18, 109)], "cl_lens": cl, "hclen": 4})
+    garbage(s, dc.INVALID_BUFFER)
+    s = new("H1/hclen19")
+    s.dynamic_block(*_t1_code(), True)
+    assert s.lit_lens[284] == 15
+    for b in b"\x00\xfe\xff\x10":
+        s.lit(b)
+    s.match(258, 3, length_symbol=284), s.match(3, 4), s.eob()
+    # H2: repeat symbols.  The lengths are what the symbols spell: literal 150 (151), the end of block, length symbol 257
+    def spelled(name, symbols, hlit, hdist, tokens, status=None):
+        s = new(name)
+        lens = dc.expand_cl_symbols(symbols)
+        if status is None:
+            assert len(lens) == hlit + hdist
+            s.dynamic_block(lens[:hlit], lens[hlit:], True, {"symbols": symbols})
+            tokens(s)
+        else:
+            lens = (lens or []) + [0] * 320
+            s.dynamic_block(lens[:hlit], lens[hlit:hlit + hdist], True, {"symbols": symbols, "check": False})
+            garbage(s, status)
+    zeros150 = [(18, 127), (18, 1)]
+    after = [(17, 0), (16, 0), (18, 127), (16, 3)]   # 3 + 3 + 138 + 6 zeros: the 16s repeat a zero
+    rest = [(2, 0)] * 3 + [(18, 92), (3, 0), (3, 0), (1, 0), (1, 0)]
+    spelled("H2/16_first", [(16, 0)] + after + rest, 258, 2, None, dc.INVALID_BUFFER)
+    spelled("H2/16_after_17_and_18", after + rest, 258, 2,
+            lambda s: (s.lit(150), s.lit(151), s.lit(152), s.match(3, 2), s.eob()))
+    spelled("H2/16_crosses_border", zeros150 + [(2, 0), (2, 0), (18, 93), (2, 0), (16, 2)], 258, 4,
+            lambda s: (s.lit(150), s.lit(151), s.lit(150), s.lit(151), s.match(3, 4), s.match(3, 1), s.eob()))
+    spelled("H2/18_crosses_border", zeros150 + [(1, 0), (18, 94), (1, 0), (18, 2), (1, 0), (1, 0)], 260, 12,
+            lambda s: (s.lit(150), s.lit(150), s.eob()))
+    tail = zeros150 + [(1, 0), (18, 94), (2, 0), (2, 0)]   # 150 at 1 bit, end of block and 257 at 2
+    spelled("H2/16_ends_exactly", tail + [(2, 0), (16, 0)], 258, 4,
+            lambda s: (s.lit(150), s.lit(150), s.lit(150), s.lit(150), s.match(3, 4), s.match(3, 1), s.eob()))
+    spelled("H2/16_one_past", tail + [(2, 0), (16, 1)], 258, 4, None, dc.INVALID_BUFFER)
+    spelled("H2/17_ends_exactly", tail + [(1, 0), (1, 0), (17, 0)], 258, 5,
+            lambda s: (s.lit(150), s.lit(150), s.match(3, 2), s.eob()))
+    spelled("H2/17_one_past", tail + [(1, 0), (1, 0), (17, 1)], 258, 5, None, dc.INVALID_BUFFER)
+    s = new("H2/16_past_320")   # HLIT 286, HDIST 30: at place 315 a repeat of 6 would fill 321 places
+    s.dynamic_block([0] * 286, [0] * 30, True,
+                    {"symbols": [(18, 127), (18, 127), (17, 7)] + [(8, 0)] * 29 + [(16, 3)], "check": False})
+    garbage(s, dc.INVALID_BUFFER)
+    # H3: the code-length code itself
+    one = [0] * 19
+    one[9] = 1
+    s = new("H3/single_symbol")   # 258 times "9": 257 + 1 codes of 9 bits, half the space of either alphabet unused
+    s.dynamic_block([9] * 259, [9], True, {"symbols": [(9, 0)] * 260, "cl_lens": one})
+    for b in b"single":
+        s.lit(b)
+    s.match(4, 1), s.eob()
+    s = new("H3/single_symbol_unused_pattern")
+    s.dynamic_block([9] * 257, [9], True, {"symbols": [(9, 0), (("raw", 1, 1), 0)] + [(9, 0)] * 256, "cl_lens": one, "check": False})
+    garbage(s, dc.INVALID_SYMBOL)
+    over = [0] * 19
+    over[0] = over[8] = over[9] = 1
+    s = new("H3/oversubscribed")
+    s.dynamic_block([8] * 257, [9], True, {"symbols": [(0, 0)] * 5, "cl_lens": over, "check": False})
+    garbage(s, dc.INVALID_BUFFER)
+    s = new("H3/all_zero")
+    s.dynamic_block([0] * 257, [0], True, {"symbols": [], "cl_lens": [0] * 19, "hclen": 4, "check": False})
+    garbage(s, dc.INVALID_SYMBOL)
+    # H4: the literal and distance code sets
+    for n in range(1, 16):
+        lens = list(range(1, n)) + [n, n, n]   # a complete set and one code more at length n
+        for alphabet in ("lit", "dist"):
+            s = new("H4/%s_oversubscribed_%d" % (alphabet, n))
+            if alphabet == "lit":
+                lit = [0] * 257
+                lit[40:40 + len(lens)] = lens
+                s.dynamic_block(lit, [1, 1], True)
+            else:
+                _small_dyn(s, True, dist=lens)
+            garbage(s, dc.INVALID_BUFFER)
+    s = new("H4/no_distance_code_literals_only")
+    _small_dyn(s, True, dist=[0])
+    abc(s, False)
+    s = new("H4/no_distance_code_one_match")
+    _small_dyn(s, True, dist=[0])
+    s.lit(97), s.lit(98), s.lit(99)
+    s.raw_code("lit", s.lit_codes[257], 3)
+    garbage(s, dc.INVALID_BUFFER)
+    s = new("H4/no_end_of_block_code")   # literals (the all-zero pattern is one) until the input runs out
+    lit = [0] * 257
+    lit[97] = 1
+    lit[98] = lit[99] = 2
+    s.dynamic_block(lit, [0], False)
+    for b in b"abcabcaabbcc" * 5:
+        s.lit(b)
+    s.expect_fail(dc.END_OF_BUFFER)
+    return out
+
+
+def _craft_t2_t3():
+    """-> [(name, Stream)]: unused patterns of incomplete codes (each followed by valid data) and the fixed codes'
+    symbols without a meaning"""
+    out = []
+
+    def new(name):
+        s = dc.Stream()
+        out.append((name, s))
+        return s
+
+    def lit_set(lens_abc_eob_257):
+        lit = [0] * 258
+        lit[97], lit[98], lit[99], lit[256], lit[257] = lens_abc_eob_257
+        return lit
+    # literal/length codes: {a, b, EOB at 2 bits} leaves "11" unused (inside the root table); 1, 2, .., 12 bits leaves
+    # twelve ones unused (beyond it)
+    deep = [0] * 258
+    for k in range(11):
+        deep[97 + k] = k + 1
+    deep[256] = 12
+    for name, lit, pattern, nbits in (("lit_short", lit_set((2, 2, 0, 2, 0)), 0b11, 2), ("lit_long", deep, 0xfff, 12)):
+        s = new("T2/%s_used" % name)
+        s.dynamic_block(lit, [1, 1], True)
+        for b in b"abbaabab" + (bytes(range(97, 108)) if name == "lit_long" else b""):
+            s.lit(b)
+        s.eob()
+        s = new("T2/%s_unused" % name)
+        s.dynamic_block(lit, [1, 1], True)
+        s.lit(97), s.lit(98)
+        s.raw_code("lit", pattern, nbits)
+        s.expect_fail(dc.INVALID_BUFFER)
+        for b in b"abab":
+            s.lit(b)
+        s.eob()
+    # distance codes: {0, 1, 2 at 2 bits} leaves "11"; 1, 2, .., 10 bits leaves ten ones; a single code of one bit
+    for name, dist, pattern, nbits in (("dist_short", [2, 2, 2], 0b11, 2), ("dist_long", list(range(1, 11)), 0x3ff, 10),
+                                       ("dist_single", [1], 0b1, 1)):
+        s = new("T2/%s_used" % name)
+        _small_dyn(s, True, dist=dist)
+        for b in b"abcabcabcabc":
+            s.lit(b)
+        for d in range(len(dist)):
+            s.match(3, dc.DIST_BASE[d])
+        s.eob()
+        s = new("T2/%s_unused" % name)
+        _small_dyn(s, True, dist=dist)
+        for b in b"abcabcabcabc":
+            s.lit(b)
+        s.raw_code("lit", s.lit_codes[257], 3)
+        s.raw_code("dist", pattern, nbits)
+        s.expect_fail(dc.INVALID_BUFFER)
+        for b in b"abc":
+            s.lit(b)
+        s.match(3, 1), s.eob()
+    for sym in (286, 287):
+        s = new("T3/fixed_litlen_%d" % sym)
+        s.fixed_block(True)
+        s.lit(1), s.lit(2), s.lit(3)
+        s.raw_code("lit", s.lit_codes[sym], 8)
+        s.expect_fail(dc.INVALID_BUFFER)
+        s.raw_bits(0, 5), s.lit(4), s.eob()
+    for sym in (30, 31):
+        s = new("T3/fixed_dist_%d" % sym)
+        s.fixed_block(True)
+        s.lit(1), s.lit(2), s.lit(3)
+        s.raw_code("lit", s.lit_codes[257], 7)
+        s.raw_code("dist", sym, 5)
+        s.expect_fail(dc.INVALID_BUFFER)
+        s.lit(4), s.eob()
+    return out
+
+
+def _craft_b4():
+    """-> [(name, Stream)]: the last end-of-block code followed by 0..7 padding bits (ones); input that ends inside a
+    length's extra bits, inside a distance code and inside a stored block's LEN.  The cut streams' blocks are not
+    final and their codes read zero bits as literals, so what the reference makes of the missing bits (it reads
+    zeros) is decided by its end-of-buffer check alone."""
+    out = []
+    for pad in range(8):
+        s = dc.Stream()
+        s.fixed_block(True)
+        s.lit(65)
+        while (s.bitpos + 7 + pad) % 8:
+            s.lit(200)   # nine bits: moves the phase by one
+        s.eob()
+        assert (8 - s.bitpos % 8) % 8 == pad
+        s.final_pad = 0xff
+        out.append(("B4/eob_pad_%d" % pad, s))
+    lit = [0] * 282
+    for i in range(97, 97 + 7):
+        lit[i] = 3
+    lit[256] = lit[281] = 4   # (281: five extra bits)
+    for what in ("length_extra", "distance_code"):
+        s = dc.Stream()
+        s.dynamic_block(lit, [2, 2, 2, 2], False)
+        for b in b"abcdefg":
+            s.lit(b)
+        while True:   # literals until the field straddles a byte border
+            field = s.bitpos + 4 if what == "length_extra" else s.bitpos + 4 + 5
+            width = 5 if what == "length_extra" else 2
+            cut = (field // 8 + 1) * 8
+            if field < cut < field + width:
+                break
+            s.lit(97)
+        s.match(131 + 21, 3, length_symbol=281)
+        s.cut_at_bit(cut)
+        s.expect_fail(dc.END_OF_BUFFER)
+        out.append(("B4/ends_in_" + what, s))
+    s = dc.Stream()
+    _craft_data_block(s, False)
+    s.stored(b"never read", True)
+    s.cut_at_bit((s.headers[-1][0] + 3 + 7) // 8 * 8 + 8)   # one byte of LEN and nothing behind it
+    s.expect_fail(dc.INVALID_BUFFER)                        # LEN + NLEN (read as zero) is not 65535
+    out.append(("B4/ends_in_stored_len", s))
+    return out
+
+
+W1_DISTANCES = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 255, 256, 257, 258, 259, 2047, 2048, 2049, 4095, 4096, 4097,
+                8191, 8192, 8193, 32767, 32768)
+W1_DISTANCES_SMALL = (1, 3, 8, 259, 2048, 32768)
+CRAFT_COUNTS = {"T1": 1, "T2": 10, "T3": 4, "W1": 30, "W2": 4, "W3": 1, "W4": 27, "B1": 12, "B2": 1, "B3": 1, "B4": 11,
+                "H1": 10, "H2": 9, "H3": 4, "H4": 33}
+CRAFT_COUNTS_SMALL = {"T1": 1, "T2": 10, "T3": 4, "W1": 6, "W2": 4, "W3": 1, "W4": 6, "B1": 3, "B2": 1, "B3": 1, "B4": 11,
+                      "H1": 10, "H2": 9, "H3": 4, "H4": 33}
+_craft_cache = {}
+
+
+def crafted_streams(small=False, info=None):
+    """The families T1-T3 (tokens), W1-W4 (writer), B1-B4 (blocks), H1-H4 (headers) -> [(name, raw deflate, plain or
+    None, status or None)].  info: a dict that receives name -> (token positions, header positions) of the builder.
+    small: the subset for the emulator (about 300 KB of output)."""
+    if small not in _craft_cache:
+        rnd = random.Random(1951)
+        named = []
+
+        def new(name):
+            s = dc.Stream()
+            named.append((name, s))
+            return s
+        _craft_t1(new("T1/48_bit_tokens"), 600 if small else 1500, True, rnd)
+        named += _craft_t2_t3()
+        for d in W1_DISTANCES_SMALL if small else W1_DISTANCES:
+            _craft_w1(new("W1/dist_%d" % d), d, True, rnd)
+        chains = 500 if small else 3000
+        for length, d, n in ((3, 3, chains), (3, 1, chains), (4, 2, chains), (258, 1, 300 if small else 3000)):
+            _craft_chain(new("W2/chain_len%d_dist%d" % (length, d)), length, d, n, True)
+        _craft_w3(new("W3/starved_rounds"), 1500 if small else 9000, 500 if small else 3000, True)
+        k = 0
+        for op in (1, 2, 258, 32767, 32768):
+            for kind in ("stored", "fixed", "dynamic"):
+                for ok in (True, False):
+                    k += 1
+                    if not ok and op == 32768:
+                        continue   # (32 769 is a distance the format cannot write)
+                    if small and not (op, kind) in ((1, "fixed"), (258, "dynamic"), (32767, "stored")):
+                        continue
+                    named.append(("W4/op%d_%s_%s" % (op, kind, "at" if ok else "past"), _craft_w4(op, kind, ok, k % 3, rnd)))
+        for kind in ("fixed", "dynamic", "stored"):
+            for n in (52,) if small else (1, 51, 52, 5000):
+                _craft_b1(new("B1/%d_empty_%s" % (n, kind)), kind, n, True)
+        _craft_b2(new("B2/header_at_every_residue"), True)
+        text = synth.corpus_file("alice29.txt")[:5000 if small else 20000]
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        parts = []
+        for o in range(0, len(text), 50):
+            parts.append(c.compress(text[o:o + 50]))
+            parts.append(c.flush(zlib.Z_PARTIAL_FLUSH))
+        parts.append(c.flush())
+        named += _craft_b4()
+        named += _craft_headers()
+        cases, positions = [], {}
+        for name, s in named:
+            positions[name] = (s.tokens, s.headers)
+            cases.append((name,) + s.finish())
+        cases.append(("B3/partial_flush_every_50", b"".join(parts), text, None))
+        _craft_cache[small] = (cases, positions)
+    cases, positions = _craft_cache[small]
+    if info is not None:
+        info.update(positions)
+    return list(cases)
+
+
+def crafted_coverage(positions):
+    """the coverage conditions of T1 and B2, from the builder's positions: (residues mod 512 at which a 48-bit token
+    starts, residues at which a fixed block's header starts, residues at which a dynamic block's does)"""
+    tokens, _ = positions["T1/48_bit_tokens"]
+    _, headers = positions["B2/header_at_every_residue"]
+    return ({p % 512 for p, bits, kind in tokens if kind == "match" and bits == 48},
+            {p % 512 for p, btype in headers if btype == 1}, {p % 512 for p, btype in headers if btype == 2})
+
+
+# Rejected cases whose status is not compared with the oracle's, only that both refuse (DESIGN.md 2): name -> reason
+CRAFT_STATUS_EXCEPTIONS = {}
+CRAFT_SINGLE_FAMILIES = ("T1", "W2", "W3", "B1")
+
+
+def _stderr_of(fn):
+    """fn() with file descriptor 2 in a temporary file -> (result, what the library wrote there)"""
+    import sys
+    import tempfile
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            res = fn()
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        return res, tmp.read().decode("utf-8", "replace")
+
+
+def check_crafted_streams(eng, small=False):
+    """crafted_streams() through the device decoder: all of them in one batch (expected bytes, the oracle's status for
+    every rejected one, neighbours untouched); T1 / W2 / W3 / B1 again one stream a call (the wide kernels); the
+    accepted ones wrapped as gzip and zlib through dfDetect (the checksum kernels see this output too); into slots of
+    exactly the expected size and one byte short (ZH_ERR_DST_TOO_SMALL with the true length, the bytes between the
+    slots unchanged); and the sizing pass for the stream that outgrows the guess a raw stream gets."""
+    cases = crafted_streams(small)
+    outs, sts = eng.uncompress_batch([c[1] for c in cases], oracle.dfDeflate)
+    bad = []
+    for (name, blob, plain, status), got, st in zip(cases, outs, sts):
+        if plain is not None:
+            if st != 0 or got != plain:
+                bad.append((name, st, None if got is None else len(got), len(plain)))
+        elif st == 0 or (st != status and name not in CRAFT_STATUS_EXCEPTIONS):
+            bad.append((name, "status", st, "expected", status))
+    assert not bad, bad
+    for name, blob, plain, status in cases:
+        if name.split("/")[0] in CRAFT_SINGLE_FAMILIES:
+            got, st = eng.uncompress_batch([blob], oracle.dfDeflate)
+            assert st == [0] and got[0] == plain, (name, "alone", st)
+    good = [c for c in cases if c[2] is not None]
+    wrapped = []
+    for name, blob, plain, _ in good:
+        wrapped.append(b"\x1f\x8b\x08\x00" + b"\x00" * 6 + blob + struct.pack("<II", zlib.crc32(plain), len(plain)))
+        wrapped.append(b"\x78\x9c" + blob + struct.pack(">I", zlib.adler32(plain)))
+    outs, sts = eng.uncompress_batch(wrapped, oracle.dfDetect)
+    bad = [(good[i // 2][0], ("gzip", "zlib")[i % 2], sts[i]) for i in range(len(wrapped))
+           if sts[i] != 0 or outs[i] != good[i // 2][2]]
+    assert not bad, bad
+    hurt = bytearray(wrapped[0])
+    hurt[-5] ^= 0x10   # (the premise: a wrong checksum does not pass)
+    assert eng.uncompress_batch([bytes(hurt)], oracle.dfDetect)[1] == [ZH_ERR_CHECKSUM]
+    for short in (0, 1):
+        some = [c for c in good if len(c[2]) >= short]
+        caps = [len(c[2]) - short if c[2] else 0 for c in some]
+        offs, pos = [], 5
+        for c in caps:
+            offs.append(pos)
+            pos += c + 7
+        arena = bytearray(b"\xa5" * (pos + 16))
+        view = memoryview(arena)
+        lens, sts, filled = eng.uncompress_batch_into([c[1] for c in some], [view[o:o + c] for o, c in zip(offs, caps)],
+                                                      oracle.dfDeflate)
+        keep = bytearray(b"\x01" * len(arena))
+        for (name, blob, plain, _), o, c, ln, st in zip(some, offs, caps, lens, sts):
+            assert ln == len(plain), (name, short, ln, len(plain))
+            if c == len(plain):
+                assert st == 0 and bytes(arena[o:o + c]) == plain, (name, short, st)
+            else:
+                assert st == ZH_ERR_DST_TOO_SMALL, (name, short, st)
+            keep[o:o + c] = bytes(c)
+        changed = [i for i in range(len(arena)) if keep[i] and arena[i] != 0xa5]
+        assert not changed, ("bytes outside the slots changed", short, changed[:4])
+    # raw deflate gets 4 x its size + 64 KiB: the chains of short matches stay below that, the chain of 258-byte
+    # matches does not -- decode, count, decode again
+    by_name = {c[0]: c for c in cases}
+    old = os.environ.get("ZH_TRACE")
+    os.environ["ZH_TRACE"] = "1"
+    try:
+        for name, passes in (("W2/chain_len258_dist1", 3), ("W2/chain_len3_dist3", 1)):
+            blob, plain = by_name[name][1:3]
+            assert (len(plain) > 4 * len(blob) + 65536) == (passes == 3)
+            (got, st), err = _stderr_of(lambda: eng.uncompress_batch([blob], oracle.dfDeflate))
+            assert st == [0] and got[0] == plain
+            assert err.count("uncompress: kernels") == passes, (name, err)
+    finally:
+        if old is None:
+            del os.environ["ZH_TRACE"]
+        else:
+            os.environ["ZH_TRACE"] = old
+
+
+def crafted_segment_streams(small=False):
+    """Crafted blocks back to back in one stream, only the last block final: a stored preamble, W1 at distances
+    32 768 and 32 767, the W2 chains, T1, 52 empty blocks of each kind, then text in zlib's dynamic blocks.  The same
+    with a symbol that has no meaning (fixed code 286) late in the text, and with a distance one beyond the start of
+    the output early (the format cannot write such a distance once 32 768 bytes are out).
+    -> [(raw deflate, plain or None, status or None)]"""
+    text = synth.gen_batch("text", 1, 120000 if small else 600000, first_index=4)[0].tobytes()
+    out = []
+    for fault in (None, "late", "early"):
+        rnd = random.Random(32768)
+        s = dc.Stream()
+        s.stored(rnd.randbytes(1000), False)
+        if fault == "early":
+            s.fixed_block(False)
+            s.lit(1), s.match(3, 1002), s.eob()
+        s.stored(rnd.randbytes(30000), False)
+        _craft_w1(s, 32768, False, rnd)
+        _craft_w1(s, 32767, False, rnd)
+        for length, d in ((3, 3), (3, 1), (4, 2)):
+            _craft_chain(s, length, d, 500 if small else 3000, False)
+        _craft_t1(s, 600 if small else 1500, False, rnd)
+        for kind in ("fixed", "dynamic", "stored"):
+            _craft_b1(s, kind, 52, False)
+        s.stored(b"", False)   # (byte-aligned from here on: zlib's blocks end in stored ones, which do not shift)
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        step = len(text) // 6
+        for k in range(6):
+            part = text[k * step:(k + 1) * step]
+            s.append_bytes(c.compress(part) + c.flush(zlib.Z_FULL_FLUSH), part)
+            if fault == "late" and k == 4:
+                s.fixed_block(False)
+                s.lit(2)
+                s.raw_code("lit", s.lit_codes[286], 8)
+                s.expect_fail(dc.INVALID_BUFFER)
+                s.lit(3), s.eob()
+                s.stored(b"", False)
+        s.append_bytes(c.flush(), b"")
+        out.append(s.finish())
+    return out
+
+
+def check_crafted_segmented(eng, monkeypatch, small=False):
+    """The streams above decoded segment-wise (2 048-byte segments): the expected bytes, the stream was cut, and the
+    faulty streams end with the status the one-workgroup decode gives them -- the oracle's."""
+    monkeypatch.setenv("ZH_SEG_MIN", "8192")
+    monkeypatch.setenv("ZH_SEG_BYTES", "2048")
+    monkeypatch.setenv("ZH_SEG_SETUP", "0")
+    for blob, plain, status in crafted_segment_streams(small):
+        try:
+            ref = oracle.uncompress(blob, oracle.dfDeflate)
+            assert plain is not None and ref == plain
+        except oracle.ZippyError as e:
+            assert plain is None and e.status == status
+        before = eng.segment_stats()
+        outs, sts = eng.uncompress_batch([blob], oracle.dfDeflate)
+        cut = eng.segment_stats()[0] - before[0]
+        assert cut >= 1, "the stream was not cut into segments"
+        if plain is not None:
+            assert sts == [0] and outs[0] == plain, sts
+        else:
+            monkeypatch.setenv("ZH_SEG", "0")
+            _, whole = eng.uncompress_batch([blob], oracle.dfDeflate)
+            monkeypatch.setenv("ZH_SEG", "1")
+            assert sts == whole == [status], (sts, whole, status)
+    for k in ("ZH_SEG_MIN", "ZH_SEG_BYTES", "ZH_SEG_SETUP", "ZH_SEG"):
+        monkeypatch.delenv(k, raising=False)

@@ -375,3 +375,11 @@ def test_emu_split_inflate_edges(eng, inflate_mode):
 def test_emu_segmented_streams(eng, monkeypatch):
     pc.check_segmented(eng, 1024, monkeypatch, 2048)
     pc.check_segmented(eng, 1024, monkeypatch, 600)  # chains of more than two window groups
+
+
+def test_emu_crafted_streams(eng, inflate_mode):
+    pc.check_crafted_streams(eng, small=True)
+
+
+def test_emu_crafted_streams_segmented(eng, monkeypatch):
+    pc.check_crafted_segmented(eng, monkeypatch, small=True)

@@ -511,6 +511,15 @@ def test_gpu_split_inflate_edges(eng, inflate_mode):
     pc.check_split_inflate_edges(eng)
 
 
+def test_gpu_crafted_streams(eng, inflate_mode):
+    """Hand-built streams no encoder emits (tests/deflate_craft.py, parity_cases.crafted_streams)."""
+    pc.check_crafted_streams(eng, small=False)
+
+
+def test_gpu_crafted_streams_segmented(eng, monkeypatch):
+    pc.check_crafted_segmented(eng, monkeypatch, small=False)
+
+
 def test_gpu_segmented_streams(eng, monkeypatch):
     """Large streams on many workgroups (zh_inflate_seg.hip), small segments and the default ones."""
     pc.check_segmented(eng, 1024, monkeypatch, 2048)

@@ -3,6 +3,7 @@ zippy_amd/libzippy_hip.so) and tests/test_emu_parity.py (the same kernel sources
 under the CPU emulator).  `eng` is a zippy_amd._binding.Engine; the oracle
 (oracle/) is the checker.  Mirrors the reference's own tests."""
 import hashlib
+import heapq
 import os
 import random
 import struct
@@ -2197,3 +2198,491 @@ def check_crafted_segmented(eng, monkeypatch, small=False):
             assert sts == whole == [status], (sts, whole, status)
     for k in ("ZH_SEG_MIN", "ZH_SEG_BYTES", "ZH_SEG_SETUP", "ZH_SEG"):
         monkeypatch.delenv(k, raising=False)
+
+
+# ---- crafted compress inputs: the encoder at its decision thresholds (stored / fixed / dynamic, the code lengths'
+# run-length coding, emission at its widest, the BestSpeed matcher's edges) ----
+FULL_BLOCK = 4194304
+FRAG = 32768
+S_LEN_FIRST = 267501   # the first block length at which the float32 product and len * 98 // 100 disagree
+S_LEN_SECOND = 600001  # (another one below 1 MiB)
+F_LENGTHS = (0, 1, 2, 3, 4, 5, 6, 14, 15, 16, 2047, 2048, 2049)
+ALL_LEVELS = (-2, -1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9)
+CHAIN_LEVELS = (2, 4, 6, 9)
+GZIP_ONLY = (oracle.dfGzip,)
+CLCL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+R_ZERO_RUNS = (1, 2, 3, 4, 10, 11, 12, 137, 138, 139, 140, 141, 148, 149, 150, 255)
+R_NONZERO_RUNS = tuple(range(1, 14)) + (19,)
+R_HEADS = (0, 63, 64, 127, 128, 191, 192, 255, 256)
+
+
+def stored_threshold(n):
+    """deflate.nim:274-277: a block of n bytes is stored from this many literals on -- a float32 product, truncated"""
+    return int(np.float32(n) * np.float32(0.98))
+
+
+def token_matches(toks):
+    """the reference's u16 token stream -> ([(position in the block, offset, length)], bytes covered)"""
+    out, pos, i = [], 0, 0
+    toks = [int(t) for t in toks]
+    while i < len(toks):
+        if toks[i] & 0x8000:
+            out.append((pos, toks[i + 1], toks[i + 2]))
+            pos += toks[i + 2]
+            i += 3
+        else:
+            pos += toks[i]
+            i += 1
+    return out, pos
+
+
+def _s_input(noise, k, total, tail):
+    """k bytes of noise, then a run of one byte up to `total`, then the second block's bytes"""
+    return noise[:k] + b"\x5a" * (total - k) + tail
+
+
+def _s_find(noise, total, tail, level, target):
+    """the input of _s_input whose first block has exactly `target` literals (the count grows by about one a byte of
+    noise; where it jumps over the target, a short island of noise inside the run makes up the difference)"""
+    block = min(total, FULL_BLOCK)
+    k, seen = target, {}
+    for _ in range(48):
+        k = max(0, min(total, k))
+        if k in seen:
+            break
+        got = oracle.block_tokens(_s_input(noise, k, total, tail), level, 0, block)[3]
+        if got == target:
+            return _s_input(noise, k, total, tail)
+        seen[k] = got
+        k += target - got
+    below = [kk for kk, g in seen.items() if g < target]
+    if below:
+        k = max(below, key=lambda kk: seen[kk])
+        for island in range(1, 64):  # noise bytes in the middle of the run: a few more literals
+            src = bytearray(_s_input(noise, k, total, tail))
+            at = k + (total - k) // 2
+            src[at:at + island] = noise[-island:]
+            if oracle.block_tokens(bytes(src), level, 0, block)[3] == target:
+                return bytes(src)
+    return None
+
+
+def _s_cases(small):
+    rnd = random.Random(9801)
+    noise = rnd.randbytes(FULL_BLOCK)
+    text = synth.corpus_file("alice29.txt")[3000:4000]
+    tail_noise = rnd.randbytes(1000)
+    out = []
+    for level, total in ((1, S_LEN_FIRST), (-1, S_LEN_FIRST), (1, S_LEN_SECOND)):
+        if small and (level, total) != (1, S_LEN_FIRST):
+            continue
+        t = stored_threshold(total)
+        for target in sorted({t - 1, t, t + 1, total * 98 // 100}):
+            out.append(("S/len%d_level%d_nlit%d" % (total, level, target), _s_find(noise, total, b"", level, target),
+                        (level,), GZIP_ONLY))
+    if not small:
+        t = stored_threshold(FULL_BLOCK)
+        for level in (1, 9):
+            for target, tail, kind in ((t - 1, text, "text"), (t - 1, tail_noise, "noise"), (t, text, "text"),
+                                       (t, tail_noise, "noise"), (t + 1, text, "text")):
+                out.append(("S/full_level%d_nlit%d_then_%s" % (level, target, kind),
+                            _s_find(noise, FULL_BLOCK, tail, level, target), (level,), GZIP_ONLY))
+    return out
+
+
+def f_inputs():
+    """Family F: the tiny blocks and the fixed / dynamic border, three kinds of data -> [(name, bytes)]"""
+    text = synth.corpus_file("alice29.txt")[5000:]
+    out = []
+    for n in F_LENGTHS:
+        out.append(("F/text_%d" % n, text[:n]))
+        out.append(("F/one_byte_%d" % n, b"\xe7" * n))
+        out.append(("F/all_bytes_%d" % n, (bytes(range(256)) * 9)[:n]))
+    return out
+
+
+def _f_cases(small):
+    out = []
+    for name, src in f_inputs():
+        if small and not name.endswith(("_0", "_3", "_15", "_2048", "_2049")):
+            continue
+        out.append((name, src, (1, 6, 7, 9), FORMATS))
+        out.append((name + "/gzip", src, (-1,) if small else (-2, -1, 0, 2, 3, 4, 5, 8), GZIP_ONLY))
+    return out
+
+
+def dyadic_input(layout, top, seed):
+    """Family R's builder.  layout: items laid over the byte values from 0 on -- ("z", n): n unused values;
+    ("zto", p): unused values up to value p; ("n", n, l): n values of code length l; ("F",): the fill, single values
+    of distinct lengths that bring the Kraft sum to exactly 1 with the end-of-block symbol at length `top`.  A value
+    of length l occurs 2 ** (top - l) times: the histogram is dyadic, its Huffman lengths are the chosen ones.
+    -> (shuffled bytes, {value: length})"""
+    mass = sum(it[1] << (top - it[2]) for it in layout if it[0] == "n")
+    deficit = (1 << top) - 1 - mass
+    assert deficit >= 0, "layout too heavy"
+    fill = [top - b for b in range(top - 1, -1, -1) if deficit >> b & 1]
+    lens, pos = {}, 0
+    for it in layout:
+        if it[0] == "z":
+            pos += it[1]
+        elif it[0] == "zto":
+            assert pos <= it[1], (pos, it)
+            pos = it[1]
+        elif it[0] == "n":
+            for _ in range(it[1]):
+                lens[pos] = it[2]
+                pos += 1
+        else:
+            assert deficit >= 0 and fill is not None
+            for l in fill:
+                lens[pos] = l
+                pos += 1
+            fill = None
+    assert pos <= 256 and (fill is None or not fill), (pos, fill)
+    body = bytearray()
+    for v, l in lens.items():
+        body += bytes([v]) * (1 << (top - l))
+    body = list(body)
+    random.Random(seed).shuffle(body)
+    return bytes(body), lens
+
+
+def r_layouts():
+    """name -> (layout, length of the end-of-block symbol)"""
+    sep = lambda k: ("n", 1, 8 + k % 2)
+    small_zero, k = [("F",)], 0
+    for z in (1, 2, 3, 4, 10, 11, 12):
+        small_zero += [("z", z), sep(k)]
+        k += 1
+    nonzero = [("F",), ("z", 1)]
+    for k, n in enumerate((2, 3, 4, 5, 6, 7, 8)):
+        nonzero += [("n", n, 9 + k % 2), ("z", 1 + k % 2)]
+    nonzero2 = [("F",), ("z", 2)]
+    for k, n in enumerate((9, 10, 11, 12, 13, 19)):
+        nonzero2 += [("n", n, 9 + k % 2), ("z", 1)]
+    out = {
+        "small_zero_runs": (small_zero, 12),
+        "nonzero_runs_2_8": (nonzero, 12),
+        "nonzero_runs_9_19": (nonzero2, 12),
+        # a run of 150 equal lengths over the whole second group of 64, heads in lanes 63 and 0
+        "nonzero_run_150": ([("F",), ("zto", 40), ("n", 150, 9), ("z", 1), ("n", 1, 8)], 12),
+        "nonzero_run_130_from_63": ([("F",), ("zto", 63), ("n", 130, 9)], 12),
+        "nonzero_run_134": ([("F",), ("zto", 14), ("n", 134, 9), ("z", 2), ("n", 100, 10)], 13),
+        # heads at 63 / 64, 127 / 128, 191 / 192, 255 / 256
+        "heads_at_group_borders": ([("F",), ("zto", 63), ("n", 1, 8), ("zto", 127), ("n", 1, 8), ("zto", 191), ("n", 1, 8),
+                                    ("zto", 255), ("n", 1, 8)], 12),
+        "heads_nonzero_at_group_borders": ([("F",), ("zto", 60), ("n", 3, 9), ("n", 1, 8), ("n", 63, 9), ("n", 1, 8),
+                                            ("n", 63, 10), ("n", 1, 8), ("n", 63, 9), ("n", 1, 8)], 13),
+        "zero_137_from_63": ([("F",), ("zto", 62), ("n", 1, 8), ("z", 137), ("n", 1, 8)], 12),
+        "zero_138_from_64": ([("F",), ("zto", 63), ("n", 1, 8), ("z", 138), ("n", 1, 8)], 12),
+        "zero_139_from_0": ([("z", 139), ("F",)], 12),
+        "zero_140_from_1": ([("n", 1, 8), ("z", 140), ("F",)], 12),
+        "zero_141_to_191": ([("F",), ("zto", 49), ("n", 1, 8), ("z", 141), ("n", 1, 8), ("n", 1, 9)], 12),
+        "zero_148_to_255": ([("F",), ("zto", 106), ("n", 1, 8), ("z", 148), ("n", 1, 8)], 12),
+        "zero_149_to_192": ([("F",), ("zto", 42), ("n", 1, 8), ("z", 149), ("n", 1, 8)], 12),
+        "zero_150": ([("F",), ("zto", 100), ("n", 1, 8), ("z", 150), ("n", 1, 8)], 12),
+        # lengths up to 15 in the header: HCLEN + 4 = 19
+        "length_15": ([("F",), ("z", 3), ("n", 5, 15), ("z", 4), ("n", 7, 14), ("zto", 250), ("n", 4, 15)], 15),
+    }
+    return out
+
+
+def _r_cases(small):
+    out = []
+    for name, (layout, top) in r_layouts().items():
+        src, _ = dyadic_input(layout, top, 77)
+        out.append(("R/" + name, src, (-2,), FORMATS if name == "small_zero_runs" else GZIP_ONLY))
+    # one used byte value: the longest run of zeros there is; the end-of-block symbol has length 1
+    out.append(("R/zero_255", b"\xff" * 3000, (-2,), GZIP_ONLY))
+    out.append(("R/zero_100_155", b"\x64" * 3000, (-2,), GZIP_ONLY))
+    # with matches the lengths cannot be dictated: the oracle says what these reach (tests/test_compress_craft.py)
+    rnd = random.Random(286)
+    far = rnd.randbytes(1500)
+    text = synth.corpus_file("alice29.txt")
+    for level in (1, 9):
+        out.append(("R/far_258_level%d" % level, far + text[:25000] + far + text[25000:26000], (level,), GZIP_ONLY))
+    out.append(("R/period_3", b"abc" * 1000, (1, 9), GZIP_ONLY))
+    out.append(("R/period_3_then_4", b"abc" * 700 + b"wxyz" * 700, (1, 9), GZIP_ONLY))  # the last run: two equal lengths
+    for n in (2500, 2600, 3000, 5000):
+        out.append(("R/run_%d" % n, b"\x11" * n, (1,), GZIP_ONLY))
+    out.append(("R/text_8000", text[40000:48000], (1, 9), GZIP_ONLY))
+    # eight periods, eight distance codes used alike: the distance lengths are 3 eight times, the last run of the array
+    periods = b"".join((rnd.randbytes(p) * 2600)[:2600] for p in (1, 2, 3, 4, 5, 7, 9, 13))
+    out.append(("R/eight_periods", periods, (1, 9), GZIP_ONLY))
+    return out
+
+
+def header_cells(src, level):
+    """What the first block's dynamic header is made of, from the oracle alone: the maximal runs of the concatenated
+    code lengths [(start, value, length)], n_litlen, n_dist and HCLEN + 4 (these three read back from the stream)."""
+    block = min(len(src), FULL_BLOCK)
+    _, lf, df, _ = oracle.block_tokens(src, level, 0, block)
+    lit = list(oracle.huffman_codes(lf, 257, 15)[1])
+    dist = list(oracle.huffman_codes(df, 2, 15)[1])
+    arr = [int(x) for x in lit + dist]
+    runs, i = [], 0
+    while i < len(arr):
+        j = i
+        while j + 1 < len(arr) and arr[j + 1] == arr[i]:
+            j += 1
+        runs.append((i, arr[i], j - i + 1))
+        i = j + 1
+    head = int.from_bytes(oracle.compress(src, level, oracle.dfDeflate)[:4], "little")
+    assert (head >> 1) & 3 == 2, "not a dynamic block"
+    n_litlen, n_dist, hclen4 = ((head >> 3) & 31) + 257, ((head >> 8) & 31) + 1, ((head >> 13) & 15) + 4
+    assert (n_litlen, n_dist) == (len(lit), len(dist))
+    stream = int.from_bytes(oracle.compress(src, level, oracle.dfDeflate)[:16], "little")
+    cl_lens = {sym: (stream >> (17 + 3 * k)) & 7 for k, sym in enumerate(CLCL_ORDER[:hclen4])}
+    return {"runs": runs, "n_litlen": n_litlen, "n_dist": n_dist, "hclen4": hclen4, "lens": arr, "cl_lens": cl_lens}
+
+
+E_RARE = tuple(range(40, 240))   # the rare byte values of E/long_literal_codes
+E_FIRST_AT = 1077                # (no multiple of 512)
+E_SECOND_AT = 3 * FRAG - 700     # the second stretch straddles a 32 KiB fragment border
+
+
+def _e_cases(small):
+    """Long literal codes: eleven dominant byte values whose frequencies double from 150 on, 200 rare values of 16
+    occurrences below them -- a Huffman tree of depth 16, so the reference's length limit runs and lifts one rare
+    value to 13 bits; the other 199, all of 14 or 15 bits, are laid out eight times each, shuffled, as a stretch of
+    1 592 consecutive positions, and that stretch is placed twice.
+    Long match tokens: long_match_input(), the same bytes at level 1 and at level 9."""
+    rnd = random.Random(15)
+    freq = np.zeros(286, np.uint32)
+    for k in range(11):
+        freq[1 + k] = 150 << k
+    freq[list(E_RARE)] = 16
+    freq[256] = 1
+    lens = oracle.huffman_codes(freq, 257, 15)[1]
+    wide = [v for v in E_RARE if lens[v] >= 14]
+    stretch = []
+    for _ in range(8):
+        rnd.shuffle(wide)
+        stretch += wide
+    body = [v for v in E_RARE if lens[v] < 14] * 16
+    for k in range(11):
+        body += [1 + k] * (150 << k)
+    rnd.shuffle(body)
+    src = bytes(body[:E_FIRST_AT]) + bytes(stretch) + bytes(body[E_FIRST_AT:])
+    src = src[:E_SECOND_AT] + bytes(stretch) + src[E_SECOND_AT:]
+    wide_matches = long_match_input()
+    return [("E/long_literal_codes", src, (-2,), FORMATS),
+            ("E/long_match_tokens_level1", wide_matches, (1,), GZIP_ONLY),
+            ("E/long_match_tokens_level9", wide_matches, (9,), GZIP_ONLY)]
+
+
+E_LENGTH_LADDER = ((240, 16), (180, 32), (150, 64), (120, 128), (105, 256), (90, 512))   # (match length, how many)
+
+
+def long_match_input():
+    """Match tokens of 41 bits back to back.  The first fragment: 1 500 bytes of noise, noise up to 16 500, a run of
+    200 equal bytes, then twelve pieces of 200 bytes of the first noise, each a match of its own (length symbol 283:
+    5 extra bits; distance 16 385 or more: 13 extra bits).  At level 1 a piece starts where the matcher probed the
+    noise (its stride grows by one every 32 misses), so the table still holds the place, and the run in front ends in
+    a match, so the next candidate is looked up at the piece's first byte.  Behind it 300 000 bytes of short copies
+    from near by, one fresh byte between two, so that far distances are rare among the distances; and among them
+    long copies from near by whose counts double from one length symbol to the next (E_LENGTH_LADDER), a ladder
+    with symbol 283 at its foot."""
+    rnd = random.Random(1)
+    noise = rnd.randbytes(1500)
+    probes, at, skip = [], 1, 32
+    while at < 1500 - 200:
+        if at >= 8:
+            probes.append(at)
+        at += skip >> 5
+        skip += 1
+    frag = noise + rnd.randbytes(15000) + b"Z" * 200
+    for start in sorted(rnd.sample(probes, 12), reverse=True):   # (descending: no piece continues the one before)
+        frag += noise[start:start + 200]
+    frag += rnd.randbytes(FRAG - len(frag))
+    longs = [length for length, count in E_LENGTH_LADDER for _ in range(count)]
+    rnd.shuffle(longs)
+    every = (300000 - 120000) // 9 // len(longs)
+    out, k = bytearray(rnd.randbytes(400)), 0
+    while len(out) < 300000:
+        k += 1
+        if longs and k % every == 0:
+            length = longs.pop()
+            dist = length + 40
+        else:
+            dist, length = min(len(out), 1 + int(rnd.expovariate(1 / 60.0))), rnd.randrange(4, 9)
+        for _ in range(length):
+            out.append(out[-dist])
+        out.append(rnd.randrange(256))
+    assert not longs
+    return frag + bytes(out[:300000])
+
+
+LENGTH_BASES = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+DISTANCE_BASES = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097,
+                  6145, 8193, 12289, 16385, 24577)
+
+
+def widest_match_stretch(src, level, min_bits=40):
+    """From the oracle's tokens and code lengths of the first block: the longest stretch of matches back to back (each
+    starts where the one before ends) whose tokens -- length code, its extra bits, distance code, its extra bits --
+    all have at least min_bits bits -> (positions covered, tokens, the fewest bits among them)"""
+    toks, lf, df, _ = oracle.block_tokens(src, level, 0, min(len(src), FULL_BLOCK))
+    lit = oracle.huffman_codes(lf, 257, 15)[1]
+    dist = oracle.huffman_codes(df, 2, 15)[1]
+    best, run = (0, 0, 0), []
+    for pos, offset, length in token_matches(toks)[0]:
+        lc = max(i for i, b in enumerate(LENGTH_BASES) if b <= length)
+        dc = max(i for i, b in enumerate(DISTANCE_BASES) if b <= offset)
+        bits = int(lit[257 + lc]) + (0 if lc < 8 or lc == 28 else (lc - 4) // 4) + int(dist[dc]) + max(0, dc // 2 - 1)
+        if bits < min_bits:
+            run = []
+            continue
+        if run and run[-1][0] + run[-1][1] != pos:
+            run = []
+        run.append((pos, length, bits))
+        span = run[-1][0] + run[-1][1] - run[0][0]
+        if span > best[0]:
+            best = (span, len(run), min(r[2] for r in run))
+    return best
+
+
+M_TABLE_BORDERS = tuple(n + d for n in (256, 512, 1024, 2048, 4096, 8192, 16384) for d in (-1, 0, 1)) + (32767, 32768)
+
+
+def _m_cases(small):
+    """Family M: the BestSpeed matcher's edges -- fragment lengths at the table-size borders, tails shorter than 15
+    bytes, position 0 as a candidate, chains of 258-byte matches and where they end, the growing probe stride, a
+    fragment written twice."""
+    rnd = random.Random(1415)
+    html = synth.corpus_file("html")
+    alice = synth.corpus_file("alice29.txt")
+    runs = synth.gen_batch("runs", 1, 3 * FRAG + 70000, first_index=3)[0].tobytes()
+    noise = rnd.randbytes(2 * FRAG + 40000)
+    out = []
+
+    def add(name, src, keep=True):
+        if keep or not small:
+            out.append(("M/" + name, src, (1,), GZIP_ONLY))
+    for i, n in enumerate(M_TABLE_BORDERS):
+        p, q = i % 3, (i + 1) % 3
+        add("frag_%d_text_behind_%d" % (n, p), html[i * 100:i * 100 + p * FRAG + n], n in (255, 257, 4096, 16385))
+        add("frag_%d_runs_behind_%d" % (n, q), runs[i * 64:i * 64 + q * FRAG + n], n in (256, 1025, 16384))
+    for k in range(1, 17):
+        add("tail_%d_behind_1" % k, (alice if k % 2 else runs)[k * 50:k * 50 + FRAG + k], k in (1, 14, 15, 16))
+        add("tail_%d_behind_2" % k, (runs if k % 2 else html)[k * 70:k * 70 + 2 * FRAG + k], k in (2, 15))
+    # the fragment's first four bytes again, at a place whose hash slot is still empty: candidate 0
+    again = b"QRST-first-bytes" + noise[:14] + b"QRST-first-bytes" + alice[:500]
+    add("position_0_first_fragment", again)
+    add("position_0_later_fragment", html[:FRAG] + again)
+    add("run_one_byte_fragment", b"\x07" * FRAG)
+    add("run_period_2_fragment", b"\x07\x70" * (FRAG // 2), False)
+    add("run_one_byte_two_fragments", b"\x33" * (2 * FRAG), False)
+    for gap in (0, 14, 15, 16):   # a run up to `gap` bytes before the fragment's end
+        add("run_ends_%d_before_end" % gap, noise[:20000] + b"\x21" * (FRAG - 20000 - gap) + noise[50000:50000 + gap] + alice[:3000],
+            gap in (0, 15))
+    add("run_crosses_border", alice[:FRAG - 1000] + b"\x42" * 2000 + alice[:4000])
+    add("probe_stride", noise[:40000] + alice[:30000] + noise[40000:70000], False)
+    add("fragment_twice", html[1000:1000 + FRAG] * 2, False)
+    return out
+
+
+_compress_craft_cache = {}
+
+
+def crafted_inputs(small=False):
+    """The families S (stored or not), F (fixed or dynamic, tiny blocks), R (the code lengths' run-length coding),
+    E (emission at its widest) and M (the BestSpeed matcher's edges) -> [(name, bytes, levels, formats)].  What each
+    input reaches is asserted from the oracle alone in tests/test_compress_craft.py.  small: the emulator's subset."""
+    if small not in _compress_craft_cache:
+        cases = _s_cases(small) + _f_cases(small) + _r_cases(small) + _e_cases(small) + _m_cases(small)
+        assert len({c[0] for c in cases}) == len(cases)
+        _compress_craft_cache[small] = cases
+    return list(_compress_craft_cache[small])
+
+
+_oracle_stream_cache = {}
+
+
+def oracle_stream(name, src, level, fmt):
+    """oracle.compress of a crafted input, computed once a process"""
+    key = (name, level, fmt)
+    if key not in _oracle_stream_cache:
+        _oracle_stream_cache[key] = oracle.compress(src, level, fmt, fname_len=0)
+    return _oracle_stream_cache[key]
+
+
+def first_bit_difference(a, b):
+    for i in range(min(len(a), len(b))):
+        if a[i] != b[i]:
+            x = a[i] ^ b[i]
+            return 8 * i + (x & -x).bit_length() - 1
+    return 8 * min(len(a), len(b))
+
+
+def check_crafted_compress(eng, cases, levels=None):
+    """check_compress_identical's conditions for named cases, one batch a (level, container): the device's bytes are
+    the oracle's -- a mismatch names the case and the first bit that differs --, zlib and the oracle's uncompress give
+    the input back, and so does the device's own.  levels: run every case at these instead of its own."""
+    eng.set_gzip_fname_len(0)
+    groups = {}
+    for name, src, own, formats in cases:
+        for level in (levels if levels is not None else own):
+            for fmt in formats:
+                groups.setdefault((level, fmt), []).append((name, src))
+    bad = []
+    for (level, fmt), items in groups.items():
+        outs, sts = eng.compress_batch([s for _, s in items], level, fmt)
+        for (name, src), out, st in zip(items, outs, sts):
+            if st != 0:
+                bad.append((name, level, fmt, "status", st))
+                continue
+            ref = oracle_stream(name, src, level, fmt)
+            if out != ref:
+                bad.append((name, level, fmt, "first differing bit", first_bit_difference(out, ref), "device %d B, oracle %d B"
+                            % (len(out), len(ref))))
+                continue
+            assert zlib.decompress(out, WBITS[fmt]) == src, (name, level, fmt, "zlib")
+            assert oracle.uncompress(out, fmt) == src, (name, level, fmt, "oracle.uncompress")
+        good = [i for i, st in enumerate(sts) if st == 0]
+        back, bsts = eng.uncompress_batch([outs[i] for i in good], fmt)
+        for i, got, st in zip(good, back, bsts):
+            if st != 0 or got != items[i][1]:
+                bad.append((items[i][0], level, fmt, "device uncompress", st))
+    assert not bad, bad
+
+
+def check_crafted_contract(eng, cases, margin=1.02):
+    """the same inputs under the opt-in parallel parse at level 1: valid streams that zlib and the oracle decode to
+    the input (the header writer is shared with contract mode); margin: the batch's size against the oracle's, as
+    check_parallel_parse takes it (None: not compared) -> (device bytes, oracle bytes)"""
+    eng.set_gzip_fname_len(0)
+    eng.set_l1_parse(1)
+    try:
+        outs, sts = eng.compress_batch([c[1] for c in cases], 1, oracle.dfGzip)
+    finally:
+        eng.set_l1_parse(-1)
+    dev = ref = 0
+    for (name, src, _, _), out, st in zip(cases, outs, sts):
+        assert st == 0, (name, st)
+        assert zlib.decompress(out, 31) == src, (name, "zlib")
+        assert oracle.uncompress(out, oracle.dfGzip) == src, (name, "oracle.uncompress")
+        dev += len(out)
+        ref += len(oracle_stream(name, src, 1, oracle.dfGzip))
+    if margin is not None:
+        assert dev <= margin * ref, "parallel parse: %d B against the oracle's %d B" % (dev, ref)
+    return dev, ref
+
+
+def block_types(src, level):
+    """BTYPE of every deflate block the oracle writes for src (a stored block of more than 65 535 bytes counts once
+    a piece) and the literals the matcher left in the first one"""
+    out, idx = oracle.compress_blocks(src, level, oracle.dfDeflate, FULL_BLOCK)
+    assert out == oracle.compress(src, level, oracle.dfDeflate)
+    types = [(int.from_bytes(out[b >> 3:(b >> 3) + 2], "little") >> (b & 7)) >> 1 & 3 for b, _ in idx[:-1]]
+    return types, len(src) if level == 0 else oracle.block_tokens(src, level, 0, min(len(src), FULL_BLOCK))[3]
+
+
+def huffman_depth(f):
+    """depth of the unlimited Huffman tree of a histogram"""
+    h = [(int(x), 0) for x in f if x]
+    heapq.heapify(h)
+    while len(h) > 1:
+        a, b = heapq.heappop(h), heapq.heappop(h)
+        heapq.heappush(h, (a[0] + b[0], max(a[1], b[1]) + 1))
+    return h[0][1]

@@ -383,3 +383,29 @@ def test_emu_crafted_streams(eng, inflate_mode):
 
 def test_emu_crafted_streams_segmented(eng, monkeypatch):
     pc.check_crafted_segmented(eng, monkeypatch, small=True)
+
+
+def _family(small, letters):
+    return [c for c in pc.crafted_inputs(small) if c[0][0] in letters]
+
+
+def test_emu_crafted_compress(eng):
+    """the small subset of parity_cases.crafted_inputs(): every cell of the dynamic header's run-length coding, the
+    stored threshold at 267 501 bytes, the fixed / dynamic border, 15-bit literals, the matcher's edges"""
+    pc.check_crafted_compress(eng, pc.crafted_inputs(small=True))
+
+
+def test_emu_crafted_chain_levels(eng):
+    """(the F inputs of the small subset carry levels -1 and 9 themselves)"""
+    cases = [(name, src, levels, pc.GZIP_ONLY) for name, src, levels, _ in _family(True, "SM")]
+    pc.check_crafted_compress(eng, cases, levels=(-1, 9))
+
+
+def test_emu_crafted_matcher_tokens(eng):
+    for name, src, _, _ in _family(True, "M"):
+        pc.check_tokens(eng, src, 1)
+
+
+def test_emu_crafted_contract(eng):
+    pc.check_crafted_contract(eng, _family(True, "R"), margin=None)
+    pc.check_parallel_parse(eng, [c[1] for c in _family(True, "M")])

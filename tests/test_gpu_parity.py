@@ -554,3 +554,29 @@ def test_gpu_one_gib_stream_decodes_segment_wise():
     assert rand["trailer_ok"] and rand["decoded_segment_wise"] and min(rand["uncompress_s"]) < 0.05, rand
     lits = gpu_big_buffer.run(1024, level=-2, with_oracle=False, with_zlib=False)
     assert lits["trailer_ok"] and min(lits["uncompress_s"]) < 0.2, lits
+
+
+def _family(letters, max_len=None):
+    return [c for c in pc.crafted_inputs() if c[0][0] in letters and (max_len is None or len(c[1]) <= max_len)]
+
+
+@pytest.mark.parametrize("family", ["S", "F", "R", "E", "M"])
+def test_gpu_crafted_compress(eng, family):
+    """parity_cases.crafted_inputs(): the encoder at its decision thresholds, byte for byte against the oracle"""
+    pc.check_crafted_compress(eng, _family(family))
+
+
+def test_gpu_crafted_chain_levels(eng):
+    cases = [(name, src, levels, pc.GZIP_ONLY) for name, src, levels, _ in _family("SFM", 300000) if not name.endswith("/gzip")]
+    pc.check_crafted_compress(eng, cases, levels=pc.CHAIN_LEVELS)
+
+
+def test_gpu_crafted_matcher_tokens(eng):
+    for name, src, _, _ in _family("M"):
+        pc.check_tokens(eng, src, 1)
+
+
+def test_gpu_crafted_contract(eng):
+    pc.check_crafted_contract(eng, _family("R"), margin=None)
+    dev, ref = pc.check_parallel_parse(eng, [c[1] for c in _family("M")])
+    print("parallel parse over the M inputs: %d B against the oracle's %d B (%.4f)" % (dev, ref, dev / ref))

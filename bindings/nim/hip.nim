@@ -369,6 +369,93 @@ proc hipWriteZipArchive*[ZipArchive](archive: ZipArchive): string {.raises: [Zip
                               DefaultCompression.cint, p.addr, n.addr, st.addr)
   take(p, n, if rc != 0: rc else: st.cint)
 
+import std/os
+
+# ---- ZipArchive.open (src/zippy/ziparchives_v1.nim:105-349 openStreamImpl) ----
+type
+  HipZipV1Entry* = object
+    path*, contents*: string            # the table's key (toUnixPath of the name), the verified contents
+    isDirectory*, inDirectory*: bool    # external attributes & 0x10; a central record named the entry
+    unixMode*: uint32                   # external attributes shr 16 (0 without a central record)
+    dosTime*, dosDate*: uint16          # the local record's words (:128-129)
+
+proc zh_zip_read_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, nZip: csize_t,
+                       readers: ptr pointer, statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_zip_entry_v1(reader: pointer, i: csize_t, dosTime, dosDate: ptr uint16,
+                     inDirectory: ptr cint): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipReadZipArchives*(images: openArray[string]): seq[seq[HipZipV1Entry]] {.raises: [ZippyError].} =
+  ## openStreamImpl (ziparchives_v1.nim:105-329) for many images in one call: every image walked from byte 0, every
+  ## entry decoded, its CRC-32 and its length verified on the device; an image's entries are its table's keys in
+  ## insertion order.  Raises on the first image whose status is not zero, as the reference would on that stream
+  ## (without the half-filled table the reference leaves behind its exception).
+  let n = images.len
+  if n == 0: return
+  var
+    ptrs = newSeq[pointer](n)
+    lens = newSeq[csize_t](n)
+    readers = newSeq[pointer](n)
+    sts = newSeq[int32](n)
+  for i, s in images:
+    ptrs[i] = if s.len > 0: s[0].unsafeAddr else: nil
+    lens[i] = s.len.csize_t
+  let rc = zh_zip_read_batch(engine(), ptrs[0].addr, lens[0].addr, n.csize_t, readers[0].addr, sts[0].addr)
+  try:
+    if rc != 0: raise newException(ZippyError, $zh_strerror(rc))
+    for st in sts:
+      if st != 0: raise newException(ZippyError, $zh_strerror(st.cint))
+    result = newSeq[seq[HipZipV1Entry]](n)
+    for t in 0 ..< n:
+      for i in 0 ..< zh_zip_num_entries(readers[t]).int:
+        var e: ZhZipEntry
+        var data: pointer
+        var len: csize_t
+        var st: int32
+        var inDir: cint
+        var item: HipZipV1Entry
+        discard zh_zip_entry_at(readers[t], i.csize_t, e.addr)
+        discard zh_zip_entry_data(readers[t], i.csize_t, data.addr, len.addr, st.addr)
+        discard zh_zip_entry_v1(readers[t], i.csize_t, item.dosTime.addr, item.dosDate.addr, inDir.addr)
+        item.isDirectory = e.isDirectory != 0
+        item.inDirectory = inDir != 0
+        item.unixMode = e.unixMode
+        item.path = newString(e.pathLen.int)
+        if e.pathLen > 0: copyMem(item.path[0].addr, e.path, e.pathLen.int)
+        item.contents = newString(len.int)
+        if len > 0: copyMem(item.contents[0].addr, data, len.int)
+        result[t].add item
+  finally:
+    for r in readers:
+      if r != nil: zh_zip_close(r)
+
+proc hipDosTime*(dosTime, dosDate: uint16): Time =
+  ## ziparchives_v1.nim:161-179, field for field: the caller's zone; a Defect for day or month 0, as there
+  let
+    seconds = (dosTime and 0b0000000000011111).int * 2
+    minutes = ((dosTime shr 5) and 0b0000000000111111).int
+    hours = ((dosTime shr 11) and 0b0000000000011111).int
+    days = (dosDate and 0b0000000000011111).int
+    months = ((dosDate shr 5) and 0b0000000000001111).int
+    years = ((dosDate shr 9) and 0b0000000001111111).int
+  if seconds <= 59 and minutes <= 59 and hours <= 23:
+    result = initDateTime(days.MonthdayRange, months.Month, years + 1980, hours.HourRange, minutes.MinuteRange,
+                          seconds.SecondRange, local()).toTime()
+
+proc hipPermissions*(unixMode: uint32): set[FilePermission] =
+  ## extractPermissions (ziparchives_v1.nim:84-103) of externalFileAttr shr 16
+  if defined(windows) or unixMode == 0:
+    result = {fpUserRead, fpUserWrite, fpGroupRead, fpGroupWrite, fpOthersRead}
+  else:
+    if (unixMode and 0o00400) != 0: result.incl fpUserRead
+    if (unixMode and 0o00200) != 0: result.incl fpUserWrite
+    if (unixMode and 0o00100) != 0: result.incl fpUserExec
+    if (unixMode and 0o00040) != 0: result.incl fpGroupRead
+    if (unixMode and 0o00020) != 0: result.incl fpGroupWrite
+    if (unixMode and 0o00010) != 0: result.incl fpGroupExec
+    if (unixMode and 0o00004) != 0: result.incl fpOthersRead
+    if (unixMode and 0o00002) != 0: result.incl fpOthersWrite
+    if (unixMode and 0o00001) != 0: result.incl fpOthersExec
+
 # ---- createZipArchive for many tables per call (src/zippy/ziparchives.nim:455-634) ----
 proc zh_zip_create_batch(ctx: ZhCtx, entries: ptr ZhZipNewEntry, first: ptr csize_t, nZip: csize_t,
                          level: cint, dsts: ptr pointer, dstLens: ptr csize_t,

@@ -80,7 +80,12 @@ enum {
   ZH_ERR_TAR_NAME = 39,           /* tarballs_v1.nim:223-227 (splitPath tail >= 100 bytes) */
   /* v1 zip writer (zh_zip_write_batch): ziparchives_v1.nim writeZipArchive */
   ZH_ERR_ZIP_EMPTY = 40,          /* ziparchives_v1.nim:375-376 */
-  ZH_ERR_ZIP_TOO_LARGE = 41       /* a count, length or offset that does not fit its 16- / 32-bit field */
+  ZH_ERR_ZIP_TOO_LARGE = 41,      /* a count, length or offset that does not fit its 16- / 32-bit field */
+  /* v1 zip reader (zh_zip_read_batch): ziparchives_v1.nim openStreamImpl */
+  ZH_ERR_ZIP_DATA_DESCRIPTOR = 42, /* ziparchives_v1.nim:138-142 */
+  ZH_ERR_ZIP_DEFLATE64 = 43,       /* ziparchives_v1.nim:144-148 (flag bit 3) */
+  ZH_ERR_ZIP_SIZE = 44,            /* ziparchives_v1.nim:213-217 */
+  ZH_ERR_ZIP_OPEN = 45             /* ziparchives_v1.nim:110-111 failOpen: :282-293, :328-329 */
 };
 
 /* Engine context: one GPU, one HIP stream, reusable scratch. Thread-compatible
@@ -408,6 +413,47 @@ const void *zh_zip_data(const zh_zip_reader *reader, size_t *len);
  * an entry whose directory understated its size: that one was decoded again on its own and has a buffer of its own
  * (the reader's as well).  A reader made by zh_zip_open, a NULL pointer or an index out of range: ZH_ERR_ARGUMENT. */
 int zh_zip_entry_data(const zh_zip_reader *reader, size_t i, const void **data, size_t *len, int32_t *status);
+
+/* ZipArchive.open(stream / path) -- ziparchives_v1.nim:105-349 openStreamImpl -- for n_zip images per call.  This is
+ * not openZipArchive under another name: it never looks for the end record.  It starts at byte 0 and walks the whole
+ * image record by record -- local headers with their data, central records, the end record --, decoding and verifying
+ * every entry on the way.  statuses[t] is the outcome of openStreamImpl on image t alone, the first check that fails:
+ *   at `pos` (0 at first): pos + 4 > len: ZH_ERR_ARCHIVE_EOF (failEOF); a signature that is none of the three:
+ *     ZH_ERR_ZIP_OPEN (:328-329);
+ *   50 4b 03 04 (:120-225): pos + 30 > len: ZH_ERR_ARCHIVE_EOF; flag bit 2: ZH_ERR_ZIP_DATA_DESCRIPTOR; flag bit 3:
+ *     ZH_ERR_ZIP_DEFLATE64; a method outside {0, 8}: ZH_ERR_ZIP_METHOD; name + extra, then the data (the 32-bit
+ *     compressed size) beyond the image: ZH_ERR_ARCHIVE_EOF; method 8: the status zh_uncompress_batch(.., ZH_DF_DEFLATE)
+ *     gives those bytes; the CRC-32 of the contents against the header's: ZH_ERR_ZIP_CRC; only then their length
+ *     against the header's uncompressed size: ZH_ERR_ZIP_SIZE.  The key is the name with every \ replaced by /
+ *     (toUnixPath); contents[key] = entry replaces the value of an earlier equal key and keeps that key's place;
+ *   50 4b 01 02 (:227-293): pos + 46 > len, then name + extra + comment beyond the image: ZH_ERR_ARCHIVE_EOF; the RAW
+ *     name is not a key inserted so far: ZH_ERR_ZIP_OPEN; else the entry's is_directory = external attributes & 0x10,
+ *     unix_mode = external attributes >> 16 (a later central record of the same name overwrites both);
+ *   50 4b 05 06 (:295-326): pos + 22 > len, then the comment beyond the image: ZH_ERR_ARCHIVE_EOF; else ZH_OK, and
+ *     nothing behind it is looked at.
+ * readers[t] is NULL unless statuses[t] is ZH_OK (the reference leaves a half-filled table behind its exception; the
+ * library returns none).  A reader's entries are the table's keys in first-insertion order, each with the value of
+ * its last local record: zh_zip_num_entries / zh_zip_entry_at (header_offset, both sizes and the CRC of that local
+ * record; is_directory and unix_mode as above, 0 without a central record; path = the key) / zh_zip_find (on the key) /
+ * zh_zip_data / zh_zip_entry_data (always ZH_OK with the bytes, a directory's too: v1 keeps them) / zh_zip_close work
+ * on it; zh_zip_extract_batch returns ZH_ERR_ARGUMENT (every entry is extracted already).  The image stays borrowed
+ * until zh_zip_close.
+ * The return value is a call-level error only: NULL arrays, an image that is NULL with a non-zero length, a missing
+ * ctx, allocation, device; images that could hold more than 2^32 - 2 walk nodes (signatures: one in four bytes, plus
+ * one node an image) or records in one call: ZH_ERR_ARGUMENT before anything is launched.  A bad image never changes
+ * another image's reader, status or bytes; n_zip == 0 launches nothing.
+ * The images are uploaded once; a signature scan over every image byte, the walk over its hits (pointer doubling),
+ * every header check, the copies of stored entries and every CRC-32 / size verdict run on the device, and ONE
+ * uncompress plan decodes every deflated local record of the call from its place in the uploaded image; the host
+ * inserts the tables (csrc/zh_zip_read_batch.hip). */
+int zh_zip_read_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n_zip,
+                      zh_zip_reader **readers, int32_t *statuses);
+/* Entry i of a reader made by zh_zip_read_batch: the raw DOS time and date words of its local record (:128-129; the
+ * conversion to times.Time, :161-179, is in the caller's zone and stays with the caller) and whether a central record
+ * named the entry (without one, permissions stay unset).  Any other reader, a NULL pointer or an index out of range:
+ * ZH_ERR_ARGUMENT. */
+int zh_zip_entry_v1(const zh_zip_reader *reader, size_t i, uint16_t *dos_time, uint16_t *dos_date,
+                    int *in_directory);
 
 /* ------------------------------------------------------------------ *
  * Tarballs: extractAll of src/zippy/tarballs.nim *

@@ -113,6 +113,10 @@ _SIGS = {
                                         _c.POINTER(_c.c_int32)]),
     "zh_zip_open_all_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                          _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int32)]),
+    "zh_zip_read_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                     _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int32)]),
+    "zh_zip_entry_v1": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_uint16), _c.POINTER(_c.c_uint16),
+                                   _c.POINTER(_c.c_int)]),
     "zh_zip_data": (_c.c_void_p, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
     "zh_zip_entry_data": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
                                      _c.POINTER(_c.c_int32)]),
@@ -291,6 +295,12 @@ class ZipReader:
         if st:
             return None
         return _c.string_at(data, n) if n else b""
+
+    def entry_v1(self, i):
+        """zh_zip_entry_v1: (dos_time, dos_date, in_directory) of entry i (a reader made by Engine.read_zips)"""
+        t, d, in_dir = _c.c_uint16(), _c.c_uint16(), _c.c_int()
+        self.engine._check(self.engine.lib.zh_zip_entry_v1(self._h, i, _c.byref(t), _c.byref(d), _c.byref(in_dir)))
+        return t.value, d.value, in_dir.value
 
     def find(self, path):
         raw = path.encode("utf-8", "surrogateescape")
@@ -629,12 +639,20 @@ class Engine:
     def open_zips(self, images):
         """zh_zip_open_all_batch: many archives opened and extracted in one call -> (readers, statuses); readers[t]
         is a ZipReader with .data / .entry_status(i) / .contents(i), or None where the archive did not open."""
+        return self._open_zips(self.lib.zh_zip_open_all_batch, images)
+
+    def read_zips(self, images):
+        """zh_zip_read_batch: ZipArchive.open (ziparchives_v1.nim:105-349) of every image in one call -> (readers,
+        statuses); readers[t] is a ZipReader with .data / .contents(i) / .entry_v1(i), or None unless statuses[t] is 0."""
+        return self._open_zips(self.lib.zh_zip_read_batch, images)
+
+    def _open_zips(self, fn, images):
         images = [bytes(b) for b in images]
         n = len(images)
         srcs = (_c.c_void_p * n)(*[_c.cast(_c.c_char_p(b), _c.c_void_p) if b else None for b in images])
         lens = (_c.c_size_t * n)(*[len(b) for b in images])
         handles, sts = (_c.c_void_p * n)(), (_c.c_int32 * n)()
-        self._check(self.lib.zh_zip_open_all_batch(self._h, srcs, lens, n, handles, sts))
+        self._check(fn(self._h, srcs, lens, n, handles, sts))
         return [ZipReader(self, b, h) if h else None for b, h in zip(images, handles)], list(sts)
 
     def create_zip(self, entries, dos_time=0, dos_date=0):

@@ -112,6 +112,15 @@ def writeZipArchive(entries, level=DefaultCompression):
     return engine().write_zip(entries, level)
 
 
+def readZipArchives(images):
+    """ziparchives_v1.nim:105-349 ZipArchive.open for many images in one call (zh_zip_read_batch): every image walked
+    from byte 0, every entry decoded and verified on the device -> a list of readers, in order, with .entries (the
+    table's keys in insertion order), .contents(i), .entry_v1(i).  Raises ZippyError on the first image that failed."""
+    eng = engine()
+    readers, sts = eng.read_zips(images)
+    return eng._raise_first(readers, sts)
+
+
 def crc32(src):
     return engine().crc32(src)
 

@@ -122,6 +122,10 @@ extern "C" const char* zh_strerror(int status) {
     case ZH_ERR_TAR_NAME: return "File name too long, must be < 100 characters";
     case ZH_ERR_ZIP_EMPTY: return "Zip archive has no contents";
     case ZH_ERR_ZIP_TOO_LARGE: return "Zip archive too large: a count, length or offset does not fit its field (no zip64)";
+    case ZH_ERR_ZIP_DATA_DESCRIPTOR: return "Unsupported zip archive, data descriptor bit set";
+    case ZH_ERR_ZIP_DEFLATE64: return "Unsupported zip archive, uses deflate64";
+    case ZH_ERR_ZIP_SIZE: return "Unexpected error verifying uncompressed size";
+    case ZH_ERR_ZIP_OPEN: return "Unexpected error opening zip archive";
     default: return "Unknown status";
   }
 }

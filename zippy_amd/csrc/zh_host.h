@@ -1,11 +1,12 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in eleven files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in twelve files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
 // wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
 // zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks) the batch writers
-// zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_zip_open_batch.hip (whose kernels
-// sit next to their host code; zh_walk.h and zh_gather.h hold what they share).  No compute happens on the host.
+// zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_zip_open_batch.hip /
+// zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h, zh_gather.h and zh_zip_dev.h hold what
+// they share).  No compute happens on the host.
 #pragma once
 #include <algorithm>
 #include <cstdio>

@@ -115,6 +115,10 @@ struct zh_zip_reader {
   std::vector<size_t> e_len;
   std::vector<int32_t> e_status;
   std::vector<void*> redone;  // entries decoded on their own (a directory that understates a size)
+  // a reader made by zh_zip_read_batch (ziparchives_v1.nim): the local records' DOS words, who was in the directory
+  bool v1 = false;
+  std::vector<uint16_t> v1_time, v1_date;
+  std::vector<uint8_t> v1_in_directory;
   ~zh_zip_reader() {
     free(block);
     for (void* p : redone) free(p);
@@ -176,6 +180,23 @@ void zh_zip_reader_set_data(zh_zip_reader* r, void* block, size_t block_len, con
       r->e_data[i] = block ? (const uint8_t*)block + off[i] : nullptr;
     }
   }
+}
+
+void zh_zip_reader_set_v1(zh_zip_reader* r, const uint16_t* dos_time, const uint16_t* dos_date,
+                          const uint8_t* in_directory) {
+  const size_t n = r->records.size();
+  r->v1 = true;
+  r->v1_time.assign(dos_time, dos_time + n);
+  r->v1_date.assign(dos_date, dos_date + n);
+  r->v1_in_directory.assign(in_directory, in_directory + n);
+}
+extern "C" int zh_zip_entry_v1(const zh_zip_reader* r, size_t i, uint16_t* dos_time, uint16_t* dos_date,
+                               int* in_directory) {
+  if (!r || !r->v1 || i >= r->records.size() || !dos_time || !dos_date || !in_directory) return ZH_ERR_ARGUMENT;
+  *dos_time = r->v1_time[i];
+  *dos_date = r->v1_date[i];
+  *in_directory = r->v1_in_directory[i];
+  return ZH_OK;
 }
 
 extern "C" const void* zh_zip_data(const zh_zip_reader* r, size_t* len) {
@@ -365,7 +386,7 @@ extern "C" int zh_zip_find(const zh_zip_reader* r, const char* path, size_t path
 // deflated ones go through one batched decode; every result's CRC-32 comes from the GPU.
 extern "C" int zh_zip_extract_batch(zh_ctx* ctx, const zh_zip_reader* r, const size_t* indices, size_t n,
                                     void** dsts, size_t* dst_lens, int32_t* statuses) {
-  if (!ctx || !r || (n && (!indices || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
+  if (!ctx || !r || r->v1 || (n && (!indices || !dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
   const Image& im = r->img;
   std::vector<size_t> deflated, stored;  // positions in the request
   std::vector<const void*> d_src, s_src;

@@ -1,0 +1,837 @@
+// Reading zip archives the v1 way: ZipArchive.open (src/zippy/ziparchives_v1.nim:105-349 openStreamImpl) for many
+// images a call.  The walk starts at byte 0 of an image and goes from record to record over the image's own bytes, so
+// the candidates of the walk are found first:
+//   zh_zipr_scan_kernel   every 16-byte chunk of the upload is read once a pass (count, then write): the positions
+//                         whose four bytes are one of the three signatures and lie inside ONE image are the hits,
+//                         sorted by position
+//   zh_zipr_ranges_kernel per image: its range of hits; an image whose byte 0 is no hit is settled here
+//   zh_zipr_next_kernel   next[h] for every hit as if a record started there, its target found among the image's hits
+//                         by binary search; a record that fails, an end record and a target that is no hit end a chain
+//   zh_walk_double_kernel the hits reachable from an image's byte 0 ARE its records (zh_walk.h)
+//   zh_walk_scan_*        every record's ordinal in walk order, the list of records
+//   zh_zipr_parse_kernel  one wave per record: the checks of the loop body in their order; one fixed-size record
+//   zh_zip_reduce_kernel  per image: the first record that failed
+//   (host)                the tables from the records in walk order (toUnixPath, replacement, the central records'
+//                         lookup); the layout of the output; ONE uncompress plan over every deflated local record of
+//                         the call, its sources in place in the uploaded images; the first failure in walk order
+//   zh_zipr_finish_kernel stored entries copied image -> slot; every record's CRC-32, then its length, held against
+//                         its header
+// The host parses no header byte, compares no CRC and copies no entry.
+//
+// Scratch: 8 bytes per hit (the list), 20 per node of the walk (a hit, or an image's END node), 4 per 16 KiB of the
+// upload (the scan's group sums).  Nothing is kept per image byte.
+//
+// Every image sits at an 8-byte aligned offset of ONE allocation that ends with 512 spare bytes (the plan reads whole
+// aligned words around a source, the stored copy and the scan aligned 16-byte chunks).  The bytes between two images
+// and behind the last are stale: a signature there, or one that begins in an image's tail and ends in the padding or
+// the next image, is no hit.
+#include <unordered_map>
+
+#include "zh_host.h"
+#include "zh_gather.h"
+#include "zh_walk.h"
+#include "zh_zip_dev.h"
+
+namespace {
+
+constexpr uint32_t kLocalSig = 0x04034b50u, kCentralSig = 0x02014b50u, kEndSig = 0x06054b50u;
+constexpr uint64_t kSlice = 32768;  // bytes of a stored entry a wave copies at most
+// the scan: a lane reads 16 bytes, a wave 1024 contiguous bytes, a workgroup 4096 a step, kScanSteps steps
+constexpr uint32_t kScanSteps = 4;
+constexpr uint64_t kScanStepBytes = 256 * 16, kScanGroupBytes = kScanStepBytes * kScanSteps;
+enum : uint8_t { kKindLocal = 1, kKindCentral = 2, kKindEnd = 3 };
+
+struct ZhZrImg {
+  uint64_t up_off, len;  // where the image lies in the upload buffer
+};
+
+// What stands at a position if a record starts there: the checks of openStreamImpl's loop body up to the decoder
+// (:115-200, :228-269, :296-319) in their order.  status: the first that failed; next: the position behind the record.
+struct ZhZrHead {
+  uint64_t next, name_off, data_off;
+  uint32_t name_len, csize, usize, crc, external;
+  int32_t status;
+  uint16_t dos_time, dos_date;
+  uint8_t kind, method;
+};
+
+// One reached record, for the host
+struct ZhZrRec {
+  uint64_t pos, name_off, data_off;  // in the image
+  uint32_t name_len, csize, usize, crc, external;
+  int32_t status, succ_status;  // its own checks; what the walk finds where the next record should start
+  uint16_t dos_time, dos_date;
+  uint8_t kind, method, backslash, pad;
+};
+
+// One local record that is verified, for zh_zipr_finish_kernel
+struct ZhZrFin {
+  uint64_t src, dst, len;  // a stored entry: len bytes from upload buffer + src to output buffer + dst
+  uint32_t want_crc, want_len;
+  uint32_t deflated;  // 1: result `idx` of the plan; 0: stored entry `idx` of the checksum launch
+  uint32_t idx;
+};
+struct ZhZrFinTask {
+  uint64_t lo, hi;  // bytes [lo, hi) of the entry's data
+  uint32_t entry, first;
+};
+
+// the last image whose up_off <= p
+__device__ __forceinline__ uint32_t find_img(const ZhZrImg* __restrict__ imgs, uint32_t n_img, uint64_t p) {
+  uint32_t lo = 0, hi = n_img;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (imgs[mid].up_off <= p)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+// the first of hits[lo, hi) that is >= p (hi if there is none)
+__device__ __forceinline__ uint32_t lower_bound(const uint64_t* __restrict__ hits, uint32_t lo, uint32_t hi, uint64_t p) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (hits[mid] < p)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ bool is_signature(uint32_t v) {
+  return (v & 0xffffu) == 0x4b50u && (v == kLocalSig || v == kCentralSig || v == kEndSig);
+}
+
+// The 16 positions of the chunk at `at` (a multiple of 16) as a mask of hits: x = the chunk's words, nw = the word
+// behind it.  A candidate counts only inside one image.
+__device__ __forceinline__ uint32_t chunk_hits(const Chunk16& x, uint32_t nw, uint64_t at,
+                                               const ZhZrImg* __restrict__ imgs, uint32_t n_img) {
+  const uint32_t w[5] = {x.w[0], x.w[1], x.w[2], x.w[3], nw};
+  uint32_t m = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 16; j++)
+    if (is_signature(__builtin_amdgcn_alignbyte(w[(j >> 2) + 1], w[j >> 2], j & 3))) m |= 1u << j;
+  for (uint32_t rest = m; rest; rest &= rest - 1) {  // (rare: a handful a record)
+    const uint32_t j = (uint32_t)__ffs(rest) - 1;
+    const ZhZrImg g = imgs[find_img(imgs, n_img, at + j)];
+    if (at + j + 4 > g.up_off + g.len) m &= ~(1u << j);
+  }
+  return m;
+}
+
+// a record's header at image position pos (p = the image, len its length); see ZhZrHead
+__device__ __forceinline__ ZhZrHead read_head(const uint8_t* __restrict__ p, uint64_t len, uint64_t pos) {
+  ZhZrHead h{};
+  const uint8_t* __restrict__ q = p + pos;
+  const uint32_t sig = ld32(q);  // (a hit: its four bytes are inside the image)
+  if (sig == kLocalSig) {
+    h.kind = kKindLocal;
+    if (pos + 30 > len) {
+      h.status = ZH_ERR_ARCHIVE_EOF;
+      return h;
+    }
+    const uint32_t flags = ld16(q + 6), method = ld16(q + 8);
+    h.dos_time = (uint16_t)ld16(q + 10);
+    h.dos_date = (uint16_t)ld16(q + 12);
+    h.crc = ld32(q + 14);
+    h.csize = ld32(q + 18);
+    h.usize = ld32(q + 22);
+    h.name_len = ld16(q + 26);
+    h.method = (uint8_t)method;
+    h.name_off = pos + 30;
+    h.data_off = h.name_off + h.name_len + ld16(q + 28);
+    h.next = h.data_off + h.csize;
+    if (flags & 4u)
+      h.status = ZH_ERR_ZIP_DATA_DESCRIPTOR;
+    else if (flags & 8u)
+      h.status = ZH_ERR_ZIP_DEFLATE64;
+    else if (method != 0 && method != 8)
+      h.status = ZH_ERR_ZIP_METHOD;
+    else if (h.data_off > len || h.next > len)
+      h.status = ZH_ERR_ARCHIVE_EOF;
+  } else if (sig == kCentralSig) {
+    h.kind = kKindCentral;
+    if (pos + 46 > len) {
+      h.status = ZH_ERR_ARCHIVE_EOF;
+      return h;
+    }
+    h.name_len = ld16(q + 28);
+    h.external = ld32(q + 38);
+    h.name_off = pos + 46;
+    h.next = h.name_off + h.name_len + ld16(q + 30) + ld16(q + 32);
+    if (h.next > len) h.status = ZH_ERR_ARCHIVE_EOF;
+  } else {
+    h.kind = kKindEnd;
+    if (pos + 22 > len) {
+      h.status = ZH_ERR_ARCHIVE_EOF;
+      return h;
+    }
+    h.next = pos + 22 + ld16(q + 20);
+    if (h.next > len) h.status = ZH_ERR_ARCHIVE_EOF;
+  }
+  return h;
+}
+
+}  // namespace
+
+// The signature scan over the upload's bytes [0, n_bytes), n_bytes a multiple of 16.  A workgroup covers
+// kScanGroupBytes in kScanSteps steps; in a step a wave reads 1024 contiguous bytes, one aligned 16-byte load a lane.
+// The three bytes behind a lane's chunk come from its neighbour's registers (lane 63: one more word, of a line the
+// wave's next step reads anyway).  WRITE = false: sums[group] = the group's hits.  WRITE = true: sums[group] = the
+// hits before the group (sums[groups] = all hits); the positions go to hits[] in ascending order, and only the groups
+// that hold a hit read their bytes a second time.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void zh_zipr_scan_kernel(const uint8_t* __restrict__ d_in, uint64_t n_bytes,
+                                                           const ZhZrImg* __restrict__ imgs, uint32_t n_img,
+                                                           uint32_t* __restrict__ sums, uint64_t* __restrict__ hits) {
+  const uint64_t base = (uint64_t)blockIdx.x * kScanGroupBytes + 16ull * threadIdx.x;
+  uint32_t carry = WRITE ? sums[blockIdx.x] : 0u, count = 0;
+  if (WRITE && sums[blockIdx.x + 1] == carry) return;  // no hit in this group: its bytes are not read again
+#pragma unroll
+  for (uint32_t step = 0; step < kScanSteps; step++) {
+    const uint64_t at = base + step * kScanStepBytes;
+    const bool live = at < n_bytes;
+    Chunk16 x{};
+    if (live) x = *reinterpret_cast<const Chunk16*>(d_in + at);
+    uint32_t nw = (uint32_t)__shfl_down(x.w[0], 1);
+    if (live && zh_lane() == 63) nw = *reinterpret_cast<const uint32_t*>(d_in + at + 16);  // (the spare bytes at the latest)
+    const uint32_t m = live ? chunk_hits(x, nw, at, imgs, n_img) : 0u;
+    if (!WRITE) {
+      count += (uint32_t)__popc(m);
+    } else {
+      uint32_t total;
+      uint32_t k = carry + block_scan((uint32_t)__popc(m), &total);
+      for (uint32_t rest = m; rest; rest &= rest - 1) hits[k++] = at + (uint32_t)__ffs(rest) - 1;
+      carry += total;
+    }
+  }
+  if (!WRITE) {
+    uint32_t total;
+    (void)block_scan(count, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+  }
+}
+
+// Per image: ranges[2t .. 2t + 1] = its hits; start[t] = ZH_OK when its byte 0 is a hit, else what the loop's first
+// trip says (:115-116, :328-329)
+__global__ __launch_bounds__(256) void zh_zipr_ranges_kernel(const ZhZrImg* __restrict__ imgs, uint32_t n_img,
+                                                             const uint64_t* __restrict__ hits, uint32_t n_hits,
+                                                             uint32_t* __restrict__ ranges, int32_t* __restrict__ start) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_img) return;
+  const ZhZrImg g = imgs[t];
+  const uint32_t lo = lower_bound(hits, 0, n_hits, g.up_off), hi = lower_bound(hits, lo, n_hits, g.up_off + g.len);
+  ranges[2 * t] = lo;
+  ranges[2 * t + 1] = hi;
+  start[t] = lo < hi && hits[lo] == g.up_off ? ZH_OK : g.len < 4 ? ZH_ERR_ARCHIVE_EOF : ZH_ERR_ZIP_OPEN;
+}
+
+// next[b] for every node b: nodes [0, n_hits) are the hits, node n_hits + t is image t's END (its own successor).  A
+// hit's successor is the hit at the position behind its record; it is END when the record fails a check of its own,
+// when it is an end record, and when that position is no hit -- succ[b] then says what the loop finds there:
+// failEOF within the last three bytes (:115-116), failOpen elsewhere (:328-329).  mark[b] = 1 for byte 0 of an image.
+__global__ __launch_bounds__(256) void zh_zipr_next_kernel(const uint8_t* __restrict__ d_in,
+                                                           const ZhZrImg* __restrict__ imgs, uint32_t n_img,
+                                                           const uint64_t* __restrict__ hits, uint32_t n_hits,
+                                                           const uint32_t* __restrict__ ranges, uint32_t n_nodes,
+                                                           uint32_t* __restrict__ jump, uint32_t* __restrict__ mark,
+                                                           int32_t* __restrict__ succ) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= n_nodes) return;
+  uint32_t nx = b, mk = 0;
+  if (b < n_hits) {
+    const uint64_t at = hits[b];
+    const uint32_t t = find_img(imgs, n_img, at);
+    const ZhZrImg g = imgs[t];
+    const uint64_t pos = at - g.up_off;
+    const ZhZrHead h = read_head(d_in + g.up_off, g.len, pos);
+    int32_t sc = ZH_OK;
+    nx = n_hits + t;
+    if (h.status == ZH_OK && h.kind != kKindEnd) {
+      if (h.next + 4 > g.len) {
+        sc = ZH_ERR_ARCHIVE_EOF;
+      } else {
+        const uint32_t hi = ranges[2 * t + 1], k = lower_bound(hits, b + 1, hi, g.up_off + h.next);
+        if (k < hi && hits[k] == g.up_off + h.next)
+          nx = k;
+        else
+          sc = ZH_ERR_ZIP_OPEN;
+      }
+    }
+    succ[b] = sc;
+    mk = pos == 0 ? 1u : 0u;
+  }
+  jump[b] = nx;
+  mark[b] = mk;
+}
+
+// One wave per reached record, in walk order (h = its ordinal in the call, list[h] its node).  The fields are read by
+// every lane (the same addresses: one broadcast load each); a local record's name goes over the lanes, which look
+// for a backslash (the host converts only the names that have one).
+__global__ __launch_bounds__(256) void zh_zipr_parse_kernel(const uint8_t* __restrict__ d_in,
+                                                            const ZhZrImg* __restrict__ imgs, uint32_t n_img,
+                                                            const uint64_t* __restrict__ hits,
+                                                            const uint32_t* __restrict__ list,
+                                                            const int32_t* __restrict__ succ, uint32_t n_rec,
+                                                            ZhZrRec* __restrict__ recs, int32_t* __restrict__ rstat) {
+  const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = zh_lane();
+  if (r >= n_rec) return;
+  const uint32_t node = list[r];
+  const uint64_t at = hits[node];
+  const ZhZrImg g = imgs[find_img(imgs, n_img, at)];
+  const uint8_t* __restrict__ p = d_in + g.up_off;
+  const ZhZrHead h = read_head(p, g.len, at - g.up_off);
+  bool slash = false;
+  if (h.status == ZH_OK && h.kind == kKindLocal)
+    for (uint32_t j = lane; j < h.name_len; j += 64) slash = slash || p[h.name_off + j] == '\\';
+  const bool backslash = __ballot(slash) != 0;
+  if (lane == 0) {
+    ZhZrRec rec{};
+    rec.pos = at - g.up_off;
+    rec.name_off = h.name_off;
+    rec.data_off = h.data_off;
+    rec.name_len = h.name_len;
+    rec.csize = h.csize;
+    rec.usize = h.usize;
+    rec.crc = h.crc;
+    rec.external = h.external;
+    rec.status = h.status;
+    rec.succ_status = succ[node];
+    rec.dos_time = h.dos_time;
+    rec.dos_date = h.dos_date;
+    rec.kind = h.kind;
+    rec.method = h.method;
+    rec.backslash = backslash ? 1 : 0;
+    recs[r] = rec;
+    rstat[r] = h.status != ZH_OK ? h.status : rec.succ_status;
+  }
+}
+
+// The images' ranges of records for the reduction: hits are in image order, so image t's records are those between
+// the ordinals of its first hit and of the next image's (ord[n_hits] = all records)
+__global__ __launch_bounds__(256) void zh_zipr_rec_ranges_kernel(const uint32_t* __restrict__ ranges, uint32_t n_img,
+                                                                 const uint32_t* __restrict__ ord,
+                                                                 uint32_t* __restrict__ rec_ranges) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_img) return;
+  rec_ranges[2 * t] = ord[ranges[2 * t]];
+  rec_ranges[2 * t + 1] = ord[ranges[2 * t + 1]];
+}
+
+// One wave per task (four a workgroup): a slice of a stored entry's bytes goes from its image to its slot (as
+// zh_zip_open_batch.hip's finish kernel copies it).  The wave of an entry's first task also settles the entry: the
+// decoder's status, else the CRC-32 against the header's (:208-212), else the length against the header's (:213-217).
+__global__ __launch_bounds__(256) void zh_zipr_finish_kernel(const uint8_t* __restrict__ d_in, uint8_t* __restrict__ d_out,
+                                                             const ZhZrFin* __restrict__ fins,
+                                                             const ZhZrFinTask* __restrict__ tasks, uint32_t n_tasks,
+                                                             const int32_t* __restrict__ plan_st,
+                                                             const uint64_t* __restrict__ plan_len,
+                                                             const uint32_t* __restrict__ plan_crc,
+                                                             const uint32_t* __restrict__ stored_crc,
+                                                             int32_t* __restrict__ est) {
+  const uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = zh_lane();
+  if (w >= n_tasks) return;
+  const ZhZrFinTask t = tasks[w];
+  const ZhZrFin e = fins[t.entry];
+  if (t.first && lane == 0) {
+    int32_t st = e.deflated ? plan_st[e.idx] : ZH_OK;
+    const uint32_t crc = e.deflated ? plan_crc[e.idx] : stored_crc[e.idx];
+    const uint64_t len = e.deflated ? plan_len[e.idx] : e.len;
+    if (st == ZH_OK && crc != e.want_crc) st = ZH_ERR_ZIP_CRC;
+    if (st == ZH_OK && len != e.want_len) st = ZH_ERR_ZIP_SIZE;
+    est[t.entry] = st;
+  }
+  if (t.lo >= t.hi) return;
+  const uint64_t a = e.dst + t.lo, b = e.dst + t.hi, delta = e.src - e.dst;  // (source byte = slot byte + delta, mod 2^64)
+  const uint64_t A = (a + 15) & ~(uint64_t)15, B = b & ~(uint64_t)15;
+  if (A >= B) {  // no whole chunk inside: at most 30 bytes
+    if (a + lane < b) d_out[a + lane] = d_in[a + lane + delta];
+    return;
+  }
+  if (a + lane < A) d_out[a + lane] = d_in[a + lane + delta];
+  if (B + lane < b) d_out[B + lane] = d_in[B + lane + delta];
+  for (uint64_t c = A + 16ull * lane; c < B; c += 1024) *reinterpret_cast<Chunk16*>(d_out + c) = gather16(d_in, c + delta);
+}
+
+namespace {
+
+struct Events {  // ZH_TRACE: kernels by themselves, between pairs of events that go away with the scope
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool ok = false;
+  bool create() {
+    ok = true;
+    for (hipEvent_t& x : e) ok = ok && hipEventCreate(&x) == hipSuccess;
+    return ok;
+  }
+  float ms(int a, int b) const {
+    float t = 0;
+    return hipEventSynchronize(e[b]) == hipSuccess && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? t : -1.f;
+  }
+  ~Events() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+// ZipArchive.contents as it grows (an OrderedTable[string, ArchiveEntry]): keys in first-insertion order
+struct Table {
+  struct Entry {
+    std::string key;
+    uint32_t rec;  // its last local record
+    bool directory = false, in_directory = false;
+    uint32_t unix_mode = 0;
+  };
+  std::vector<Entry> entries;
+  std::unordered_map<std::string, size_t> index;
+};
+
+}  // namespace
+
+extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n_zip,
+                                 zh_zip_reader** readers, int32_t* statuses) {
+  if (!ctx || (n_zip && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
+  for (size_t t = 0; t < n_zip; t++) {
+    readers[t] = nullptr;
+    statuses[t] = ZH_OK;
+  }
+  for (size_t t = 0; t < n_zip; t++)
+    if (!images[t] && lens[t]) return ZH_ERR_ARGUMENT;
+  if (!n_zip) return ZH_OK;
+
+  // ---- 1. the layout of the upload; the most nodes there can be (two signatures do not overlap) ----
+  std::vector<ZhZrImg> imgs(n_zip);
+  std::vector<uint64_t> up_off(n_zip), up_len(n_zip);
+  uint64_t up_total = 0, most_nodes = 0, max_chain = 0;
+  for (size_t t = 0; t < n_zip; t++) {
+    imgs[t] = ZhZrImg{up_total, (uint64_t)lens[t]};
+    up_off[t] = up_total;
+    up_len[t] = lens[t];
+    up_total += round_up8(lens[t]);
+    most_nodes += lens[t] / 4 + 1;
+    max_chain = std::max<uint64_t>(max_chain, lens[t] / 22 + 1);  // (no record is shorter than the end record)
+  }
+  if (most_nodes >= 0xffffffffull || n_zip >= 0x7fffffffull) return ZH_ERR_ARGUMENT;
+  ZH_HIP(ctx, hipSetDevice(ctx->device));
+  Trace tr;
+  int st;
+  hipStream_t s = ctx->stream;
+  const dim3 wg(256);
+  const uint32_t n_img = (uint32_t)n_zip;
+
+  // ---- 2. one upload ----
+  DevBuf d_in, d_imgs;
+  if (dev_alloc(ctx, d_in, up_total + 512) != hipSuccess) return ZH_ERR_NOMEM;
+  if (up_total && (st = zhh_upload_slices(ctx, images, up_off, up_len, up_total, d_in.p))) return st;
+  std::vector<uint64_t> ioff;
+  if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_zip * sizeof(ZhZrImg)}}, d_imgs, ioff))) return st;
+  const ZhZrImg* const dimgs = reinterpret_cast<const ZhZrImg*>(d_imgs.p);
+  const uint8_t* const in = d_in.p;  // (plain pointers: a launch must not take the guard of a buffer along)
+  tr.mark(ctx, "zip read: upload");
+
+  // ---- 3. the signature scan ----
+  const uint64_t scan_bytes = (up_total + 15) & ~(uint64_t)15;
+  const uint64_t n_groups64 = std::max<uint64_t>(1, (scan_bytes + kScanGroupBytes - 1) / kScanGroupBytes);
+  if (n_groups64 >= 0x7fffffffull) return ZH_ERR_ARGUMENT;
+  const uint32_t n_groups = (uint32_t)n_groups64;
+  DevBuf d_sums, d_hits;
+  if (dev_alloc(ctx, d_sums, ((size_t)n_groups + 1) * 4) != hipSuccess) return ZH_ERR_NOMEM;
+  uint32_t* const gsums = reinterpret_cast<uint32_t*>(d_sums.p);
+  Events evs;
+  if (tr.on) evs.create();
+  if (evs.ok) (void)hipEventRecord(evs.e[0], s);
+  hipLaunchKernelGGL(zh_zipr_scan_kernel<false>, dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums,
+                     (uint64_t*)nullptr);
+  if (evs.ok) (void)hipEventRecord(evs.e[1], s);
+  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, gsums, n_groups);
+  ZH_HIP(ctx, hipGetLastError());
+  uint32_t n_hits = 0;  // everything behind the scan is sized by the hits there are
+  ZH_HIP(ctx, hipMemcpyAsync(&n_hits, gsums + n_groups, 4, hipMemcpyDeviceToHost, s));
+  ZH_HIP(ctx, hipStreamSynchronize(s));
+  if (dev_alloc(ctx, d_hits, (size_t)n_hits * 8 + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  uint64_t* const hits = reinterpret_cast<uint64_t*>(d_hits.p);
+  if (evs.ok) (void)hipEventRecord(evs.e[2], s);
+  if (n_hits)
+    hipLaunchKernelGGL(zh_zipr_scan_kernel<true>, dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums, hits);
+  if (evs.ok) {
+    (void)hipEventRecord(evs.e[3], s);
+    fprintf(stderr, "[zh] %-28s %8.3f ms (HIP events; count pass: %llu bytes read)\n", "zip read: scan kernel 1",
+            evs.ms(0, 1), (unsigned long long)scan_bytes);
+    fprintf(stderr, "[zh] %-28s %8.3f ms (HIP events; write pass: %u hits, at most %llu bytes read)\n",
+            "zip read: scan kernel 2", evs.ms(2, 3), n_hits,
+            (unsigned long long)std::min<uint64_t>(scan_bytes, (uint64_t)n_hits * kScanGroupBytes));
+  }
+  tr.mark(ctx, "zip read: scan");
+
+  // ---- 4. the walk ----
+  // after `rounds` rounds every node up to 2^rounds - 1 steps from a start is marked; a chain has no more records
+  // than there are hits, nor than its image has room for
+  max_chain = std::min<uint64_t>(max_chain, n_hits);
+  uint32_t rounds = 0;
+  while ((1ull << rounds) < max_chain + 1) rounds++;
+  const uint32_t N = n_hits + n_img, n_sums = (N + kScanItems - 1) / kScanItems;
+  DevBuf d_scr;
+  Arena ar;
+  const size_t o_j0 = ar.reserve((size_t)N * 4), o_j1 = ar.reserve((size_t)N * 4), o_mark = ar.reserve((size_t)N * 4),
+               o_ord = ar.reserve((size_t)N * 4), o_succ = ar.reserve((size_t)n_hits * 4),
+               o_sums = ar.reserve(((size_t)n_sums + 1) * 4), o_hr = ar.reserve((size_t)n_img * 8);
+  if (dev_alloc(ctx, d_scr, ar.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  uint32_t* const j0 = carve<uint32_t>(d_scr.p, o_j0);
+  uint32_t* const j1 = carve<uint32_t>(d_scr.p, o_j1);
+  uint32_t* const mark = carve<uint32_t>(d_scr.p, o_mark);
+  uint32_t* const ord = carve<uint32_t>(d_scr.p, o_ord);
+  int32_t* const succ = carve<int32_t>(d_scr.p, o_succ);
+  uint32_t* const sums = carve<uint32_t>(d_scr.p, o_sums);
+  uint32_t* const hit_ranges = carve<uint32_t>(d_scr.p, o_hr);
+  // the per-image outputs live in the block that is downloaded with the records (below); the start statuses are
+  // written now, so they get a place of their own here
+  DevBuf d_start;
+  if (dev_alloc(ctx, d_start, (size_t)n_img * 4 + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  int32_t* const start = reinterpret_cast<int32_t*>(d_start.p);
+  const dim3 node_grid((N + 255) / 256), img_grid((n_img + 255) / 256);
+  hipLaunchKernelGGL(zh_zipr_ranges_kernel, img_grid, wg, 0, s, dimgs, n_img, (const uint64_t*)hits, n_hits, hit_ranges,
+                     start);
+  hipLaunchKernelGGL(zh_zipr_next_kernel, node_grid, wg, 0, s, in, dimgs, n_img, (const uint64_t*)hits,
+                     n_hits, (const uint32_t*)hit_ranges, N, j0, mark, succ);
+  uint32_t *jin = j0, *jout = j1;
+  for (uint32_t r = 0; r < rounds; r++) {
+    hipLaunchKernelGGL(zh_walk_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
+    std::swap(jin, jout);
+  }
+  // (the jump arrays are dead from here on: the list of records takes the place of the first)
+  uint32_t* const list = j0;
+  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
+  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
+  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, (const uint32_t*)sums,
+                     ord, list);
+  ZH_HIP(ctx, hipGetLastError());
+  uint32_t n_rec = 0;
+  ZH_HIP(ctx, hipMemcpyAsync(&n_rec, sums + n_sums, 4, hipMemcpyDeviceToHost, s));
+  ZH_HIP(ctx, hipStreamSynchronize(s));
+  tr.mark(ctx, "zip read: reach + scan");
+
+  // ---- 5. the records ----
+  Arena out;
+  const size_t o_recs = out.reserve((size_t)n_rec * sizeof(ZhZrRec)), o_ranges = out.reserve((size_t)n_img * 8),
+               o_bad = out.reserve((size_t)n_img * 4), o_start = out.reserve((size_t)n_img * 4);
+  const size_t out_bytes = out.size;
+  const size_t o_rstat = out.reserve((size_t)n_rec * 4), o_any = out.reserve((size_t)n_img * 4);
+  DevBuf d_rec;
+  if (dev_alloc(ctx, d_rec, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  uint8_t* const rec_p = d_rec.p;
+  if (n_rec)
+    hipLaunchKernelGGL(zh_zipr_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, in, dimgs, n_img,
+                       (const uint64_t*)hits, (const uint32_t*)list, (const int32_t*)succ, n_rec,
+                       carve<ZhZrRec>(rec_p, o_recs), carve<int32_t>(rec_p, o_rstat));
+  hipLaunchKernelGGL(zh_zipr_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img,
+                     (const uint32_t*)ord, carve<uint32_t>(rec_p, o_ranges));
+  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)carve<uint32_t>(rec_p, o_ranges),
+                     (const int32_t*)carve<int32_t>(rec_p, o_rstat), (const uint8_t*)nullptr,
+                     carve<uint32_t>(rec_p, o_bad), carve<uint32_t>(rec_p, o_any));
+  ZH_HIP(ctx, hipGetLastError());
+  ZH_HIP(ctx, hipMemcpyAsync(rec_p + o_start, start, (size_t)n_img * 4, hipMemcpyDeviceToDevice, s));
+  HostBufs own;
+  void* h_rec = nullptr;
+  {
+    size_t got = 0;
+    int32_t dst_st = ZH_OK;
+    st = zhh_download(ctx, d_rec.p, 1, {0}, {out_bytes}, {1}, &h_rec, &got, &dst_st);
+    own.p.push_back(h_rec);
+    if (st || dst_st) return st ? st : dst_st;
+  }
+  const uint8_t* const hr = (const uint8_t*)h_rec;
+  const ZhZrRec* const recs = reinterpret_cast<const ZhZrRec*>(hr + o_recs);
+  const uint32_t* const ranges = reinterpret_cast<const uint32_t*>(hr + o_ranges);
+  const uint32_t* const first_bad = reinterpret_cast<const uint32_t*>(hr + o_bad);
+  const int32_t* const start_st = reinterpret_cast<const int32_t*>(hr + o_start);
+  tr.mark(ctx, "zip read: parse + reduce");
+
+  // ---- 6. the tables, from the records in walk order; the layout of the output ----
+  // hst[t]: the first failure of the header checks, the central records' lookups and the walk's steps.  A local
+  // record in front of it still has its say (decoder, CRC, size): every one of them gets a slot.
+  struct Slot {
+    size_t img;
+    uint32_t rec;
+    uint64_t dst = 0, cap = 0;
+  };
+  std::vector<Table> tables(n_zip);
+  std::vector<int32_t> hst(n_zip, ZH_OK);
+  std::vector<Slot> slots;
+  std::vector<uint64_t> aoff(n_zip, 0), alen(n_zip, 0);
+  std::vector<size_t> slot_lo(n_zip, 0), slot_hi(n_zip, 0);
+  std::unordered_map<uint32_t, size_t> slot_of;  // a local record's slot
+  uint64_t out_total = 0;
+  for (size_t t = 0; t < n_zip; t++) {
+    slot_lo[t] = slot_hi[t] = slots.size();
+    if (start_st[t] != ZH_OK) {
+      hst[t] = start_st[t];
+      continue;
+    }
+    const uint8_t* const image = (const uint8_t*)images[t];
+    const uint32_t lo = ranges[2 * t], hi = ranges[2 * t + 1];
+    // records behind the first that failed on the device are never reached by the serial loop
+    const uint32_t stop = first_bad[t] == kNone ? hi : first_bad[t] + 1;
+    Table& tab = tables[t];
+    out_total = (out_total + 15) & ~(uint64_t)15;  // (the download moves a block 16 bytes at a time)
+    aoff[t] = out_total;
+    bool ended = false;
+    for (uint32_t i = lo; i < stop && hst[t] == ZH_OK && !ended; i++) {
+      const ZhZrRec& e = recs[i];
+      if (e.status != ZH_OK) {
+        hst[t] = e.status;
+        break;
+      }
+      if (e.kind == kKindLocal) {
+        Slot sl{t, i};
+        // never above the stream's expansion bound: a tiny image cannot claim gigabytes
+        sl.cap = e.method == 8 ? std::min<uint64_t>(e.usize, (uint64_t)e.csize * 1032 + 64) : e.csize;
+        sl.dst = out_total;
+        out_total += round_up8(sl.cap);
+        slot_of[i] = slots.size();
+        slots.push_back(sl);
+        std::string key((const char*)image + e.name_off, e.name_len);
+        if (e.backslash) std::replace(key.begin(), key.end(), '\\', '/');  // toUnixPath
+        const auto it = tab.index.find(key);
+        if (it == tab.index.end()) {
+          tab.index.emplace(key, tab.entries.size());
+          tab.entries.push_back(Table::Entry{std::move(key), i});
+        } else {
+          tab.entries[it->second] = Table::Entry{std::move(key), i};  // a fresh ArchiveEntry in the key's place
+        }
+      } else if (e.kind == kKindCentral) {
+        const auto it = tab.index.find(std::string((const char*)image + e.name_off, e.name_len));
+        if (it == tab.index.end()) {
+          hst[t] = ZH_ERR_ZIP_OPEN;
+          break;
+        }
+        Table::Entry& en = tab.entries[it->second];
+        if (e.external & 0x10u) en.directory = true;
+        en.unix_mode = e.external >> 16;
+        en.in_directory = true;
+      } else {
+        ended = true;
+      }
+      if (e.succ_status != ZH_OK) hst[t] = e.succ_status;
+    }
+    if (hst[t] == ZH_OK && !ended) {
+      ctx->last_error = "zh_zip_read_batch: a walk that ends nowhere";
+      return ZH_ERR_DEVICE;
+    }
+    slot_hi[t] = slots.size();
+    alen[t] = out_total - aoff[t];
+  }
+  const size_t n_slot = slots.size();
+  if (n_slot >= 0xffffffffull) return ZH_ERR_ARGUMENT;
+  tr.mark(ctx, "zip read: tables");
+
+  // ---- 7. one decode; 8. the stored entries and every verdict ----
+  std::vector<int32_t> est(n_slot, ZH_OK), ast(hst);
+  std::vector<void*> blocks(n_zip, nullptr);
+  size_t blocks_at = 0;  // blocks[t] is own.p[blocks_at + t] until a reader takes it
+  if (n_slot) {
+    std::vector<ZhZrFin> fins(n_slot);
+    std::vector<ZhZrFinTask> tasks;
+    std::vector<uint64_t> p_soff, p_slen, p_doff, p_dcap;
+    std::vector<ZhPieceDesc> pieces;
+    std::vector<ZhBufDesc> sbufs;
+    std::vector<uint32_t> eranges(2 * n_zip, 0);
+    for (size_t t = 0; t < n_zip; t++) {
+      eranges[2 * t] = (uint32_t)slot_lo[t];
+      eranges[2 * t + 1] = (uint32_t)slot_hi[t];
+    }
+    for (size_t j = 0; j < n_slot; j++) {
+      const Slot& sl = slots[j];
+      const ZhZrRec& e = recs[sl.rec];
+      const uint64_t src = imgs[sl.img].up_off + e.data_off;
+      ZhZrFin& f = fins[j];
+      f = ZhZrFin{src, sl.dst, 0, e.crc, e.usize, 0, 0};
+      uint64_t copy = 0;
+      if (e.method == 8) {
+        f.deflated = 1;
+        f.idx = (uint32_t)p_soff.size();
+        p_soff.push_back(src);
+        p_slen.push_back(e.csize);
+        p_doff.push_back(sl.dst);
+        p_dcap.push_back(sl.cap);
+      } else {
+        f.len = copy = e.csize;
+        f.idx = (uint32_t)sbufs.size();
+        ZhBufDesc b;
+        memset(&b, 0, sizeof(b));
+        b.src_off = src;
+        b.src_len = copy;
+        b.first_piece = (uint32_t)pieces.size();
+        for (uint64_t o = 0; o < copy; o += ZH_FRAG_SIZE)
+          pieces.push_back(ZhPieceDesc{src + o, (uint32_t)std::min<uint64_t>(copy - o, ZH_FRAG_SIZE), f.idx, o});
+        b.npieces = (uint32_t)pieces.size() - b.first_piece;
+        sbufs.push_back(b);
+      }
+      uint32_t first = 1;
+      for (uint64_t o = 0; first || o < copy; o += kSlice, first = 0)
+        tasks.push_back(ZhZrFinTask{o, std::min<uint64_t>(copy, o + kSlice), (uint32_t)j, first});
+    }
+    const size_t n_def = p_soff.size(), n_sto = sbufs.size(), n_piece = pieces.size(), n_task = tasks.size();
+    if (n_task >= 0xffffffffull || n_piece >= 0xffffffffull) return ZH_ERR_ARGUMENT;
+    DevBuf d_out, d_fin;
+    if (dev_alloc(ctx, d_out, out_total + 256) != hipSuccess) return ZH_ERR_NOMEM;
+    Arena fa;
+    const size_t o_fins = fa.reserve(n_slot * sizeof(ZhZrFin)), o_tasks = fa.reserve(n_task * sizeof(ZhZrFinTask)),
+                 o_sbufs = fa.reserve(n_sto * sizeof(ZhBufDesc)), o_pieces = fa.reserve(n_piece * sizeof(ZhPieceDesc)),
+                 o_er = fa.reserve(n_zip * 8);
+    const size_t fa_in = fa.size;
+    const size_t o_pcrc = fa.reserve(n_piece * 4), o_pad = fa.reserve(n_piece * 4), o_plen = fa.reserve(n_piece * 4),
+                 o_scrc = fa.reserve(n_sto * 4), o_sad = fa.reserve(n_sto * 4), o_est = fa.reserve(n_slot * 4),
+                 o_ebad = fa.reserve(n_zip * 4), o_eany = fa.reserve(n_zip * 4);
+    if (dev_alloc(ctx, d_fin, fa.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+    uint8_t* const fin_p = d_fin.p;
+    {
+      std::vector<uint8_t> h(fa_in);
+      memcpy(h.data() + o_fins, fins.data(), n_slot * sizeof(ZhZrFin));
+      memcpy(h.data() + o_tasks, tasks.data(), n_task * sizeof(ZhZrFinTask));
+      if (n_sto) memcpy(h.data() + o_sbufs, sbufs.data(), n_sto * sizeof(ZhBufDesc));
+      if (n_piece) memcpy(h.data() + o_pieces, pieces.data(), n_piece * sizeof(ZhPieceDesc));
+      memcpy(h.data() + o_er, eranges.data(), n_zip * 8);
+      const void* src = h.data();
+      if ((st = zhh_upload_slices(ctx, &src, {0}, {(uint64_t)fa_in}, fa_in, fin_p))) return st;
+    }
+    PlanGuard pg;
+    if (n_def) {
+      if ((st = zh_plan_uncompress(ctx, n_def, p_soff.data(), p_slen.data(), p_doff.data(), p_dcap.data(),
+                                   ZH_DF_DEFLATE, &pg.p)) ||
+          (st = zh_plan_request_crc32(pg.p, 1)))
+        return st;
+      if (tr.on) zh_plan_set_profiling(pg.p, 1);
+      if ((st = zh_plan_run(pg.p, d_in.p, d_out.p))) return st;
+      if (tr.on) {
+        const char* names[64];
+        float ms[64];
+        const int nk = zh_plan_kernel_times(pg.p, names, ms, 64);
+        for (int i = 0; i < nk && i < 64; i++) fprintf(stderr, "[zh]   plan kernel %-24s %8.3f ms\n", names[i], ms[i]);
+      }
+    }
+    tr.mark(ctx, "zip read: decode");
+    zh_launch_checksum_pieces(s, ctx->cktabs, d_in.p, carve<ZhPieceDesc>(fin_p, o_pieces), (uint32_t)n_piece, nullptr,
+                              1, 0, carve<uint32_t>(fin_p, o_pcrc), carve<uint32_t>(fin_p, o_pad),
+                              carve<uint32_t>(fin_p, o_plen));
+    zh_launch_checksum_combine(s, ctx->cktabs, carve<ZhBufDesc>(fin_p, o_sbufs), (uint32_t)n_sto,
+                               carve<uint32_t>(fin_p, o_pcrc), carve<uint32_t>(fin_p, o_pad),
+                               carve<uint32_t>(fin_p, o_plen), 1, 0, carve<uint32_t>(fin_p, o_scrc),
+                               carve<uint32_t>(fin_p, o_sad));
+    // (plain pointers: a launch must not take the guard of the plan along)
+    const int32_t* const plan_st = n_def ? zh_plan_device_statuses(pg.p) : nullptr;
+    const uint64_t* const plan_len = n_def ? zh_plan_device_lens(pg.p) : nullptr;
+    const uint32_t* const plan_crc = n_def ? pg.p->buf_crc : nullptr;
+    uint8_t* const outp = d_out.p;
+    hipLaunchKernelGGL(zh_zipr_finish_kernel, dim3(((uint32_t)n_task + 3) / 4), wg, 0, s, in, outp,
+                       (const ZhZrFin*)carve<ZhZrFin>(fin_p, o_fins),
+                       (const ZhZrFinTask*)carve<ZhZrFinTask>(fin_p, o_tasks), (uint32_t)n_task, plan_st, plan_len,
+                       plan_crc, (const uint32_t*)carve<uint32_t>(fin_p, o_scrc), carve<int32_t>(fin_p, o_est));
+    hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)carve<uint32_t>(fin_p, o_er),
+                       (const int32_t*)carve<int32_t>(fin_p, o_est), (const uint8_t*)nullptr,
+                       carve<uint32_t>(fin_p, o_ebad), carve<uint32_t>(fin_p, o_eany));
+    ZH_HIP(ctx, hipGetLastError());
+    std::vector<uint32_t> ebad(n_zip, kNone);
+    ZH_HIP(ctx, hipMemcpyAsync(est.data(), d_fin.p + o_est, n_slot * 4, hipMemcpyDeviceToHost, s));
+    ZH_HIP(ctx, hipMemcpyAsync(ebad.data(), d_fin.p + o_ebad, n_zip * 4, hipMemcpyDeviceToHost, s));
+    ZH_HIP(ctx, hipStreamSynchronize(s));
+    tr.mark(ctx, "zip read: finish");
+
+    // A stream that outgrew its slot decodes to more than its header claims: CRC comes before size (:208-217), so it
+    // is decoded again in full, from the host image, all of the call in one batch (rare: the CRC of these is
+    // compared here).  None of them can end well: at best the length is not the header's.
+    {
+      std::vector<size_t> redo;
+      for (size_t j = 0; j < n_slot; j++)
+        if (est[j] == ZH_ERR_DST_TOO_SMALL) redo.push_back(j);
+      if (!redo.empty()) {
+        const size_t nr = redo.size();
+        std::vector<const void*> rsrc(nr);
+        std::vector<size_t> rlen(nr), rout(nr);
+        std::vector<uint64_t> rhint(nr);
+        std::vector<void*> rdst(nr, nullptr);
+        std::vector<int32_t> rst(nr);
+        std::vector<uint32_t> rcrc(nr);
+        for (size_t q = 0; q < nr; q++) {
+          const Slot& sl = slots[redo[q]];
+          rsrc[q] = (const uint8_t*)images[sl.img] + recs[sl.rec].data_off;
+          rlen[q] = recs[sl.rec].csize;
+          rhint[q] = sl.cap;
+        }
+        st = zh_uncompress_batch_sized(ctx, rsrc.data(), rlen.data(), nr, ZH_DF_DEFLATE, rhint.data(), rdst.data(),
+                                       rout.data(), rst.data(), rcrc.data());
+        own.p.insert(own.p.end(), rdst.begin(), rdst.end());
+        if (st) return st;
+        std::vector<char> stale(n_zip, 0);
+        for (size_t q = 0; q < nr; q++) {
+          const size_t j = redo[q];
+          const ZhZrRec& e = recs[slots[j].rec];
+          est[j] = rst[q] != ZH_OK ? rst[q] : rcrc[q] != e.crc ? ZH_ERR_ZIP_CRC : rout[q] != e.usize ? ZH_ERR_ZIP_SIZE : ZH_OK;
+          stale[slots[j].img] = 1;
+        }
+        for (size_t t = 0; t < n_zip; t++) {  // the first failing record of these images, once more
+          if (!stale[t]) continue;
+          ebad[t] = kNone;
+          for (size_t j = slot_lo[t]; j < slot_hi[t]; j++)
+            if (est[j] != ZH_OK) {
+              ebad[t] = (uint32_t)j;
+              break;
+            }
+        }
+        tr.mark(ctx, "zip read: redo");
+      }
+    }
+    // every verified record stands in front of its image's hst in walk order
+    for (size_t t = 0; t < n_zip; t++)
+      if (ebad[t] != kNone) ast[t] = est[ebad[t]];
+
+    // ---- 9. one download: the block of every archive that opened ----
+    std::vector<char> take(n_zip, 0);
+    for (size_t t = 0; t < n_zip; t++) take[t] = ast[t] == ZH_OK && alen[t] ? 1 : 0;
+    std::vector<size_t> blen(n_zip, 0);
+    std::vector<int32_t> bst(n_zip, ZH_OK);
+    st = zhh_download(ctx, d_out.p, n_zip, aoff, alen, take, blocks.data(), blen.data(), bst.data());
+    blocks_at = own.p.size();
+    own.p.insert(own.p.end(), blocks.begin(), blocks.end());
+    if (st) return st;
+    for (size_t t = 0; t < n_zip; t++)
+      if (take[t] && bst[t]) return bst[t];  // (allocation)
+    tr.mark(ctx, "zip read: download");
+  }
+
+  // ---- the readers: the table's keys in first-insertion order, each with its last local record ----
+  Readers made;
+  made.r.assign(n_zip, nullptr);
+  for (size_t t = 0; t < n_zip; t++) {
+    if (ast[t] != ZH_OK) continue;
+    const Table& tab = tables[t];
+    const size_t n = tab.entries.size();
+    zh_zip_reader* r = zh_zip_reader_new(images[t], lens[t]);
+    made.r[t] = r;
+    std::vector<uint64_t> off(n, 0), len(n, 0);
+    std::vector<int32_t> stt(n, ZH_OK);
+    std::vector<void*> red(n, nullptr);
+    std::vector<uint16_t> dtime(n), ddate(n);
+    std::vector<uint8_t> in_dir(n);
+    for (size_t i = 0; i < n; i++) {
+      const Table::Entry& en = tab.entries[i];
+      const ZhZrRec& e = recs[en.rec];
+      zh_zip_reader_add(r, en.key, en.directory, (int64_t)e.pos, e.crc, (int64_t)e.csize, (int64_t)e.usize, en.unix_mode);
+      off[i] = slots[slot_of[en.rec]].dst - aoff[t];
+      len[i] = e.usize;
+      dtime[i] = e.dos_time;
+      ddate[i] = e.dos_date;
+      in_dir[i] = en.in_directory ? 1 : 0;
+    }
+    void* const block = blocks[t];
+    if (block) own.p[blocks_at + t] = nullptr;  // the reader's from here on
+    zh_zip_reader_set_data(r, block, (size_t)alen[t], off.data(), len.data(), stt.data(), red.data());
+    zh_zip_reader_set_v1(r, dtime.data(), ddate.data(), in_dir.data());
+  }
+  for (size_t t = 0; t < n_zip; t++) {
+    readers[t] = made.r[t];
+    statuses[t] = ast[t];
+    made.r[t] = nullptr;
+  }
+  return ZH_OK;
+}

@@ -1,5 +1,5 @@
-// What zh_zip.hip (zh_zip_open, one archive, host) and zh_zip_open_batch.hip (zh_zip_open_all_batch, many archives,
-// device) share: where an image's central directory is, the CP437 conversion, and the readers the batch call builds
+// What zh_zip.hip (zh_zip_open, one archive, host) and the batch readers (zh_zip_open_batch.hip: zh_zip_open_all_batch;
+// zh_zip_read_batch.hip: zh_zip_read_batch; many archives, device) share: where an image's central directory is, the CP437 conversion, and the readers the batch call builds
 // from its kernels' records.  Host code only.
 #pragma once
 #include <stddef.h>
@@ -32,3 +32,7 @@ ZH_ZIP_INTERNAL void zh_zip_reader_add(zh_zip_reader* r, std::string path, bool 
                                        uint32_t unix_mode);
 ZH_ZIP_INTERNAL void zh_zip_reader_set_data(zh_zip_reader* r, void* block, size_t block_len, const uint64_t* off,
                                             const uint64_t* len, const int32_t* status, void* const* redone);
+// A reader of zh_zip_read_batch (ziparchives_v1.nim's table): per entry the DOS time and date words of its local record
+// and whether a central record named it.  zh_zip_extract_batch refuses such a reader (its entries are all extracted).
+ZH_ZIP_INTERNAL void zh_zip_reader_set_v1(zh_zip_reader* r, const uint16_t* dos_time, const uint16_t* dos_date,
+                                          const uint8_t* in_directory);

@@ -489,3 +489,57 @@ proc createZipArchives*(tables: seq[OrderedTable[string, string]]): seq[string] 
       result.add take(ps[i], ns[i], 0)
   if firstBad != 0:
     raise newException(ZippyError, $zh_strerror(firstBad))
+
+# ---- Tarball.open (src/zippy/tarballs_v1.nim:66-157 openStreamImpl) ----
+type
+  HipTarV1Entry* = object
+    path*, contents*: string            # the table's key ((prefix / name).toUnixPath()), the contents
+    kind*: char                         # '0' ekNormalFile, '5' ekDirectory (nothing else set, as :150-154)
+    mode*: uint32                       # parseOctInt of the mode field's six bytes (a file's)
+    mtime*: int64                       # parseOctInt of the mtime field (a file's)
+
+proc zh_tar_read_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, formats: ptr int32, nTar: csize_t,
+                       readers: ptr pointer, statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipReadTarballs*(images: openArray[string],
+                      formats: openArray[int32] = []): seq[seq[HipTarV1Entry]] {.raises: [ZippyError].} =
+  ## openStreamImpl (tarballs_v1.nim:66-157) for many images in one call: every gzip image through one
+  ## uncompress(data, dfGzip) batch, the header loop of :99-157 for all images at once on the device; an image's
+  ## entries are its table's keys in the table's order.  formats: ord(tarballFormat) an image (tfDetect, tfUncompressed,
+  ## tfGzip = 0, 1, 2); none: all tfDetect.  Raises on the first image whose status is not zero, as the reference
+  ## would on that stream (without the half-filled table the reference leaves behind its exception).
+  let n = images.len
+  if n == 0: return
+  if formats.len != 0 and formats.len != n:
+    raise newException(ZippyError, "hipReadTarballs: one format an image")
+  var
+    ptrs = newSeq[pointer](n)
+    lens = newSeq[csize_t](n)
+    fmts = @formats
+    readers = newSeq[pointer](n)
+    sts = newSeq[int32](n)
+  for i, s in images:
+    ptrs[i] = if s.len > 0: s[0].unsafeAddr else: nil
+    lens[i] = s.len.csize_t
+  let rc = zh_tar_read_batch(engine(), ptrs[0].addr, lens[0].addr, (if fmts.len > 0: fmts[0].addr else: nil),
+                             n.csize_t, readers[0].addr, sts[0].addr)
+  try:
+    if rc != 0: raise newException(ZippyError, $zh_strerror(rc))
+    for st in sts:
+      if st != 0: raise newException(ZippyError, $zh_strerror(st.cint))
+    result = newSeq[seq[HipTarV1Entry]](n)
+    for t in 0 ..< n:
+      var dataLen: csize_t
+      let data = cast[ptr UncheckedArray[char]](zh_tar_data(readers[t], dataLen.addr))
+      for i in 0 ..< zh_tar_num_entries(readers[t]).int:
+        var e: ZhTarEntry
+        discard zh_tar_entry_at(readers[t], i.csize_t, e.addr)
+        var item = HipTarV1Entry(kind: e.typeflag, mode: e.mode, mtime: e.mtime)
+        item.path = newString(e.pathLen.int)
+        if e.pathLen > 0: copyMem(item.path[0].addr, e.path, e.pathLen.int)
+        item.contents = newString(e.size.int)
+        if e.size > 0: copyMem(item.contents[0].addr, data[e.offset.int].addr, e.size.int)
+        result[t].add item
+  finally:
+    for r in readers:
+      if r != nil: zh_tar_close(r)

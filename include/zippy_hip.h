@@ -85,7 +85,12 @@ enum {
   ZH_ERR_ZIP_DATA_DESCRIPTOR = 42, /* ziparchives_v1.nim:138-142 */
   ZH_ERR_ZIP_DEFLATE64 = 43,       /* ziparchives_v1.nim:144-148 (flag bit 3) */
   ZH_ERR_ZIP_SIZE = 44,            /* ziparchives_v1.nim:213-217 */
-  ZH_ERR_ZIP_OPEN = 45             /* ziparchives_v1.nim:110-111 failOpen: :282-293, :328-329 */
+  ZH_ERR_ZIP_OPEN = 45,            /* ziparchives_v1.nim:110-111 failOpen: :282-293, :328-329 */
+  /* v1 tarball reader (zh_tar_read_batch): tarballs_v1.nim openStreamImpl */
+  ZH_ERR_TAR_FORMAT = 46,          /* tarballs_v1.nim:86 */
+  ZH_ERR_TAR_OPEN = 47,            /* tarballs_v1.nim:118,124 (size or mtime that parseOctInt rejects) */
+  ZH_ERR_TAR_OPEN_MODE = 48,       /* tarballs_v1.nim:131 */
+  ZH_ERR_TAR_EOF = 49              /* tarballs_v1.nim:61-64 failEOF */
 };
 
 /* Engine context: one GPU, one HIP stream, reusable scratch. Thread-compatible
@@ -495,6 +500,50 @@ const void *zh_tar_data(const zh_tar_reader *reader, size_t *len);
  * More than 2^32 - 2 blocks of 512 bytes in one call (2 TiB of uncompressed images): ZH_ERR_ARGUMENT. */
 int zh_tar_open_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n_tar,
                       zh_tar_reader **readers, int32_t *statuses);
+
+/* Tarball.open(stream, tarballFormat) of the v1 API -- tarballs_v1.nim:66-157 openStreamImpl -- for n_tar images per
+ * call.  Not zh_tar_open_batch under another name: there is no end of archive, no long name, no symlink, no
+ * unsupported type and no path check here (that is extractAll's, :294-309, and stays with the caller).
+ * formats[t]: the caller's TarballFormat for image t; formats == NULL: all ZH_TF_DETECT.  statuses[t] is the outcome
+ * of openStreamImpl on image t alone, the first check that fails:
+ *   ZH_TF_DETECT (:80-88): byte 0 is 0x1F and byte 1 is 0x8B: gzip; byte 0 is 0x1F otherwise: ZH_ERR_TAR_FORMAT; else
+ *     uncompressed;
+ *   gzip (:94): the status zh_uncompress_batch(.., ZH_DF_GZIP, ..) gives the same bytes -- uncompress(data, dfGzip)
+ *     with its CRC-32 and ISIZE checks, not trustSize;
+ *   then, at pos (0 at first) while pos < len (:99):
+ *     1. pos + 512 > len: ZH_ERR_TAR_EOF (:100);
+ *     2. byte 0 of the name field is NUL: pos += 512 and on (:109-110) -- no other field of that header is read;
+ *     3. the size, bytes 124..134, by strutils.parseOctInt: ZH_ERR_TAR_OPEN (:118);
+ *     4. the mtime, bytes 136..146, likewise: ZH_ERR_TAR_OPEN (:124);
+ *     5. the mode, bytes 100..105, likewise: ZH_ERR_TAR_OPEN_MODE (:131);
+ *     6. pos + 512 + size > len: ZH_ERR_TAR_EOF (:139); contents that end the image without padding are accepted;
+ *     7. typeflag '0' or NUL: contents[key] = a file; '5': = a directory; any other byte: nothing (:142-154);
+ *     8. pos += 512 + (size + 511) & ~511 (:157).
+ *   parseOctInt(s): an optional 0o / 0O when at least one byte follows it, then digits 0-7 and '_' (skipped); an
+ *   error unless that is all of s and a digit was among them -- so a space or NUL inside the slice, an 8, or no digit.
+ *   key = (prefix / name).toUnixPath(): name and prefix end at their first NUL or fill their 100 / 155 bytes; the
+ *   prefix counts only when bytes 257..262 equal "ustar\0", the NUL included (GNU's "ustar  \0": no prefix); `/` is
+ *   std/os's join (an empty prefix: the name alone; one '/' at a seam of two); toUnixPath turns every \ into /.
+ *   contents[key] = entry replaces the value of an earlier equal key and keeps that key's place.
+ * readers[t]: an ordinary reader -- zh_tar_num_entries / zh_tar_entry_at / zh_tar_data / zh_tar_close --, NULL when
+ * statuses[t] != 0; a bad image never changes the others.  Its entries are the table's keys in the table's order:
+ * path = the key; linkname_len = 0; a file: typeflag '0' (for '0' and NUL), mode = the six-byte octal, mtime, and
+ * offset / size of the contents inside zh_tar_data(); a directory: typeflag '5' and every other field 0 whatever its
+ * header says (TarballEntry(kind: ekDirectory), :150-154).  initTime(mtime, 0) and parseFilePermissions(mode) stay
+ * with the caller.
+ * Differences from the reference: it leaves a half-filled table behind its exception, the library returns no reader;
+ * and where it raises a Defect, not a ZippyError, by indexing past the string -- ZH_TF_DETECT on an image of 0 bytes, or
+ * of 1 byte that is 0x1F -- the library answers ZH_ERR_TAR_FORMAT.
+ * The return value is a call-level error only: NULL arrays, an image that is NULL with a non-zero length, a format
+ * outside 0..2 (ZH_ERR_ARGUMENT), allocation, device.  A plain image is borrowed until its reader is closed; the
+ * uncompressed image of a gzip one is owned by its reader.  ctx is required; n_tar == 0 launches nothing.
+ * Every gzip image of the call is decoded by one uncompress plan; the loop runs for all images at once: every
+ * 512-byte block is read as if the loop stood on it, the blocks it does stand on are found by pointer doubling, and
+ * one wave per named header parses it and checks it (csrc/zh_tar_read_batch.hip).  The host parses no header byte.
+ * More than 2^32 - 2 blocks of 512 bytes in one call (2 TiB of uncompressed images): ZH_ERR_ARGUMENT. */
+enum { ZH_TF_DETECT = 0, ZH_TF_UNCOMPRESSED = 1, ZH_TF_GZIP = 2 }; /* TarballFormat, tarballs_v1.nim:18-19 */
+int zh_tar_read_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, const int32_t *formats,
+                      size_t n_tar, zh_tar_reader **readers, int32_t *statuses);
 
 /* Writing tarballs: writeTarball(tarball, path) -- tarballs_v1.nim:203-270 -- for n_tar in-memory
  * tarballs at once, without the file write.  The host lays the images out and sends every entry's

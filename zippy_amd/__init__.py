@@ -8,7 +8,9 @@ zippy_amd/csrc).  There is no CPU fallback: importing zippy_amd.api without the
 built library, or calling it without a GPU, raises.
 """
 from .common import (ZippyError, dfDetect, dfZlib, dfGzip, dfDeflate, NoCompression, BestSpeed,
-                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN)
+                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN, tfDetect, tfUncompressed,
+                     tfGzip)
 
 __all__ = ["ZippyError", "dfDetect", "dfZlib", "dfGzip", "dfDeflate", "NoCompression",
-           "BestSpeed", "BestCompression", "DefaultCompression", "HuffmanOnly", "TAR_PLAIN"]
+           "BestSpeed", "BestCompression", "DefaultCompression", "HuffmanOnly", "TAR_PLAIN",
+           "tfDetect", "tfUncompressed", "tfGzip"]

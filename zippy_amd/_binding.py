@@ -131,6 +131,9 @@ _SIGS = {
     "zh_tar_data": (_c.c_void_p, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
     "zh_tar_open_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                      _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int32)]),
+    "zh_tar_read_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                     _c.POINTER(_c.c_int32), _c.c_size_t, _c.POINTER(_c.c_void_p),
+                                     _c.POINTER(_c.c_int32)]),
     "zh_tar_create_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_size_t), _c.c_size_t, _c.c_int,
                                        _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
                                        _c.POINTER(_c.c_int32)]),
@@ -685,6 +688,21 @@ class Engine:
         lens = (_c.c_size_t * n)(*[len(b) for b in images])
         handles, sts = (_c.c_void_p * n)(), (_c.c_int32 * n)()
         self._check(self.lib.zh_tar_open_batch(self._h, srcs, lens, n, handles, sts))
+        return [TarReader(self, b, h) if h else None for b, h in zip(images, handles)], list(sts)
+
+    def read_tars(self, images, formats=None):
+        """zh_tar_read_batch: Tarball.open (tarballs_v1.nim:66-157) of every image in one call -> (readers, statuses);
+        formats: tfDetect / tfUncompressed / tfGzip (0 / 1 / 2), one an image, None: all detect.  readers[t] is a TarReader
+        whose entries are the table's keys in the table's order, or None where statuses[t] != 0."""
+        images = [bytes(b) for b in images]
+        n = len(images)
+        srcs = (_c.c_void_p * n)(*[_c.cast(_c.c_char_p(b), _c.c_void_p) if b else None for b in images])
+        lens = (_c.c_size_t * n)(*[len(b) for b in images])
+        if formats is not None and len(formats) != n:
+            raise ValueError("formats: one value an image")
+        fmts = None if formats is None else (_c.c_int32 * n)(*[int(f) for f in formats])
+        handles, sts = (_c.c_void_p * n)(), (_c.c_int32 * n)()
+        self._check(self.lib.zh_tar_read_batch(self._h, srcs, lens, fmts, n, handles, sts))
         return [TarReader(self, b, h) if h else None for b, h in zip(images, handles)], list(sts)
 
     def create_tars(self, tarballs, data_format=dfGzip, level=DefaultCompression):

@@ -13,7 +13,8 @@ import os
 
 from ._binding import Engine
 from .common import (ZippyError, dfDetect, dfZlib, dfGzip, dfDeflate, NoCompression, BestSpeed,
-                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN, to_msdos)
+                     BestCompression, DefaultCompression, HuffmanOnly, TAR_PLAIN, tfDetect, tfUncompressed, tfGzip,
+                     to_msdos)
 
 # ZIPPY_HIP_LIB: tuning builds of the same library (tools/); never a different implementation
 LIB_PATH = os.environ.get("ZIPPY_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
@@ -95,6 +96,17 @@ def openTarballs(images):
     walk on the device -> a list of readers, in order.  Raises ZippyError on the first image that failed."""
     eng = engine()
     readers, sts = eng.open_tars(images)
+    return eng._raise_first(readers, sts)
+
+
+def readTarballs(images, formats=None):
+    """tarballs_v1.nim:66-157 Tarball.open for many images in one call (zh_tar_read_batch): every gzip image decoded
+    and verified in one batch, every header walk on the device -> a list of readers, in order, whose .entries are the
+    table's keys in the table's order ('0' files with mode, mtime and .contents(i); '5' directories with nothing).
+    formats: tfDetect / tfUncompressed / tfGzip, one an image; None: all detect.  Raises ZippyError on the first image
+    that failed."""
+    eng = engine()
+    readers, sts = eng.read_tars(images, formats)
     return eng._raise_first(readers, sts)
 
 

@@ -23,6 +23,9 @@ HuffmanOnly = -2
 # zh_tar_create_batch's data format for a plain .tar image (include/zippy_hip.h ZH_TAR_PLAIN)
 TAR_PLAIN = -1
 
+# TarballFormat (tarballs_v1.nim:18-19), ordinals 0..2: zh_tar_read_batch's formats
+tfDetect, tfUncompressed, tfGzip = 0, 1, 2
+
 
 def to_msdos(unix_time):
     """toMsDos (ziparchives_v1.nim:356-369) of a Unix time, in local time -> (dos_time, dos_date)"""

@@ -126,6 +126,10 @@ extern "C" const char* zh_strerror(int status) {
     case ZH_ERR_ZIP_DEFLATE64: return "Unsupported zip archive, uses deflate64";
     case ZH_ERR_ZIP_SIZE: return "Unexpected error verifying uncompressed size";
     case ZH_ERR_ZIP_OPEN: return "Unexpected error opening zip archive";
+    case ZH_ERR_TAR_FORMAT: return "Unsupported tarball format";
+    case ZH_ERR_TAR_OPEN: return "Unexpected error while opening tarball";
+    case ZH_ERR_TAR_OPEN_MODE: return "Unexpected error while opening tarball (mode)";
+    case ZH_ERR_TAR_EOF: return "Attempted to read past end of file, corrupted tarball?";
     default: return "Unknown status";
   }
 }

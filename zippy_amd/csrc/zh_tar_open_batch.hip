@@ -8,18 +8,9 @@
 //   zh_tar_parse_kernel   one wave per header: fields, the joined path, the checks, one fixed-size record
 //   zh_tar_reduce_kernel  per tarball: the first header in walk order that failed is the tarball's status
 // The host builds the zh_tar_readers from the records; it parses no header byte itself.
-#include "zh_host.h"
-#include "zh_walk.h"
+#include "zh_tar_dev.h"
 
 namespace {
-
-// One tarball of the walk.  All tarballs of a call share one index space of 512-byte blocks ("nodes"): this one's
-// are [blk0, blk0 + nblk), nblk = ceil(len / 512), followed by its END node blk0 + nblk, which points to itself.
-struct ZhTarImg {
-  const uint8_t* data;  // device address of the uncompressed image, 8-byte aligned, readable up to len + 16
-  uint64_t len;
-  uint32_t blk0, nblk;
-};
 
 // One header that tarballs.nim:61-124 looks at (48 bytes).  `reported`: an entry of the reader (typeflags 0, \0, 5,
 // 2 of an active header); the other fields mean something only then.  The path is the 256-byte pool slot of the
@@ -30,18 +21,6 @@ struct ZhTarRec {
   uint32_t mode;
   uint8_t typeflag, link_len, reported, path_in_image;
 };
-
-__device__ __forceinline__ uint32_t find_img(const ZhTarImg* __restrict__ imgs, uint32_t n_img, uint32_t node) {
-  uint32_t lo = 0, hi = n_img;  // the last image whose blk0 <= node
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (imgs[mid].blk0 <= node)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
 
 // tarballs.nim:5-23 parseTarOctInt over the n bytes that start `shift` bytes into the 16 bytes (lo, hi): the first
 // run of decimal digits, read as octal; a digit 8 or 9 in it is an error (-> false)
@@ -99,21 +78,6 @@ __global__ __launch_bounds__(256) void zh_tar_next_kernel(const ZhTarImg* __rest
 }
 
 namespace {
-
-// bits [a, a + n) of the header as a mask over this lane's eight bytes [8 * lane, + 8)
-__device__ __forceinline__ uint32_t lane_span(uint32_t lane, uint32_t a, uint32_t n) {
-  const uint32_t lo = lane * 8, hi = lo + 8;
-  const uint32_t s = a > lo ? a - lo : 0u, e = a + n < hi ? (a + n > lo ? a + n - lo : 0u) : 8u;
-  return e > s ? ((1u << e) - 1u) & ~((1u << s) - 1u) : 0u;
-}
-// $(slice).cstring: the length of the NUL-terminated field [a, a + n); zm = this lane's zero-byte mask
-__device__ __forceinline__ uint32_t field_len(uint32_t zm, uint32_t lane, uint32_t a, uint32_t n) {
-  const uint32_t m = zm & lane_span(lane, a, n);
-  const uint64_t hit = __ballot(m != 0);
-  const uint32_t src = hit ? (uint32_t)__ffsll((unsigned long long)hit) - 1u : 0u;
-  const uint32_t mm = __shfl(m, (int)src);
-  return hit ? src * 8 + (uint32_t)__ffs(mm) - 1u - a : n;
-}
 
 // internal.nim:294-302 verifyPathIsSafeToExtract on the four bytes x of a path that start at position `at`
 __device__ __forceinline__ bool unsafe_at(uint32_t x, uint64_t at) {
@@ -256,47 +220,6 @@ __global__ __launch_bounds__(256) void zh_tar_parse_kernel(const ZhTarImg* __res
   }
 }
 
-// One workgroup per tarball: its headers are the ordinals [ord[blk0], ord[END]); the first of them whose status is
-// not ZH_OK gives the tarball's status, as the serial loop stops there.
-__global__ __launch_bounds__(256) void zh_tar_reduce_kernel(const ZhTarImg* __restrict__ imgs,
-                                                            const uint32_t* __restrict__ ord,
-                                                            const int32_t* __restrict__ hstat,
-                                                            uint32_t* __restrict__ ranges,
-                                                            int32_t* __restrict__ tstat) {
-  __shared__ uint32_t wave_min[4];
-  const ZhTarImg g = imgs[blockIdx.x];
-  const uint32_t first = ord[g.blk0], end = ord[g.blk0 + g.nblk];
-  uint32_t best = 0xffffffffu;
-  for (uint32_t i = first + threadIdx.x; i < end && best == 0xffffffffu; i += 256)
-    if (hstat[i] != ZH_OK) best = i;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) best = min(best, (uint32_t)__shfl_xor(best, m));
-  if (zh_lane() == 0) wave_min[threadIdx.x >> 6] = best;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    best = min(min(wave_min[0], wave_min[1]), min(wave_min[2], wave_min[3]));
-    tstat[blockIdx.x] = best == 0xffffffffu ? ZH_OK : hstat[best];
-    ranges[2 * blockIdx.x] = first;
-    ranges[2 * blockIdx.x + 1] = end;
-  }
-}
-
-namespace {
-
-struct HostBufs {  // host buffers of the call that no reader owns yet
-  std::vector<void*> p;
-  ~HostBufs() {
-    for (void* q : p) free(q);
-  }
-};
-
-uint32_t gzip_isize(const uint8_t* src, size_t len) {
-  const uint8_t* t = src + len - 4;
-  return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-}
-
-}  // namespace
-
 extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n_tar,
                                  zh_tar_reader** readers, int32_t* statuses) {
   if (!ctx || (n_tar && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
@@ -324,122 +247,20 @@ extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const s
   Trace tr;
   int st;
 
-  // ---- one upload: the plain images at 512-byte aligned offsets, the gzip members behind them ----
-  std::vector<const void*> up_src;
-  std::vector<uint64_t> up_off, up_len;
-  uint64_t o = 0;
-  for (size_t t : plain) {
-    up_src.push_back(images[t]);
-    up_off.push_back(o);
-    up_len.push_back(lens[t]);
-    o += (lens[t] + 511) & ~(uint64_t)511;
-  }
-  for (size_t t : gz) {
-    up_src.push_back(images[t]);
-    up_off.push_back(o);
-    up_len.push_back(lens[t]);
-    o += (lens[t] + 255) & ~(uint64_t)255;
-  }
-  DevBuf d_in, d_dec, d_redo;
-  if (dev_alloc(ctx, d_in, o + 512) != hipSuccess) return ZH_ERR_NOMEM;
-  if ((st = zhh_upload_slices(ctx, up_src.data(), up_off, up_len, o, d_in.p))) return st;
-  tr.mark(ctx, "tar open: upload");
-
-  // the tarballs of the walk: where their bytes are on the device, who owns them on the host
-  struct Walk {
-    size_t t;
-    const uint8_t* d_data;
-    uint64_t len;
-    int host = -1;  // index into `own` of the host copy a .tar.gz's reader will own
-    int slot = -1;  // ... or the decode slot it is still to be fetched from
-  };
-  std::vector<Walk> walk;
-  for (size_t k = 0; k < plain.size(); k++) walk.push_back({plain[k], d_in.p + up_off[k], lens[plain[k]]});
-  HostBufs own;
-
-  // ---- one decode: every gzip member through one sized plan, ISIZE as the slot (gzip.nim:72-76 trustSize) ----
-  const size_t n_gz = gz.size();
-  std::vector<uint64_t> doff(n_gz), dcap(n_gz), olen(n_gz);
-  if (n_gz) {
-    std::vector<uint64_t> soff(up_off.begin() + plain.size(), up_off.end()),
-        slen(up_len.begin() + plain.size(), up_len.end());
-    uint64_t total = 0;
-    for (size_t k = 0; k < n_gz; k++) {
-      const size_t t = gz[k];
-      dcap[k] = std::min<uint64_t>(gzip_isize((const uint8_t*)images[t], lens[t]), (uint64_t)lens[t] * 1032 + 64);
-      doff[k] = total;
-      total += (dcap[k] + 511) & ~(uint64_t)511;
-    }
-    if (dev_alloc(ctx, d_dec, total + 512) != hipSuccess) return ZH_ERR_NOMEM;
-    PlanGuard pg;
-    std::vector<int32_t> ost(n_gz);
-    if ((st = zh_plan_uncompress(ctx, n_gz, soff.data(), slen.data(), doff.data(), dcap.data(), ZH_DF_GZIP, &pg.p)) ||
-        (st = zh_plan_run(pg.p, d_in.p, d_dec.p)) || (st = zh_plan_results(pg.p, olen.data(), ost.data())))
-      return st;
-    tr.mark(ctx, "tar open: decode");
-    // A member that outgrew its ISIZE (4 GiB and more, or damaged) takes zh_tar_open's own route, the host call that
-    // retries at the expansion bound: its status is that call's, its image comes back to the device for the walk.
-    std::vector<size_t> redo;
-    for (size_t k = 0; k < n_gz; k++) {
-      if (ost[k] == ZH_ERR_DST_TOO_SMALL)
-        redo.push_back(k);
-      else if (ost[k] != ZH_OK)
-        statuses[gz[k]] = ost[k];
-      else
-        walk.push_back({gz[k], d_dec.p + doff[k], olen[k], -1, (int)k});
-    }
-    if (!redo.empty()) {
-      const size_t nr = redo.size();
-      std::vector<const void*> rsrc(nr);
-      std::vector<size_t> rlen(nr), rout(nr);
-      std::vector<uint64_t> rhint(nr);
-      std::vector<void*> rdst(nr, nullptr);
-      std::vector<int32_t> rst(nr);
-      for (size_t j = 0; j < nr; j++) {
-        rsrc[j] = images[gz[redo[j]]];
-        rlen[j] = lens[gz[redo[j]]];
-        rhint[j] = gzip_isize((const uint8_t*)rsrc[j], rlen[j]);
-      }
-      st = zh_uncompress_batch_sized(ctx, rsrc.data(), rlen.data(), nr, ZH_DF_GZIP, rhint.data(), rdst.data(),
-                                     rout.data(), rst.data(), nullptr);
-      own.p = rdst;
-      if (st) return st;
-      std::vector<const void*> hsrc;
-      std::vector<size_t> hlen, hwalk;
-      for (size_t j = 0; j < nr; j++) {
-        if (rst[j] != ZH_OK) {
-          statuses[gz[redo[j]]] = rst[j];
-          continue;
-        }
-        hwalk.push_back(walk.size());
-        walk.push_back({gz[redo[j]], nullptr, rout[j], (int)j, -1});
-        hsrc.push_back(rdst[j]);
-        hlen.push_back(rout[j]);
-      }
-      if (!hsrc.empty()) {
-        std::vector<uint64_t> hoff, hlen64;
-        if ((st = zhh_upload(ctx, hsrc.data(), hlen.data(), hsrc.size(), d_redo, hoff, hlen64))) return st;
-        for (size_t j = 0; j < hwalk.size(); j++) walk[hwalk[j]].d_data = d_redo.p + hoff[j];
-      }
-    }
-  }
+  // ---- one upload, one decode (zh_tar_dev.h) ----
+  TarStage stage;
+  if ((st = tar_stage(ctx, images, lens, plain, gz, statuses, tr, "tar open: upload", "tar open: decode", stage)))
+    return st;
+  std::vector<TarWalk>& walk = stage.walk;
+  HostBufs& own = stage.own;
   const size_t n_walk = walk.size();
   if (!n_walk) return ZH_OK;
 
   // ---- the walk ----
-  std::vector<ZhTarImg> imgs(n_walk);
-  uint64_t n_nodes = 0, max_blk = 0;
-  for (size_t k = 0; k < n_walk; k++) {
-    const uint64_t nblk = (walk[k].len + 511) >> 9;
-    if (n_nodes + nblk + 1 >= 0xffffffffull) return ZH_ERR_ARGUMENT;  // (2 TiB of images in one call)
-    imgs[k] = ZhTarImg{walk[k].d_data, walk[k].len, (uint32_t)n_nodes, (uint32_t)nblk};
-    n_nodes += nblk + 1;
-    max_blk = std::max(max_blk, nblk);
-  }
-  // after `rounds` rounds every node up to 2^rounds - 1 steps from a start is marked; a chain has at most max_blk
-  uint32_t rounds = 0;
-  while ((1ull << rounds) < max_blk + 1) rounds++;
-  const uint32_t N = (uint32_t)n_nodes, n_sums = (N + kScanItems - 1) / kScanItems;
+  std::vector<ZhTarImg> imgs;
+  uint32_t n_nodes = 0, rounds = 0;
+  if ((st = tar_nodes(walk, imgs, &n_nodes, &rounds))) return st;
+  const uint32_t N = n_nodes, n_sums = (N + kScanItems - 1) / kScanItems;
   DevBuf d_imgs, d_scr;
   std::vector<uint64_t> ioff;
   if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_walk * sizeof(ZhTarImg)}}, d_imgs, ioff))) return st;
@@ -482,13 +303,17 @@ extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const s
   const size_t o_hstat = out.reserve((size_t)n_hdr * 4);
   DevBuf d_out;
   if (dev_alloc(ctx, d_out, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  // (plain pointers for the launches: a launch must not take the DevBuf itself along)
+  ZhTarRec* const d_recs = carve<ZhTarRec>(d_out.p, o_recs);
+  uint32_t* const d_pool = carve<uint32_t>(d_out.p, o_pool);
+  uint32_t* const d_ranges = carve<uint32_t>(d_out.p, o_ranges);
+  int32_t* const d_tstat = carve<int32_t>(d_out.p, o_tstat);
+  int32_t* const d_hstat = carve<int32_t>(d_out.p, o_hstat);
   if (n_hdr)
     hipLaunchKernelGGL(zh_tar_parse_kernel, dim3((n_hdr + 3) / 4), wg, 0, s, dimgs, (uint32_t)n_walk,
-                       (const uint32_t*)ord, (const uint32_t*)list, n_hdr, carve<ZhTarRec>(d_out.p, o_recs),
-                       carve<uint32_t>(d_out.p, o_pool), carve<int32_t>(d_out.p, o_hstat));
+                       (const uint32_t*)ord, (const uint32_t*)list, n_hdr, d_recs, d_pool, d_hstat);
   hipLaunchKernelGGL(zh_tar_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s, dimgs, (const uint32_t*)ord,
-                     (const int32_t*)carve<int32_t>(d_out.p, o_hstat), carve<uint32_t>(d_out.p, o_ranges),
-                     carve<int32_t>(d_out.p, o_tstat));
+                     (const int32_t*)d_hstat, d_ranges, d_tstat);
   ZH_HIP(ctx, hipGetLastError());
   void* h_out = nullptr;
   {
@@ -508,23 +333,7 @@ extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const s
   tr.mark(ctx, "tar open: parse + reduce");
 
   // ---- the decoded images of the tarballs that opened ----
-  {
-    std::vector<char> take(n_gz, 0);
-    for (size_t k = 0; k < n_walk; k++)
-      if (walk[k].slot >= 0 && tstat[k] == ZH_OK) take[(size_t)walk[k].slot] = 1;
-    std::vector<void*> idst(n_gz, nullptr);
-    std::vector<size_t> ilen(n_gz, 0);
-    std::vector<int32_t> ist(n_gz, ZH_OK);
-    st = n_gz ? zhh_download(ctx, d_dec.p, n_gz, doff, olen, take, idst.data(), ilen.data(), ist.data()) : ZH_OK;
-    const size_t base = own.p.size();
-    own.p.insert(own.p.end(), idst.begin(), idst.end());
-    if (st) return st;
-    for (size_t k = 0; k < n_walk; k++)
-      if (walk[k].slot >= 0 && tstat[k] == ZH_OK) {
-        if (ist[(size_t)walk[k].slot]) return ist[(size_t)walk[k].slot];  // (allocation)
-        walk[k].host = (int)(base + (size_t)walk[k].slot);
-      }
-  }
+  if ((st = tar_fetch(ctx, stage, tstat))) return st;
   tr.mark(ctx, "tar open: download");
 
   // ---- the readers, from the records ----

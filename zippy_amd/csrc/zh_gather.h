@@ -1,5 +1,6 @@
 // Sixteen bytes at any source alignment, for kernels that copy byte ranges between unaligned places with 16-byte
-// stores (zh_zip_write.hip's writers, zh_zip_open_batch.hip's stored entries).
+// stores (zh_zip_write.hip's writers; zh_zip_dev.h's finish kernel for the stored entries of both batch zip readers;
+// zh_zip_read_batch.hip's signature scan loads its chunks as Chunk16).
 #pragma once
 #include "zh_common.h"
 

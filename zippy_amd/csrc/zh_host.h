@@ -1,12 +1,13 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in twelve files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in thirteen files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
 // wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
 // zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks) the batch writers
-// zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_zip_open_batch.hip /
-// zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h, zh_gather.h and zh_zip_dev.h hold what
-// they share).  No compute happens on the host.
+// zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
+// zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
+// all four share, zh_tar_dev.h and zh_zip_dev.h what the two of a format share, zh_gather.h the unaligned copy).
+// No compute happens on the host.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -385,4 +386,53 @@ static inline int writer_hand_out(zh_ctx* ctx, const uint8_t* d_img, const std::
     statuses[pos[k]] = st[k];
   }
   return ZH_OK;
+}
+
+// ---- the batch readers (zh_tar_open_batch, zh_tar_read_batch, zh_zip_open_all_batch, zh_zip_read_batch) ----
+// Their call-level checks, in this order: the pointers; readers / statuses cleared; every image there.  The caller
+// goes on only on ZH_OK with n > 0.
+template <class Reader>
+static int reader_checks(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n, Reader** readers,
+                         int32_t* statuses) {
+  if (!ctx || (n && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
+  for (size_t t = 0; t < n; t++) {
+    readers[t] = nullptr;
+    statuses[t] = ZH_OK;
+  }
+  for (size_t t = 0; t < n; t++)
+    if (!images[t] && lens[t]) return ZH_ERR_ARGUMENT;
+  return ZH_OK;
+}
+
+struct HostBufs {  // host buffers of the call that no reader owns yet
+  std::vector<void*> p;
+  ~HostBufs() {
+    for (void* q : p) free(q);
+  }
+};
+
+struct Events {  // ZH_TRACE: kernels by themselves, between pairs of events that go away with the scope
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool ok = false;
+  bool create() {
+    ok = true;
+    for (hipEvent_t& x : e) ok = ok && hipEventCreate(&x) == hipSuccess;
+    return ok;
+  }
+  float ms(int a, int b) const {
+    float t = 0;
+    return hipEventSynchronize(e[b]) == hipSuccess && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? t : -1.f;
+  }
+  ~Events() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+// internal.nim:294-302 verifyPathIsSafeToExtract on the four bytes x of a path that start at position `at` (the
+// parse kernels of zh_tar_open_batch.hip and zh_zip_open_batch.hip)
+static __device__ __forceinline__ bool unsafe_at(uint32_t x, uint64_t at) {
+  if (x == 0x2f2e2e2fu || x == 0x5c2e2e5cu) return true;  // "/../", "\..\"
+  if (at != 0) return false;
+  return (x & 0xffu) == '/' || (x & 0xffffffu) == 0x2f2e2eu || (x & 0xffffffu) == 0x5c2e2eu;  // "/", "../", "..\"
 }

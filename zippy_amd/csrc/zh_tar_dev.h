@@ -1,10 +1,11 @@
 // What the two batch tarball readers share (zh_tar_open_batch.hip: extractAll of tarballs.nim; zh_tar_read_batch.hip:
 // Tarball.open of tarballs_v1.nim): the images of a call on the device -- the plain ones uploaded at 512-byte aligned
 // offsets, every gzip member decoded by ONE sized uncompress plan --, the index space of their 512-byte blocks, the
-// string fields of a header held 8 bytes a lane, and the reduction of the headers' statuses to one per tarball.
+// string fields of a header held 8 bytes a lane, the reduction of the headers' statuses to one per tarball, and the
+// host stages around each file's own kernels: tar_stage (upload, decode), tar_nodes, tar_results (parse, reduce, the
+// records on the host), tar_fetch (the decoded images on the host), tar_reader_of.
 // The kernel has internal linkage: each file that includes this header launches its own copy.
 #pragma once
-#include "zh_host.h"
 #include "zh_walk.h"
 
 namespace {
@@ -68,13 +69,6 @@ __global__ __launch_bounds__(256) void zh_tar_reduce_kernel(const ZhTarImg* __re
     ranges[2 * blockIdx.x + 1] = end;
   }
 }
-
-struct HostBufs {  // host buffers of the call that no reader owns yet
-  std::vector<void*> p;
-  ~HostBufs() {
-    for (void* q : p) free(q);
-  }
-};
 
 inline uint32_t gzip_isize(const uint8_t* src, size_t len) {
   const uint8_t* t = src + len - 4;
@@ -213,6 +207,51 @@ inline int tar_nodes(const std::vector<TarWalk>& walk, std::vector<ZhTarImg>& im
   return ZH_OK;
 }
 
+// What the device found, on the host (in a buffer of s.own): the records of all headers in walk order, their 256-byte
+// pool slots, and per tarball of s.walk its range of headers and its status
+template <class Rec>
+struct TarResults {
+  const Rec* recs;
+  const uint8_t* pool;
+  const uint32_t* ranges;
+  const int32_t* tstat;
+};
+// launch_parse(recs, pool, hstat) launches the caller's parse kernel over the n_hdr headers the walk listed; the
+// reduction follows, and everything but the headers' statuses comes back in one download.
+template <class Rec, class Parse>
+inline int tar_results(zh_ctx* ctx, TarStage& s, const Walk& w, const ZhTarImg* dimgs, size_t n_walk, uint32_t n_hdr,
+                       Parse launch_parse, TarResults<Rec>& r) {
+  Arena out;
+  const size_t o_recs = out.reserve((size_t)n_hdr * sizeof(Rec)), o_pool = out.reserve((size_t)n_hdr * 256),
+               o_ranges = out.reserve(n_walk * 8), o_tstat = out.reserve(n_walk * 4);
+  const size_t out_bytes = out.size;
+  const size_t o_hstat = out.reserve((size_t)n_hdr * 4);
+  DevBuf d_out;
+  if (dev_alloc(ctx, d_out, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  // (plain pointers for the launches: a launch must not take the DevBuf itself along)
+  uint32_t* const d_ranges = carve<uint32_t>(d_out.p, o_ranges);
+  int32_t* const d_tstat = carve<int32_t>(d_out.p, o_tstat);
+  int32_t* const d_hstat = carve<int32_t>(d_out.p, o_hstat);
+  const uint32_t* const ord = w.ord;
+  if (n_hdr) launch_parse(carve<Rec>(d_out.p, o_recs), carve<uint32_t>(d_out.p, o_pool), d_hstat);
+  hipLaunchKernelGGL(zh_tar_reduce_kernel, dim3((uint32_t)n_walk), dim3(256), 0, ctx->stream, dimgs, ord,
+                     (const int32_t*)d_hstat, d_ranges, d_tstat);
+  ZH_HIP(ctx, hipGetLastError());
+  void* h_out = nullptr;
+  size_t got = 0;
+  int32_t dst_st = ZH_OK;
+  if (const int st = zhh_download(ctx, d_out.p, 1, {0}, {out_bytes}, {1}, &h_out, &got, &dst_st)) {
+    free(h_out);
+    return st;
+  }
+  s.own.p.push_back(h_out);
+  if (dst_st) return dst_st;
+  const uint8_t* const ho = (const uint8_t*)h_out;
+  r = TarResults<Rec>{reinterpret_cast<const Rec*>(ho + o_recs), ho + o_pool,
+                      reinterpret_cast<const uint32_t*>(ho + o_ranges), reinterpret_cast<const int32_t*>(ho + o_tstat)};
+  return ZH_OK;
+}
+
 // The decoded images of the tarballs that opened (tstat[k] of s.walk[k]) come to the host: walk[k].host says where.
 inline int tar_fetch(zh_ctx* ctx, TarStage& s, const int32_t* tstat) {
   const size_t n_gz = s.doff.size(), n_walk = s.walk.size();
@@ -234,5 +273,24 @@ inline int tar_fetch(zh_ctx* ctx, TarStage& s, const int32_t* tstat) {
     }
   return ZH_OK;
 }
+
+// The empty reader of s.walk[k], *data its image: the caller's (borrowed), or the host copy it owns from here on
+inline zh_tar_reader* tar_reader_of(TarStage& s, size_t k, const void* const* images, const uint8_t** data) {
+  const TarWalk& w = s.walk[k];
+  const bool borrowed = w.host < 0;
+  void* const owned = borrowed ? nullptr : s.own.p[(size_t)w.host];
+  *data = (const uint8_t*)(borrowed ? images[w.t] : owned);
+  zh_tar_reader* r = zh_tar_reader_new(owned, *data, (size_t)w.len);
+  if (r && !borrowed) s.own.p[(size_t)w.host] = nullptr;
+  return r;
+}
+struct CloseAll {  // the readers made so far: closed when the call fails
+  std::vector<zh_tar_reader*>& v;
+  bool armed = true;
+  ~CloseAll() {
+    if (armed)
+      for (zh_tar_reader* r : v) zh_tar_close(r);
+  }
+};
 
 }  // namespace

@@ -77,17 +77,6 @@ __global__ __launch_bounds__(256) void zh_tar_next_kernel(const ZhTarImg* __rest
   mark[b] = b == g.blk0 && b != end ? 1u : 0u;
 }
 
-namespace {
-
-// internal.nim:294-302 verifyPathIsSafeToExtract on the four bytes x of a path that start at position `at`
-__device__ __forceinline__ bool unsafe_at(uint32_t x, uint64_t at) {
-  if (x == 0x2f2e2e2fu || x == 0x5c2e2e5cu) return true;  // "/../", "\..\"
-  if (at != 0) return false;
-  return (x & 0xffu) == '/' || (x & 0xffffffu) == 0x2f2e2eu || (x & 0xffffffu) == 0x5c2e2eu;  // "/", "../", "..\"
-}
-
-}  // namespace
-
 // One wave per header, in walk order (h = its ordinal in the call, list[h] its node).  The lanes load the header 8
 // bytes each; string fields end at the first zero byte of their range (ballot + shuffle), the octal fields are read
 // from the two lanes that hold them.  The header's own status follows the reference's order: the block is whole
@@ -222,13 +211,7 @@ __global__ __launch_bounds__(256) void zh_tar_parse_kernel(const ZhTarImg* __res
 
 extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n_tar,
                                  zh_tar_reader** readers, int32_t* statuses) {
-  if (!ctx || (n_tar && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_tar; t++) {
-    readers[t] = nullptr;
-    statuses[t] = ZH_OK;
-  }
-  for (size_t t = 0; t < n_tar; t++)
-    if (!images[t] && lens[t]) return ZH_ERR_ARGUMENT;
+  if (const int e = reader_checks(ctx, images, lens, n_tar, readers, statuses)) return e;
   if (!n_tar) return ZH_OK;
 
   // ---- classify: lengths and magic bytes only (tarballs.nim:43-54, gzip.nim:10-11) ----
@@ -251,120 +234,68 @@ extern "C" int zh_tar_open_batch(zh_ctx* ctx, const void* const* images, const s
   TarStage stage;
   if ((st = tar_stage(ctx, images, lens, plain, gz, statuses, tr, "tar open: upload", "tar open: decode", stage)))
     return st;
-  std::vector<TarWalk>& walk = stage.walk;
-  HostBufs& own = stage.own;
+  const std::vector<TarWalk>& walk = stage.walk;
   const size_t n_walk = walk.size();
   if (!n_walk) return ZH_OK;
 
-  // ---- the walk ----
+  // ---- the walk (zh_walk.h) ----
   std::vector<ZhTarImg> imgs;
-  uint32_t n_nodes = 0, rounds = 0;
-  if ((st = tar_nodes(walk, imgs, &n_nodes, &rounds))) return st;
-  const uint32_t N = n_nodes, n_sums = (N + kScanItems - 1) / kScanItems;
-  DevBuf d_imgs, d_scr;
+  uint32_t N = 0, rounds = 0;
+  if ((st = tar_nodes(walk, imgs, &N, &rounds))) return st;
+  DevBuf d_imgs;
   std::vector<uint64_t> ioff;
   if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_walk * sizeof(ZhTarImg)}}, d_imgs, ioff))) return st;
-  // scratch: two jump arrays, the marks, the ordinals -- 4 bytes a node each -- and the scan's workgroup sums
-  Arena ar;
-  const size_t o_j0 = ar.reserve((size_t)N * 4), o_j1 = ar.reserve((size_t)N * 4), o_mark = ar.reserve((size_t)N * 4),
-               o_ord = ar.reserve((size_t)N * 4), o_sums = ar.reserve(((size_t)n_sums + 1) * 4);
-  if (dev_alloc(ctx, d_scr, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
-  uint32_t* const j0 = carve<uint32_t>(d_scr.p, o_j0);
-  uint32_t* const j1 = carve<uint32_t>(d_scr.p, o_j1);
-  uint32_t* const mark = carve<uint32_t>(d_scr.p, o_mark);
-  uint32_t* const ord = carve<uint32_t>(d_scr.p, o_ord);
-  uint32_t* const sums = carve<uint32_t>(d_scr.p, o_sums);
+  Walk w;
+  if ((st = walk_alloc(ctx, w, N))) return st;
+  // (plain pointers for the launches: a launch must not take a DevBuf, or the Walk that holds one, along)
   const ZhTarImg* const dimgs = reinterpret_cast<const ZhTarImg*>(d_imgs.p);
-  const dim3 node_grid((N + 255) / 256), wg(256);
+  uint32_t *const j0 = w.j0, *const mark = w.mark;
+  const uint32_t *const ord = w.ord, *const list = w.list;
+  const dim3 wg(256);
   hipStream_t s = ctx->stream;
-  hipLaunchKernelGGL(zh_tar_next_kernel, node_grid, wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark);
-  uint32_t *jin = j0, *jout = j1;
-  for (uint32_t r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(zh_walk_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
-    std::swap(jin, jout);
-  }
-  // (the jump arrays are dead from here on: the list of headers takes the place of the first)
-  uint32_t* const list = j0;
-  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
-  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
-  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
-                     (const uint32_t*)sums, ord, list);
-  ZH_HIP(ctx, hipGetLastError());
-  uint32_t n_hdr = 0;  // the records are sized by the headers there are, not by the blocks
-  ZH_HIP(ctx, hipMemcpyAsync(&n_hdr, sums + n_sums, 4, hipMemcpyDeviceToHost, s));
-  ZH_HIP(ctx, hipStreamSynchronize(s));
+  hipLaunchKernelGGL(zh_tar_next_kernel, dim3((N + 255) / 256), wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark);
+  walk_double(w, rounds, s);
+  walk_scan(w, s);
+  uint32_t n_hdr = 0;
+  if ((st = walk_count(ctx, w, &n_hdr))) return st;
   tr.mark(ctx, "tar open: reach + scan");
 
   // results: records, path pool, the tarballs' header ranges and statuses come back; the headers' statuses stay
-  Arena out;
-  const size_t o_recs = out.reserve((size_t)n_hdr * sizeof(ZhTarRec)), o_pool = out.reserve((size_t)n_hdr * 256),
-               o_ranges = out.reserve(n_walk * 8), o_tstat = out.reserve(n_walk * 4);
-  const size_t out_bytes = out.size;
-  const size_t o_hstat = out.reserve((size_t)n_hdr * 4);
-  DevBuf d_out;
-  if (dev_alloc(ctx, d_out, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  // (plain pointers for the launches: a launch must not take the DevBuf itself along)
-  ZhTarRec* const d_recs = carve<ZhTarRec>(d_out.p, o_recs);
-  uint32_t* const d_pool = carve<uint32_t>(d_out.p, o_pool);
-  uint32_t* const d_ranges = carve<uint32_t>(d_out.p, o_ranges);
-  int32_t* const d_tstat = carve<int32_t>(d_out.p, o_tstat);
-  int32_t* const d_hstat = carve<int32_t>(d_out.p, o_hstat);
-  if (n_hdr)
-    hipLaunchKernelGGL(zh_tar_parse_kernel, dim3((n_hdr + 3) / 4), wg, 0, s, dimgs, (uint32_t)n_walk,
-                       (const uint32_t*)ord, (const uint32_t*)list, n_hdr, d_recs, d_pool, d_hstat);
-  hipLaunchKernelGGL(zh_tar_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s, dimgs, (const uint32_t*)ord,
-                     (const int32_t*)d_hstat, d_ranges, d_tstat);
-  ZH_HIP(ctx, hipGetLastError());
-  void* h_out = nullptr;
-  {
-    size_t got = 0;
-    int32_t dst_st = ZH_OK;
-    if ((st = zhh_download(ctx, d_out.p, 1, {0}, {out_bytes}, {1}, &h_out, &got, &dst_st))) {
-      free(h_out);
-      return st;
-    }
-    own.p.push_back(h_out);
-    if (dst_st) return dst_st;
-  }
-  const uint8_t* const ho = (const uint8_t*)h_out;
-  const ZhTarRec* const recs = reinterpret_cast<const ZhTarRec*>(ho + o_recs);
-  const uint32_t* const ranges = reinterpret_cast<const uint32_t*>(ho + o_ranges);
-  const int32_t* const tstat = reinterpret_cast<const int32_t*>(ho + o_tstat);
+  TarResults<ZhTarRec> res;
+  if ((st = tar_results(ctx, stage, w, dimgs, n_walk, n_hdr,
+                        [&](ZhTarRec* d_recs, uint32_t* d_pool, int32_t* d_hstat) {
+                          hipLaunchKernelGGL(zh_tar_parse_kernel, dim3((n_hdr + 3) / 4), wg, 0, s, dimgs,
+                                             (uint32_t)n_walk, ord, list, n_hdr, d_recs, d_pool, d_hstat);
+                        },
+                        res)))
+    return st;
   tr.mark(ctx, "tar open: parse + reduce");
 
   // ---- the decoded images of the tarballs that opened ----
-  if ((st = tar_fetch(ctx, stage, tstat))) return st;
+  if ((st = tar_fetch(ctx, stage, res.tstat))) return st;
   tr.mark(ctx, "tar open: download");
 
   // ---- the readers, from the records ----
   std::vector<zh_tar_reader*> made(n_walk, nullptr);
-  bool nomem = false;
-  for (size_t k = 0; k < n_walk && !nomem; k++) {
-    if (tstat[k] != ZH_OK) continue;
-    const bool borrowed = walk[k].host < 0;
-    const uint8_t* data = borrowed ? (const uint8_t*)images[walk[k].t] : (const uint8_t*)own.p[(size_t)walk[k].host];
-    zh_tar_reader* r = zh_tar_reader_new(borrowed ? nullptr : own.p[(size_t)walk[k].host], data, (size_t)walk[k].len);
-    if (!r) {
-      nomem = true;
-      break;
-    }
-    if (!borrowed) own.p[(size_t)walk[k].host] = nullptr;  // the reader's from here on
-    made[k] = r;
-    for (uint32_t i = ranges[2 * k]; i < ranges[2 * k + 1] && !nomem; i++) {
-      const ZhTarRec& e = recs[i];
+  CloseAll close_made{made};
+  for (size_t k = 0; k < n_walk; k++) {
+    if (res.tstat[k] != ZH_OK) continue;
+    const uint8_t* data;
+    zh_tar_reader* r = made[k] = tar_reader_of(stage, k, images, &data);
+    if (!r) return ZH_ERR_NOMEM;
+    for (uint32_t i = res.ranges[2 * k]; i < res.ranges[2 * k + 1]; i++) {
+      const ZhTarRec& e = res.recs[i];
       if (!e.reported) continue;
-      const char* path = (const char*)(e.path_in_image ? data : ho + o_pool) + e.path_off;
-      nomem = zh_tar_reader_add(r, path, (size_t)e.path_len, (const char*)data + e.offset - 512 + 157, e.link_len,
-                                (char)e.typeflag, e.mode, e.mtime, e.offset, e.size) != ZH_OK;
+      const char* path = (const char*)(e.path_in_image ? data : res.pool) + e.path_off;
+      if (zh_tar_reader_add(r, path, (size_t)e.path_len, (const char*)data + e.offset - 512 + 157, e.link_len,
+                            (char)e.typeflag, e.mode, e.mtime, e.offset, e.size) != ZH_OK)
+        return ZH_ERR_NOMEM;
     }
   }
-  if (nomem) {
-    for (zh_tar_reader* r : made) zh_tar_close(r);
-    return ZH_ERR_NOMEM;
-  }
+  close_made.armed = false;
   for (size_t k = 0; k < n_walk; k++) {
     readers[walk[k].t] = made[k];
-    statuses[walk[k].t] = tstat[k];
+    statuses[walk[k].t] = res.tstat[k];
   }
   return ZH_OK;
 }

@@ -179,14 +179,9 @@ __global__ __launch_bounds__(256) void zh_tarv_parse_kernel(const ZhTarImg* __re
 
 extern "C" int zh_tar_read_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, const int32_t* formats,
                                  size_t n_tar, zh_tar_reader** readers, int32_t* statuses) {
-  if (!ctx || (n_tar && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_tar; t++) {
-    readers[t] = nullptr;
-    statuses[t] = ZH_OK;
-  }
-  for (size_t t = 0; t < n_tar; t++)
-    if ((!images[t] && lens[t]) || (formats && (formats[t] < ZH_TF_DETECT || formats[t] > ZH_TF_GZIP)))
-      return ZH_ERR_ARGUMENT;
+  if (const int e = reader_checks(ctx, images, lens, n_tar, readers, statuses)) return e;
+  for (size_t t = 0; formats && t < n_tar; t++)
+    if (formats[t] < ZH_TF_DETECT || formats[t] > ZH_TF_GZIP) return ZH_ERR_ARGUMENT;
   if (!n_tar) return ZH_OK;
 
   // ---- classify: the format, lengths and the first two bytes only (tarballs_v1.nim:79-96, gzip.nim:10-11) ----
@@ -216,14 +211,7 @@ extern "C" int zh_tar_read_batch(zh_ctx* ctx, const void* const* images, const s
     }
   }
   std::vector<zh_tar_reader*> made_empty(empty.size(), nullptr);
-  struct CloseAll {
-    std::vector<zh_tar_reader*>& v;
-    bool armed = true;
-    ~CloseAll() {
-      if (armed)
-        for (zh_tar_reader* r : v) zh_tar_close(r);
-    }
-  } close_empty{made_empty};
+  CloseAll close_empty{made_empty};
   for (size_t k = 0; k < empty.size(); k++)
     if (!(made_empty[k] = zh_tar_reader_new(nullptr, images[empty[k]], 0))) return ZH_ERR_NOMEM;
   auto hand_out_empty = [&]() {
@@ -240,90 +228,47 @@ extern "C" int zh_tar_read_batch(zh_ctx* ctx, const void* const* images, const s
   TarStage stage;
   if ((st = tar_stage(ctx, images, lens, plain, gz, statuses, tr, "tar read: upload", "tar read: decode", stage)))
     return st;
-  std::vector<TarWalk>& walk = stage.walk;
-  HostBufs& own = stage.own;
+  const std::vector<TarWalk>& walk = stage.walk;
   const size_t n_walk = walk.size();
   if (!n_walk) return hand_out_empty();
 
-  // ---- the walk ----
+  // ---- the walk (zh_walk.h); behind its scratch a byte a node for "gets a record" ----
   std::vector<ZhTarImg> imgs;
   uint32_t N = 0, rounds = 0;
   if ((st = tar_nodes(walk, imgs, &N, &rounds))) return st;
-  const uint32_t n_sums = (N + kScanItems - 1) / kScanItems;
-  DevBuf d_imgs, d_scr;
+  DevBuf d_imgs;
   std::vector<uint64_t> ioff;
   if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_walk * sizeof(ZhTarImg)}}, d_imgs, ioff))) return st;
-  // scratch: two jump arrays, the marks, the ordinals -- 4 bytes a node each --, a byte a node for "gets a record",
-  // and the scan's workgroup sums
-  Arena ar;
-  const size_t o_j0 = ar.reserve((size_t)N * 4), o_j1 = ar.reserve((size_t)N * 4), o_mark = ar.reserve((size_t)N * 4),
-               o_ord = ar.reserve((size_t)N * 4), o_sums = ar.reserve(((size_t)n_sums + 1) * 4),
-               o_rec = ar.reserve((size_t)N);
-  if (dev_alloc(ctx, d_scr, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
-  uint32_t* const j0 = carve<uint32_t>(d_scr.p, o_j0);
-  uint32_t* const j1 = carve<uint32_t>(d_scr.p, o_j1);
-  uint32_t* const mark = carve<uint32_t>(d_scr.p, o_mark);
-  uint32_t* const ord = carve<uint32_t>(d_scr.p, o_ord);
-  uint32_t* const sums = carve<uint32_t>(d_scr.p, o_sums);
-  uint8_t* const rec = carve<uint8_t>(d_scr.p, o_rec);
+  Walk w;
+  if ((st = walk_alloc(ctx, w, N, N))) return st;
+  // (plain pointers for the launches: a launch must not take a DevBuf, or the Walk that holds one, along)
   const ZhTarImg* const dimgs = reinterpret_cast<const ZhTarImg*>(d_imgs.p);
+  uint32_t *const j0 = w.j0, *const mark = w.mark;
+  const uint32_t* const list = w.list;
+  uint8_t* const rec = w.extra;
   const dim3 node_grid((N + 255) / 256), wg(256);
   hipStream_t s = ctx->stream;
   hipLaunchKernelGGL(zh_tarv_next_kernel, node_grid, wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark, rec);
-  uint32_t *jin = j0, *jout = j1;
-  for (uint32_t r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(zh_walk_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
-    std::swap(jin, jout);
-  }
+  walk_double(w, rounds, s);
   hipLaunchKernelGGL(zh_tarv_select_kernel, node_grid, wg, 0, s, mark, (const uint8_t*)rec, N);
-  // (the jump arrays are dead from here on: the list of headers takes the place of the first)
-  uint32_t* const list = j0;
-  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
-  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
-  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
-                     (const uint32_t*)sums, ord, list);
-  ZH_HIP(ctx, hipGetLastError());
-  uint32_t n_hdr = 0;  // the records are sized by the named headers there are, not by the blocks
-  ZH_HIP(ctx, hipMemcpyAsync(&n_hdr, sums + n_sums, 4, hipMemcpyDeviceToHost, s));
-  ZH_HIP(ctx, hipStreamSynchronize(s));
+  walk_scan(w, s);
+  uint32_t n_hdr = 0;  // the named headers
+  if ((st = walk_count(ctx, w, &n_hdr))) return st;
   tr.mark(ctx, "tar read: reach + scan");
 
   // results: records, key pool, the tarballs' header ranges and statuses come back; the headers' statuses stay
-  Arena out;
-  const size_t o_recs = out.reserve((size_t)n_hdr * sizeof(ZhTarvRec)), o_pool = out.reserve((size_t)n_hdr * 256),
-               o_ranges = out.reserve(n_walk * 8), o_tstat = out.reserve(n_walk * 4);
-  const size_t out_bytes = out.size;
-  const size_t o_hstat = out.reserve((size_t)n_hdr * 4);
-  DevBuf d_out;
-  if (dev_alloc(ctx, d_out, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  // (plain pointers for the launches: a launch must not take the DevBuf itself along)
-  ZhTarvRec* const d_recs = carve<ZhTarvRec>(d_out.p, o_recs);
-  uint32_t* const d_pool = carve<uint32_t>(d_out.p, o_pool);
-  uint32_t* const d_ranges = carve<uint32_t>(d_out.p, o_ranges);
-  int32_t* const d_tstat = carve<int32_t>(d_out.p, o_tstat);
-  int32_t* const d_hstat = carve<int32_t>(d_out.p, o_hstat);
-  if (n_hdr)
-    hipLaunchKernelGGL(zh_tarv_parse_kernel, dim3((n_hdr + 3) / 4), wg, 0, s, dimgs, (uint32_t)n_walk,
-                       (const uint32_t*)list, n_hdr, d_recs, d_pool, d_hstat);
-  hipLaunchKernelGGL(zh_tar_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s, dimgs, (const uint32_t*)ord,
-                     (const int32_t*)d_hstat, d_ranges, d_tstat);
-  ZH_HIP(ctx, hipGetLastError());
-  void* h_out = nullptr;
-  {
-    size_t got = 0;
-    int32_t dst_st = ZH_OK;
-    if ((st = zhh_download(ctx, d_out.p, 1, {0}, {out_bytes}, {1}, &h_out, &got, &dst_st))) {
-      free(h_out);
-      return st;
-    }
-    own.p.push_back(h_out);
-    if (dst_st) return dst_st;
-  }
-  const uint8_t* const ho = (const uint8_t*)h_out;
-  const ZhTarvRec* const recs = reinterpret_cast<const ZhTarvRec*>(ho + o_recs);
-  const char* const keys = (const char*)(ho + o_pool);
-  const uint32_t* const ranges = reinterpret_cast<const uint32_t*>(ho + o_ranges);
-  const int32_t* const tstat = reinterpret_cast<const int32_t*>(ho + o_tstat);
+  TarResults<ZhTarvRec> res;
+  if ((st = tar_results(ctx, stage, w, dimgs, n_walk, n_hdr,
+                        [&](ZhTarvRec* d_recs, uint32_t* d_pool, int32_t* d_hstat) {
+                          hipLaunchKernelGGL(zh_tarv_parse_kernel, dim3((n_hdr + 3) / 4), wg, 0, s, dimgs,
+                                             (uint32_t)n_walk, list, n_hdr, d_recs, d_pool, d_hstat);
+                        },
+                        res)))
+    return st;
+  const ZhTarvRec* const recs = res.recs;
+  const char* const keys = (const char*)res.pool;
+  const uint32_t* const ranges = res.ranges;
+  const int32_t* const tstat = res.tstat;
   tr.mark(ctx, "tar read: parse + reduce");
 
   // ---- the decoded images of the tarballs that opened ----
@@ -338,12 +283,9 @@ extern "C" int zh_tar_read_batch(zh_ctx* ctx, const void* const* images, const s
     std::vector<uint32_t> table;  // ordinals, in the table's order
     for (size_t k = 0; k < n_walk; k++) {
       if (tstat[k] != ZH_OK) continue;
-      const bool borrowed = walk[k].host < 0;
-      const uint8_t* data = borrowed ? (const uint8_t*)images[walk[k].t] : (const uint8_t*)own.p[(size_t)walk[k].host];
-      zh_tar_reader* r = zh_tar_reader_new(borrowed ? nullptr : own.p[(size_t)walk[k].host], data, (size_t)walk[k].len);
+      const uint8_t* data;
+      zh_tar_reader* r = made[k] = tar_reader_of(stage, k, images, &data);
       if (!r) return ZH_ERR_NOMEM;
-      if (!borrowed) own.p[(size_t)walk[k].host] = nullptr;  // the reader's from here on
-      made[k] = r;
       place.clear();
       table.clear();
       for (uint32_t i = ranges[2 * k]; i < ranges[2 * k + 1]; i++) {

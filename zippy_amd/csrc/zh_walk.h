@@ -1,11 +1,13 @@
-// What the batch readers' walks share (zh_tar_open_batch.hip, zh_zip_open_batch.hip): a chain of records whose
-// positions are sums of the variable lengths before them is found in parallel.  Every candidate position ("node") gets
-// next[b] as if a record started there; the nodes reachable from a start ARE the records:
+// What the four batch readers' walks share (zh_tar_open_batch.hip, zh_tar_read_batch.hip, zh_zip_open_batch.hip,
+// zh_zip_read_batch.hip): a chain of records whose positions are sums of the variable lengths before them is found in
+// parallel.  Every candidate position ("node") gets next[b] as if a record started there; the nodes reachable from a
+// start ARE the records:
 //   zh_walk_double_kernel  pointer doubling with marks
 //   zh_walk_scan_*         a prefix sum over the marks: every record's ordinal in walk order, the list of records
+// and the host half that launches them (Walk).  What a node is, and next[b], is the caller's.
 // The kernels have internal linkage: each file that includes this header launches its own copy.
 #pragma once
-#include "zh_common.h"
+#include "zh_host.h"
 
 namespace {
 
@@ -86,6 +88,58 @@ __global__ __launch_bounds__(256) void zh_walk_scan_write_kernel(const uint32_t*
     }
     carry += total;
   }
+}
+
+// The walk's scratch: two jump arrays, the marks, the ordinals -- 4 bytes a node each --, the scan's workgroup sums,
+// and `extra` bytes of the caller's behind them.  The caller's `next` kernel fills j0 and mark.
+struct Walk {
+  DevBuf scr;
+  uint32_t N = 0, n_sums = 0;
+  uint32_t *j0 = nullptr, *j1 = nullptr, *mark = nullptr, *ord = nullptr, *sums = nullptr;
+  uint32_t* list = nullptr;  // = j0: the jump arrays are dead behind the doubling, the list of records takes their place
+  uint8_t* extra = nullptr;
+};
+inline int walk_alloc(zh_ctx* ctx, Walk& w, uint32_t n_nodes, size_t extra = 0) {
+  const size_t N = w.N = n_nodes;
+  w.n_sums = (n_nodes + kScanItems - 1) / kScanItems;
+  Arena ar;
+  const size_t o_j0 = ar.reserve(N * 4), o_j1 = ar.reserve(N * 4), o_mark = ar.reserve(N * 4), o_ord = ar.reserve(N * 4),
+               o_sums = ar.reserve(((size_t)w.n_sums + 1) * 4), o_extra = ar.reserve(extra);
+  if (dev_alloc(ctx, w.scr, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
+  w.list = w.j0 = carve<uint32_t>(w.scr.p, o_j0);
+  w.j1 = carve<uint32_t>(w.scr.p, o_j1);
+  w.mark = carve<uint32_t>(w.scr.p, o_mark);
+  w.ord = carve<uint32_t>(w.scr.p, o_ord);
+  w.sums = carve<uint32_t>(w.scr.p, o_sums);
+  w.extra = w.scr.p + o_extra;
+  return ZH_OK;
+}
+// `rounds` rounds of doubling on stream s: every node up to 2^rounds - 1 steps from a start is marked.
+// (Plain pointers for the launches here and below: a launch must not take the Walk, that is its DevBuf, along.)
+inline void walk_double(const Walk& w, uint32_t rounds, hipStream_t s) {
+  const uint32_t N = w.N;
+  uint32_t *jin = w.j0, *jout = w.j1, *const mark = w.mark;
+  for (uint32_t r = 0; r < rounds; r++) {
+    hipLaunchKernelGGL(zh_walk_double_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (const uint32_t*)jin, jout, mark, N);
+    std::swap(jin, jout);
+  }
+}
+// ... then the scan over the marks: ord[] and list[]; nothing is waited for
+inline void walk_scan(const Walk& w, hipStream_t s) {
+  const uint32_t N = w.N, n_sums = w.n_sums;
+  uint32_t *const mark = w.mark, *const sums = w.sums, *const ord = w.ord, *const list = w.list;
+  const dim3 wg(256);
+  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
+  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
+  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
+                     (const uint32_t*)sums, ord, list);
+}
+// ... and the number of records comes back (what follows is sized by them, not by the nodes): this waits
+inline int walk_count(zh_ctx* ctx, const Walk& w, uint32_t* n_rec) {
+  ZH_HIP(ctx, hipGetLastError());
+  ZH_HIP(ctx, hipMemcpyAsync(n_rec, w.sums + w.n_sums, 4, hipMemcpyDeviceToHost, ctx->stream));
+  ZH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ZH_OK;
 }
 
 }  // namespace

@@ -12,6 +12,7 @@
 //                         layout of the output; ONE uncompress plan over every deflated entry of the call, its
 //                         sources in place in the uploaded images
 //   zh_zip_finish_kernel  stored entries copied image -> slot, every entry's CRC-32 held against its record
+//                         (zh_zip_dev.h, with the host stages around it)
 // The host parses no central record and no local header, compares no CRC and copies no entry.
 //
 // Scratch of the walk: 16 bytes per node -- two jump arrays, the marks, the ordinals, 4 bytes each.  A node is a byte
@@ -23,15 +24,12 @@
 // bytes, so those reads stay inside it whatever an archive's last byte is.
 #include <unordered_set>
 
-#include "zh_host.h"
-#include "zh_gather.h"
 #include "zh_walk.h"
 #include "zh_zip_dev.h"
 
 namespace {
 
 constexpr uint32_t kLocalSig = 0x04034b50u, kCentralSig = 0x02014b50u;
-constexpr uint64_t kSlice = 32768;  // bytes of a stored entry a wave copies at most
 constexpr uint64_t kRecordMax = 46 + 3 * 65535;  // the longest central record: name, extra and comment of 65535 bytes
 
 // One archive of the walk.  All archives of a call share one index space of nodes: this one's are node0 + k for the
@@ -63,19 +61,6 @@ struct ZhZipRec {
   uint8_t directory, from_cp437, after_dup, unsafe;
 };
 
-// One file entry of an archive that opened, for zh_zip_finish_kernel
-struct ZhZipFin {
-  uint64_t src, dst, len;  // a stored entry: len bytes from upload buffer + src to output buffer + dst
-  uint32_t want_crc;
-  int32_t local_status;    // not ZH_OK: nothing to extract, this is the entry's status
-  uint32_t deflated;       // 1: result `idx` of the plan; 0: stored entry `idx` of the checksum launch
-  uint32_t idx;
-};
-struct ZhZipFinTask {
-  uint64_t lo, hi;  // bytes [lo, hi) of the entry's data
-  uint32_t entry, first;
-};
-
 __device__ __forceinline__ uint32_t find_img(const ZhZipImg* __restrict__ imgs, uint32_t n_img, uint32_t node) {
   uint32_t lo = 0, hi = n_img;  // the last archive whose node0 <= node
   while (hi - lo > 1) {
@@ -86,16 +71,6 @@ __device__ __forceinline__ uint32_t find_img(const ZhZipImg* __restrict__ imgs, 
       hi = mid;
   }
   return lo;
-}
-
-// internal.nim:294-302 verifyPathIsSafeToExtract on the four bytes x of a path that start at position `at`.  The
-// rule looks at ASCII bytes only, and utf8ify (ziparchives.nim:108-160) keeps every ASCII byte and turns a byte
-// >= 0x80 into bytes >= 0x80: the raw name is unsafe exactly when the converted path is, so the raw name is checked.
-// (The same rule as zh_tar_open_batch.hip's.)
-__device__ __forceinline__ bool unsafe_at(uint32_t x, uint64_t at) {
-  if (x == 0x2f2e2e2fu || x == 0x5c2e2e5cu) return true;  // "/../", "\..\"
-  if (at != 0) return false;
-  return (x & 0xffu) == '/' || (x & 0xffffffu) == 0x2f2e2eu || (x & 0xffffffu) == 0x5c2e2eu;  // "/", "../", "..\"
 }
 
 }  // namespace
@@ -188,6 +163,8 @@ __global__ __launch_bounds__(256) void zh_zip_parse_kernel(const ZhZipImg* __res
           } else {
             bad = true;
           }
+          // (the path rule looks at ASCII bytes only, and utf8ify (ziparchives.nim:108-160) keeps every ASCII byte and
+          // turns a byte >= 0x80 into bytes >= 0x80: the raw name is unsafe exactly when the converted path is)
           risky = risky || unsafe_at(c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), (uint64_t)j);
         }
         const bool invalid_utf8 = __ballot(bad) != 0;
@@ -275,57 +252,9 @@ __global__ __launch_bounds__(256) void zh_zip_ranges_kernel(const ZhZipImg* __re
   ranges[2 * a + 1] = first + (uint32_t)((uint64_t)found < g.num_records ? (uint64_t)found : g.num_records);
 }
 
-// One wave per task (four a workgroup): a slice of a stored entry's bytes goes from its image to its slot -- the
-// bytes in front of the first and behind the last aligned 16-byte chunk of the slot one a lane, the chunks in between
-// with one 16-byte store each, their bytes gathered from the (differently aligned) source.  The wave of an entry's
-// first task also settles the entry: a local header that failed, else the decoder's status (deflated entries: the
-// plan's status, length and CRC-32), else the CRC-32 against the record's (:91-92).
-__global__ __launch_bounds__(256) void zh_zip_finish_kernel(const uint8_t* __restrict__ d_in, uint8_t* __restrict__ d_out,
-                                                            const ZhZipFin* __restrict__ fins,
-                                                            const ZhZipFinTask* __restrict__ tasks, uint32_t n_tasks,
-                                                            const int32_t* __restrict__ plan_st,
-                                                            const uint64_t* __restrict__ plan_len,
-                                                            const uint32_t* __restrict__ plan_crc,
-                                                            const uint32_t* __restrict__ stored_crc,
-                                                            int32_t* __restrict__ est, uint64_t* __restrict__ elen) {
-  const uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = zh_lane();
-  if (w >= n_tasks) return;
-  const ZhZipFinTask t = tasks[w];
-  const ZhZipFin e = fins[t.entry];
-  if (t.first && lane == 0) {
-    int32_t st = e.local_status;
-    uint64_t len = 0;
-    if (st == ZH_OK) {
-      st = e.deflated ? plan_st[e.idx] : ZH_OK;
-      const uint32_t crc = e.deflated ? plan_crc[e.idx] : stored_crc[e.idx];
-      len = e.deflated ? plan_len[e.idx] : e.len;
-      if (st == ZH_OK && crc != e.want_crc) st = ZH_ERR_ZIP_CRC;
-      if (st != ZH_OK) len = 0;
-    }
-    est[t.entry] = st;
-    elen[t.entry] = len;
-  }
-  if (t.lo >= t.hi) return;
-  const uint64_t a = e.dst + t.lo, b = e.dst + t.hi, delta = e.src - e.dst;  // (source byte = slot byte + delta, mod 2^64)
-  const uint64_t A = (a + 15) & ~(uint64_t)15, B = b & ~(uint64_t)15;
-  if (A >= B) {  // no whole chunk inside: at most 30 bytes
-    if (a + lane < b) d_out[a + lane] = d_in[a + lane + delta];
-    return;
-  }
-  if (a + lane < A) d_out[a + lane] = d_in[a + lane + delta];
-  if (B + lane < b) d_out[B + lane] = d_in[B + lane + delta];
-  for (uint64_t c = A + 16ull * lane; c < B; c += 1024) *reinterpret_cast<Chunk16*>(d_out + c) = gather16(d_in, c + delta);
-}
-
 extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n_zip,
                                      zh_zip_reader** readers, int32_t* statuses) {
-  if (!ctx || (n_zip && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_zip; t++) {
-    readers[t] = nullptr;
-    statuses[t] = ZH_OK;
-  }
-  for (size_t t = 0; t < n_zip; t++)
-    if (!images[t] && lens[t]) return ZH_ERR_ARGUMENT;
+  if (const int e = reader_checks(ctx, images, lens, n_zip, readers, statuses)) return e;
   if (!n_zip) return ZH_OK;
 
   // ---- 1. the directories (host: the end records only) ----
@@ -381,52 +310,28 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
   // after `rounds` rounds every node up to 2^rounds - 1 steps from a start is marked; max_chain records are wanted
   uint32_t rounds = 0;
   while ((1ull << rounds) < max_chain + 1) rounds++;
-  const uint32_t N = (uint32_t)n_nodes, n_sums = (N + kScanItems - 1) / kScanItems;
-  DevBuf d_imgs, d_scr;
+  const uint32_t N = (uint32_t)n_nodes;
+  DevBuf d_imgs;
   std::vector<uint64_t> ioff;
   if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_walk * sizeof(ZhZipImg)}}, d_imgs, ioff))) return st;
-  Arena ar;
-  const size_t o_j0 = ar.reserve((size_t)N * 4), o_j1 = ar.reserve((size_t)N * 4), o_mark = ar.reserve((size_t)N * 4),
-               o_ord = ar.reserve((size_t)N * 4), o_sums = ar.reserve(((size_t)n_sums + 1) * 4);
-  if (dev_alloc(ctx, d_scr, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
-  uint32_t* const j0 = carve<uint32_t>(d_scr.p, o_j0);
-  uint32_t* const j1 = carve<uint32_t>(d_scr.p, o_j1);
-  uint32_t* const mark = carve<uint32_t>(d_scr.p, o_mark);
-  uint32_t* const ord = carve<uint32_t>(d_scr.p, o_ord);
-  uint32_t* const sums = carve<uint32_t>(d_scr.p, o_sums);
+  Walk w;
+  if ((st = walk_alloc(ctx, w, N))) return st;
+  // (plain pointers for the launches: a launch must not take a DevBuf, or the Walk that holds one, along)
   const ZhZipImg* const dimgs = reinterpret_cast<const ZhZipImg*>(d_imgs.p);
-  const dim3 node_grid((N + 255) / 256);
-  struct Events {  // ZH_TRACE: the walk's kernels by themselves, between two events that go away with the scope
-    hipEvent_t e[2] = {nullptr, nullptr};
-    bool ok = false;
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  if (tr.on) evs.ok = hipEventCreate(&evs.e[0]) == hipSuccess && hipEventCreate(&evs.e[1]) == hipSuccess;
-  hipEvent_t* const ev = evs.e;
-  if (evs.ok) (void)hipEventRecord(ev[0], s);
-  hipLaunchKernelGGL(zh_zip_next_kernel, node_grid, wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark);
-  uint32_t *jin = j0, *jout = j1;
-  for (uint32_t r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(zh_walk_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
-    std::swap(jin, jout);
-  }
-  // (the jump arrays are dead from here on: the list of records takes the place of the first)
-  uint32_t* const list = j0;
-  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
-  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
-  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N,
-                     (const uint32_t*)sums, ord, list);
-  if (evs.ok) (void)hipEventRecord(ev[1], s);
-  ZH_HIP(ctx, hipGetLastError());
-  uint32_t n_rec = 0;  // the records are sized by the marks there are, not by the nodes
-  ZH_HIP(ctx, hipMemcpyAsync(&n_rec, sums + n_sums, 4, hipMemcpyDeviceToHost, s));
-  ZH_HIP(ctx, hipStreamSynchronize(s));
+  uint32_t *const j0 = w.j0, *const mark = w.mark;
+  const uint32_t *const ord = w.ord, *const list = w.list;
+  Events evs;  // ZH_TRACE: the walk's kernels by themselves
+  if (tr.on) evs.create();
+  if (evs.ok) (void)hipEventRecord(evs.e[0], s);
+  hipLaunchKernelGGL(zh_zip_next_kernel, dim3((N + 255) / 256), wg, 0, s, dimgs, (uint32_t)n_walk, N, j0, mark);
+  walk_double(w, rounds, s);
+  walk_scan(w, s);
+  if (evs.ok) (void)hipEventRecord(evs.e[1], s);
+  uint32_t n_rec = 0;
+  if ((st = walk_count(ctx, w, &n_rec))) return st;
   if (evs.ok) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+    const float ms = evs.ms(0, 1);
+    if (ms >= 0)
       fprintf(stderr, "[zh] %-28s %8.3f ms (HIP events; %u nodes, %u rounds)\n", "zip open: walk kernels", ms, N, rounds);
   }
   tr.mark(ctx, "zip open: reach + scan");
@@ -441,10 +346,10 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
   if (dev_alloc(ctx, d_rec, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
   if (n_rec)
     hipLaunchKernelGGL(zh_zip_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, dimgs, (uint32_t)n_walk,
-                       (const uint32_t*)ord, (const uint32_t*)list, n_rec, carve<ZhZipRec>(d_rec.p, o_recs),
+                       ord, list, n_rec, carve<ZhZipRec>(d_rec.p, o_recs),
                        carve<int32_t>(d_rec.p, o_rstat), carve<uint8_t>(d_rec.p, o_rflag));
   hipLaunchKernelGGL(zh_zip_ranges_kernel, dim3(((uint32_t)n_walk + 255) / 256), wg, 0, s, dimgs, (uint32_t)n_walk,
-                     (const uint32_t*)ord, carve<uint32_t>(d_rec.p, o_ranges));
+                     ord, carve<uint32_t>(d_rec.p, o_ranges));
   hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s,
                      (const uint32_t*)carve<uint32_t>(d_rec.p, o_ranges), (const int32_t*)carve<int32_t>(d_rec.p, o_rstat),
                      (const uint8_t*)carve<uint8_t>(d_rec.p, o_rflag), carve<uint32_t>(d_rec.p, o_bad),
@@ -470,12 +375,8 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
   Readers made;
   made.r.assign(n_walk, nullptr);
   std::vector<int32_t> ast(n_walk, ZH_OK);
-  struct Slot {  // a file entry of an archive that is extracted
-    size_t walk, entry;
-    const ZhZipRec* rec;
-    uint64_t dst = 0, cap = 0;
-  };
-  std::vector<Slot> slots;
+  std::vector<ZipSlot> slots;  // the file entries of the archives that are extracted
+  std::vector<uint32_t> eranges(2 * n_walk, 0);  // an archive's slots are contiguous
   std::vector<uint64_t> aoff(n_walk, 0), alen(n_walk, 0);
   uint64_t out_total = 0;
   for (size_t k = 0; k < n_walk; k++) {
@@ -520,10 +421,11 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
     }
     out_total = (out_total + 15) & ~(uint64_t)15;  // (the download moves a block 16 bytes at a time)
     aoff[k] = out_total;
+    eranges[2 * k] = (uint32_t)slots.size();
     for (uint32_t i = lo; i < hi; i++) {
       const ZhZipRec& e = recs[i];
       if (e.directory) continue;
-      Slot sl{k, (size_t)(i - lo), &e};
+      ZipSlot sl{k, i, e.src_off, e.src_len, 0, 0, e.crc, 0, e.local_status, e.local_method};
       if (e.local_status == ZH_OK) {
         // (what zh_uncompress_batch_sized makes of zh_zip_extract_batch's hint: never above its expansion bound)
         sl.cap = e.local_method == 8 ? std::min<uint64_t>(e.cap, e.src_len * 1032 + 64) : e.cap;
@@ -532,196 +434,43 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
       }
       slots.push_back(sl);
     }
+    eranges[2 * k + 1] = (uint32_t)slots.size();
     alen[k] = out_total - aoff[k];
   }
   const size_t n_slot = slots.size();
-  std::vector<size_t> slot_lo(n_walk, 0), slot_hi(n_walk, 0);  // an archive's slots are contiguous
-  for (size_t j = 0; j < n_slot; j++) {
-    if (!j || slots[j - 1].walk != slots[j].walk) slot_lo[slots[j].walk] = j;
-    slot_hi[slots[j].walk] = j + 1;
-  }
   if (n_slot >= 0xffffffffull) return ZH_ERR_ARGUMENT;
   tr.mark(ctx, "zip open: readers");
 
-  // ---- 6. one decode; 7. the stored entries and every verdict ----
-  std::vector<int32_t> est(n_slot, ZH_OK);
-  std::vector<uint64_t> elen(n_slot, 0);
+  // ---- 6. one decode; 7. the stored entries and every verdict; 8. one download: every archive's block ----
+  std::vector<int32_t> est;
+  std::vector<uint64_t> elen;
   std::vector<uint32_t> ebad(n_walk, kNone);
   std::vector<void*> blocks(n_walk, nullptr);
-  size_t blocks_at = 0;  // blocks[k] is own.p[blocks_at + k] until a reader takes it
+  size_t blocks_at = 0;
   if (n_slot) {
-    std::vector<ZhZipFin> fins(n_slot);
-    std::vector<ZhZipFinTask> tasks;
-    std::vector<uint64_t> p_soff, p_slen, p_doff, p_dcap;
-    std::vector<ZhPieceDesc> pieces;
-    std::vector<ZhBufDesc> sbufs;
-    std::vector<uint32_t> eranges(2 * n_walk, 0);
-    for (size_t j = 0; j < n_slot; j++) {
-      const Slot& sl = slots[j];
-      const ZhZipRec& e = *sl.rec;
-      if (!j || slots[j - 1].walk != sl.walk) eranges[2 * sl.walk] = (uint32_t)j;
-      eranges[2 * sl.walk + 1] = (uint32_t)j + 1;
-      ZhZipFin& f = fins[j];
-      f = ZhZipFin{e.src_off, sl.dst, 0, e.crc, e.local_status, 0, 0};
-      uint64_t copy = 0;
-      if (e.local_status == ZH_OK && e.local_method == 8) {
-        f.deflated = 1;
-        f.idx = (uint32_t)p_soff.size();
-        p_soff.push_back(e.src_off);
-        p_slen.push_back(e.src_len);
-        p_doff.push_back(sl.dst);
-        p_dcap.push_back(sl.cap);
-      } else if (e.local_status == ZH_OK) {
-        f.len = copy = e.src_len;
-        f.idx = (uint32_t)sbufs.size();
-        ZhBufDesc b;
-        memset(&b, 0, sizeof(b));
-        b.src_off = e.src_off;
-        b.src_len = copy;
-        b.first_piece = (uint32_t)pieces.size();
-        for (uint64_t o = 0; o < copy; o += ZH_FRAG_SIZE)
-          pieces.push_back(ZhPieceDesc{e.src_off + o, (uint32_t)std::min<uint64_t>(copy - o, ZH_FRAG_SIZE), f.idx, o});
-        b.npieces = (uint32_t)pieces.size() - b.first_piece;
-        sbufs.push_back(b);
-      }
-      uint32_t first = 1;
-      for (uint64_t o = 0; first || o < copy; o += kSlice, first = 0)
-        tasks.push_back(ZhZipFinTask{o, std::min<uint64_t>(copy, o + kSlice), (uint32_t)j, first});
-    }
-    const size_t n_def = p_soff.size(), n_sto = sbufs.size(), n_piece = pieces.size(), n_task = tasks.size();
-    if (n_task >= 0xffffffffull || n_piece >= 0xffffffffull) return ZH_ERR_ARGUMENT;
-    DevBuf d_out, d_fin;
-    if (dev_alloc(ctx, d_out, out_total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    Arena fa;
-    const size_t o_fins = fa.reserve(n_slot * sizeof(ZhZipFin)), o_tasks = fa.reserve(n_task * sizeof(ZhZipFinTask)),
-                 o_sbufs = fa.reserve(n_sto * sizeof(ZhBufDesc)), o_pieces = fa.reserve(n_piece * sizeof(ZhPieceDesc)),
-                 o_er = fa.reserve(n_walk * 8);
-    const size_t fa_in = fa.size;
-    const size_t o_pcrc = fa.reserve(n_piece * 4), o_pad = fa.reserve(n_piece * 4), o_plen = fa.reserve(n_piece * 4),
-                 o_scrc = fa.reserve(n_sto * 4), o_sad = fa.reserve(n_sto * 4), o_est = fa.reserve(n_slot * 4),
-                 o_elen = fa.reserve(n_slot * 8), o_ebad = fa.reserve(n_walk * 4), o_eany = fa.reserve(n_walk * 4);
-    if (dev_alloc(ctx, d_fin, fa.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    {
-      std::vector<uint8_t> h(fa_in);
-      memcpy(h.data() + o_fins, fins.data(), n_slot * sizeof(ZhZipFin));
-      memcpy(h.data() + o_tasks, tasks.data(), n_task * sizeof(ZhZipFinTask));
-      if (n_sto) memcpy(h.data() + o_sbufs, sbufs.data(), n_sto * sizeof(ZhBufDesc));
-      if (n_piece) memcpy(h.data() + o_pieces, pieces.data(), n_piece * sizeof(ZhPieceDesc));
-      memcpy(h.data() + o_er, eranges.data(), n_walk * 8);
-      const void* src = h.data();
-      if ((st = zhh_upload_slices(ctx, &src, {0}, {(uint64_t)fa_in}, fa_in, d_fin.p))) return st;
-    }
-    PlanGuard pg;
-    if (n_def) {
-      if ((st = zh_plan_uncompress(ctx, n_def, p_soff.data(), p_slen.data(), p_doff.data(), p_dcap.data(),
-                                   ZH_DF_DEFLATE, &pg.p)) ||
-          (st = zh_plan_request_crc32(pg.p, 1)))
-        return st;
-      if (tr.on) zh_plan_set_profiling(pg.p, 1);
-      if ((st = zh_plan_run(pg.p, d_in.p, d_out.p))) return st;
-      if (tr.on) {
-        const char* names[64];
-        float ms[64];
-        const int nk = zh_plan_kernel_times(pg.p, names, ms, 64);
-        for (int i = 0; i < nk && i < 64; i++) fprintf(stderr, "[zh]   plan kernel %-24s %8.3f ms\n", names[i], ms[i]);
-      }
-    }
-    tr.mark(ctx, "zip open: decode");
-    zh_launch_checksum_pieces(s, ctx->cktabs, d_in.p, carve<ZhPieceDesc>(d_fin.p, o_pieces), (uint32_t)n_piece, nullptr,
-                              1, 0, carve<uint32_t>(d_fin.p, o_pcrc), carve<uint32_t>(d_fin.p, o_pad),
-                              carve<uint32_t>(d_fin.p, o_plen));
-    zh_launch_checksum_combine(s, ctx->cktabs, carve<ZhBufDesc>(d_fin.p, o_sbufs), (uint32_t)n_sto,
-                               carve<uint32_t>(d_fin.p, o_pcrc), carve<uint32_t>(d_fin.p, o_pad),
-                               carve<uint32_t>(d_fin.p, o_plen), 1, 0, carve<uint32_t>(d_fin.p, o_scrc),
-                               carve<uint32_t>(d_fin.p, o_sad));
-    // (plain pointers: a launch must not take the guard of the plan along)
-    const int32_t* const plan_st = n_def ? zh_plan_device_statuses(pg.p) : nullptr;
-    const uint64_t* const plan_len = n_def ? zh_plan_device_lens(pg.p) : nullptr;
-    const uint32_t* const plan_crc = n_def ? pg.p->buf_crc : nullptr;
-    const uint8_t* const in = d_in.p;
-    uint8_t* const outp = d_out.p;
-    hipLaunchKernelGGL(zh_zip_finish_kernel, dim3(((uint32_t)n_task + 3) / 4), wg, 0, s, in, outp,
-                       (const ZhZipFin*)carve<ZhZipFin>(d_fin.p, o_fins),
-                       (const ZhZipFinTask*)carve<ZhZipFinTask>(d_fin.p, o_tasks), (uint32_t)n_task,
-                       plan_st, plan_len, plan_crc,
-                       (const uint32_t*)carve<uint32_t>(d_fin.p, o_scrc), carve<int32_t>(d_fin.p, o_est),
-                       carve<uint64_t>(d_fin.p, o_elen));
-    hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s,
-                       (const uint32_t*)carve<uint32_t>(d_fin.p, o_er), (const int32_t*)carve<int32_t>(d_fin.p, o_est),
-                       (const uint8_t*)nullptr, carve<uint32_t>(d_fin.p, o_ebad), carve<uint32_t>(d_fin.p, o_eany));
-    ZH_HIP(ctx, hipGetLastError());
-    ZH_HIP(ctx, hipMemcpyAsync(est.data(), d_fin.p + o_est, n_slot * 4, hipMemcpyDeviceToHost, s));
-    ZH_HIP(ctx, hipMemcpyAsync(elen.data(), d_fin.p + o_elen, n_slot * 8, hipMemcpyDeviceToHost, s));
-    ZH_HIP(ctx, hipMemcpyAsync(ebad.data(), d_fin.p + o_ebad, n_walk * 4, hipMemcpyDeviceToHost, s));
-    ZH_HIP(ctx, hipStreamSynchronize(s));
-    tr.mark(ctx, "zip open: finish");
-
-    // ---- 8. one download: every archive's block ----
+    DevBuf d_out;
+    if ((st = zip_extract(ctx, tr, "zip open", slots, eranges, d_in.p, out_total, false, d_out, est, &elen, ebad)))
+      return st;
     std::vector<char> take(n_walk, 0);
     for (size_t k = 0; k < n_walk; k++) take[k] = made.r[k] && ast[k] == ZH_OK && alen[k] ? 1 : 0;
-    std::vector<size_t> blen(n_walk, 0);
-    std::vector<int32_t> bst(n_walk, ZH_OK);
-    st = zhh_download(ctx, d_out.p, n_walk, aoff, alen, take, blocks.data(), blen.data(), bst.data());
-    blocks_at = own.p.size();
-    own.p.insert(own.p.end(), blocks.begin(), blocks.end());
-    if (st) return st;
-    for (size_t k = 0; k < n_walk; k++)
-      if (take[k] && bst[k]) return bst[k];  // (allocation)
+    if ((st = zip_download(ctx, d_out.p, aoff, alen, take, own, blocks, &blocks_at))) return st;
     tr.mark(ctx, "zip open: download");
   }
 
   // An entry that outgrew its slot has a directory that understates its size; the reference does not look at the
-  // size field, only at the CRC.  Such entries take zh_zip_extract_batch's own route, from the host image, all of
-  // the call in one batch (rare: the CRC of these is compared here).
+  // size field, only at the CRC: such an entry is decoded again (zip_redo), and a reader keeps the result.
   std::vector<void*> redone(n_slot, nullptr);
-  {
-    std::vector<size_t> redo;
-    for (size_t j = 0; j < n_slot; j++)
-      if (est[j] == ZH_ERR_DST_TOO_SMALL) redo.push_back(j);
-    if (!redo.empty()) {
-      const size_t nr = redo.size();
-      std::vector<const void*> rsrc(nr);
-      std::vector<size_t> rlen(nr), rout(nr);
-      std::vector<uint64_t> rhint(nr);
-      std::vector<void*> rdst(nr, nullptr);
-      std::vector<int32_t> rst(nr);
-      std::vector<uint32_t> rcrc(nr);
-      std::vector<char> stale(n_walk, 0);
-      for (size_t q = 0; q < nr; q++) {
-        const Slot& sl = slots[redo[q]];
-        rsrc[q] = (const uint8_t*)images[walk[sl.walk]] + (sl.rec->src_off - imgs[sl.walk].up_off);
-        rlen[q] = (size_t)sl.rec->src_len;
-        rhint[q] = sl.rec->cap;
-      }
-      st = zh_uncompress_batch_sized(ctx, rsrc.data(), rlen.data(), nr, ZH_DF_DEFLATE, rhint.data(), rdst.data(),
-                                     rout.data(), rst.data(), rcrc.data());
-      own.p.insert(own.p.end(), rdst.begin(), rdst.end());
-      const size_t base = own.p.size() - nr;
-      if (st) return st;
-      for (size_t q = 0; q < nr; q++) {
-        const size_t j = redo[q];
-        est[j] = rst[q] == ZH_OK && rcrc[q] != slots[j].rec->crc ? ZH_ERR_ZIP_CRC : rst[q];
-        elen[j] = est[j] == ZH_OK ? rout[q] : 0;
-        if (est[j] == ZH_OK) {
-          redone[j] = rdst[q];
-          own.p[base + q] = nullptr;  // the reader's from here on
-        }
-        stale[slots[j].walk] = 1;
-      }
-      for (size_t q = 0; q < nr; q++) {  // the first failing entry of these archives, once more
-        const size_t k = slots[redo[q]].walk;
-        if (!stale[k]) continue;
-        stale[k] = 0;
-        ebad[k] = kNone;
-        for (size_t j = slot_lo[k]; j < slot_hi[k]; j++)
-          if (est[j] != ZH_OK) {
-            ebad[k] = (uint32_t)j;
-            break;
-          }
-      }
-      tr.mark(ctx, "zip open: redo");
-    }
-  }
+  if ((st = zip_redo(ctx, tr, "zip open", slots, eranges, up_src.data(), up_off, own, est, ebad,
+                     [&](size_t j, int32_t rst, uint32_t rcrc, size_t rout, void*& buf) {
+                       const int32_t v = rst == ZH_OK && rcrc != slots[j].want_crc ? ZH_ERR_ZIP_CRC : rst;
+                       elen[j] = v == ZH_OK ? rout : 0;
+                       if (v == ZH_OK) {  // the reader's from here on
+                         redone[j] = buf;
+                         buf = nullptr;
+                       }
+                       return v;
+                     })))
+    return st;
 
   // ---- the results into the readers ----
   {
@@ -738,8 +487,8 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
         for (size_t i = 0; i < n; i++)
           if (!recs[lo + i].directory) stt[i] = ZH_ERR_UNSAFE_PATH;
       } else {
-        for (; j < n_slot && slots[j].walk == k; j++) {
-          const size_t i = slots[j].entry;
+        for (; j < n_slot && slots[j].img == k; j++) {
+          const size_t i = slots[j].rec - ranges[2 * k];
           off[i] = slots[j].dst - aoff[k];
           len[i] = elen[j];
           stt[i] = est[j];

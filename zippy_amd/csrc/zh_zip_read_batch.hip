@@ -14,8 +14,8 @@
 //   (host)                the tables from the records in walk order (toUnixPath, replacement, the central records'
 //                         lookup); the layout of the output; ONE uncompress plan over every deflated local record of
 //                         the call, its sources in place in the uploaded images; the first failure in walk order
-//   zh_zipr_finish_kernel stored entries copied image -> slot; every record's CRC-32, then its length, held against
-//                         its header
+//   zh_zip_finish_kernel  stored entries copied image -> slot; every record's CRC-32, then its length, held against
+//                         its header (zh_zip_dev.h, with the host stages around it)
 // The host parses no header byte, compares no CRC and copies no entry.
 //
 // Scratch: 8 bytes per hit (the list), 20 per node of the walk (a hit, or an image's END node), 4 per 16 KiB of the
@@ -27,15 +27,12 @@
 // the next image, is no hit.
 #include <unordered_map>
 
-#include "zh_host.h"
-#include "zh_gather.h"
 #include "zh_walk.h"
 #include "zh_zip_dev.h"
 
 namespace {
 
 constexpr uint32_t kLocalSig = 0x04034b50u, kCentralSig = 0x02014b50u, kEndSig = 0x06054b50u;
-constexpr uint64_t kSlice = 32768;  // bytes of a stored entry a wave copies at most
 // the scan: a lane reads 16 bytes, a wave 1024 contiguous bytes, a workgroup 4096 a step, kScanSteps steps
 constexpr uint32_t kScanSteps = 4;
 constexpr uint64_t kScanStepBytes = 256 * 16, kScanGroupBytes = kScanStepBytes * kScanSteps;
@@ -62,18 +59,6 @@ struct ZhZrRec {
   int32_t status, succ_status;  // its own checks; what the walk finds where the next record should start
   uint16_t dos_time, dos_date;
   uint8_t kind, method, backslash, pad;
-};
-
-// One local record that is verified, for zh_zipr_finish_kernel
-struct ZhZrFin {
-  uint64_t src, dst, len;  // a stored entry: len bytes from upload buffer + src to output buffer + dst
-  uint32_t want_crc, want_len;
-  uint32_t deflated;  // 1: result `idx` of the plan; 0: stored entry `idx` of the checksum launch
-  uint32_t idx;
-};
-struct ZhZrFinTask {
-  uint64_t lo, hi;  // bytes [lo, hi) of the entry's data
-  uint32_t entry, first;
 };
 
 // the last image whose up_off <= p
@@ -320,60 +305,7 @@ __global__ __launch_bounds__(256) void zh_zipr_rec_ranges_kernel(const uint32_t*
   rec_ranges[2 * t + 1] = ord[ranges[2 * t + 1]];
 }
 
-// One wave per task (four a workgroup): a slice of a stored entry's bytes goes from its image to its slot (as
-// zh_zip_open_batch.hip's finish kernel copies it).  The wave of an entry's first task also settles the entry: the
-// decoder's status, else the CRC-32 against the header's (:208-212), else the length against the header's (:213-217).
-__global__ __launch_bounds__(256) void zh_zipr_finish_kernel(const uint8_t* __restrict__ d_in, uint8_t* __restrict__ d_out,
-                                                             const ZhZrFin* __restrict__ fins,
-                                                             const ZhZrFinTask* __restrict__ tasks, uint32_t n_tasks,
-                                                             const int32_t* __restrict__ plan_st,
-                                                             const uint64_t* __restrict__ plan_len,
-                                                             const uint32_t* __restrict__ plan_crc,
-                                                             const uint32_t* __restrict__ stored_crc,
-                                                             int32_t* __restrict__ est) {
-  const uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = zh_lane();
-  if (w >= n_tasks) return;
-  const ZhZrFinTask t = tasks[w];
-  const ZhZrFin e = fins[t.entry];
-  if (t.first && lane == 0) {
-    int32_t st = e.deflated ? plan_st[e.idx] : ZH_OK;
-    const uint32_t crc = e.deflated ? plan_crc[e.idx] : stored_crc[e.idx];
-    const uint64_t len = e.deflated ? plan_len[e.idx] : e.len;
-    if (st == ZH_OK && crc != e.want_crc) st = ZH_ERR_ZIP_CRC;
-    if (st == ZH_OK && len != e.want_len) st = ZH_ERR_ZIP_SIZE;
-    est[t.entry] = st;
-  }
-  if (t.lo >= t.hi) return;
-  const uint64_t a = e.dst + t.lo, b = e.dst + t.hi, delta = e.src - e.dst;  // (source byte = slot byte + delta, mod 2^64)
-  const uint64_t A = (a + 15) & ~(uint64_t)15, B = b & ~(uint64_t)15;
-  if (A >= B) {  // no whole chunk inside: at most 30 bytes
-    if (a + lane < b) d_out[a + lane] = d_in[a + lane + delta];
-    return;
-  }
-  if (a + lane < A) d_out[a + lane] = d_in[a + lane + delta];
-  if (B + lane < b) d_out[B + lane] = d_in[B + lane + delta];
-  for (uint64_t c = A + 16ull * lane; c < B; c += 1024) *reinterpret_cast<Chunk16*>(d_out + c) = gather16(d_in, c + delta);
-}
-
 namespace {
-
-struct Events {  // ZH_TRACE: kernels by themselves, between pairs of events that go away with the scope
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ok = false;
-  bool create() {
-    ok = true;
-    for (hipEvent_t& x : e) ok = ok && hipEventCreate(&x) == hipSuccess;
-    return ok;
-  }
-  float ms(int a, int b) const {
-    float t = 0;
-    return hipEventSynchronize(e[b]) == hipSuccess && hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess ? t : -1.f;
-  }
-  ~Events() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
 
 // ZipArchive.contents as it grows (an OrderedTable[string, ArchiveEntry]): keys in first-insertion order
 struct Table {
@@ -391,13 +323,7 @@ struct Table {
 
 extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const size_t* lens, size_t n_zip,
                                  zh_zip_reader** readers, int32_t* statuses) {
-  if (!ctx || (n_zip && (!images || !lens || !readers || !statuses))) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_zip; t++) {
-    readers[t] = nullptr;
-    statuses[t] = ZH_OK;
-  }
-  for (size_t t = 0; t < n_zip; t++)
-    if (!images[t] && lens[t]) return ZH_ERR_ARGUMENT;
+  if (const int e = reader_checks(ctx, images, lens, n_zip, readers, statuses)) return e;
   if (!n_zip) return ZH_OK;
 
   // ---- 1. the layout of the upload; the most nodes there can be (two signatures do not overlap) ----
@@ -470,20 +396,17 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   max_chain = std::min<uint64_t>(max_chain, n_hits);
   uint32_t rounds = 0;
   while ((1ull << rounds) < max_chain + 1) rounds++;
-  const uint32_t N = n_hits + n_img, n_sums = (N + kScanItems - 1) / kScanItems;
-  DevBuf d_scr;
-  Arena ar;
-  const size_t o_j0 = ar.reserve((size_t)N * 4), o_j1 = ar.reserve((size_t)N * 4), o_mark = ar.reserve((size_t)N * 4),
-               o_ord = ar.reserve((size_t)N * 4), o_succ = ar.reserve((size_t)n_hits * 4),
-               o_sums = ar.reserve(((size_t)n_sums + 1) * 4), o_hr = ar.reserve((size_t)n_img * 8);
-  if (dev_alloc(ctx, d_scr, ar.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  uint32_t* const j0 = carve<uint32_t>(d_scr.p, o_j0);
-  uint32_t* const j1 = carve<uint32_t>(d_scr.p, o_j1);
-  uint32_t* const mark = carve<uint32_t>(d_scr.p, o_mark);
-  uint32_t* const ord = carve<uint32_t>(d_scr.p, o_ord);
-  int32_t* const succ = carve<int32_t>(d_scr.p, o_succ);
-  uint32_t* const sums = carve<uint32_t>(d_scr.p, o_sums);
-  uint32_t* const hit_ranges = carve<uint32_t>(d_scr.p, o_hr);
+  // behind the walk's scratch: what the loop finds behind every hit (succ), every image's range of hits
+  const uint32_t N = n_hits + n_img;
+  Arena ex;
+  const size_t o_succ = ex.reserve((size_t)n_hits * 4), o_hr = ex.reserve((size_t)n_img * 8);
+  Walk w;
+  if ((st = walk_alloc(ctx, w, N, ex.size + 256))) return st;
+  // (plain pointers for the launches: a launch must not take a DevBuf, or the Walk that holds one, along)
+  uint32_t *const j0 = w.j0, *const mark = w.mark;
+  const uint32_t *const ord = w.ord, *const list = w.list;
+  int32_t* const succ = carve<int32_t>(w.extra, o_succ);
+  uint32_t* const hit_ranges = carve<uint32_t>(w.extra, o_hr);
   // the per-image outputs live in the block that is downloaded with the records (below); the start statuses are
   // written now, so they get a place of their own here
   DevBuf d_start;
@@ -494,21 +417,10 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
                      start);
   hipLaunchKernelGGL(zh_zipr_next_kernel, node_grid, wg, 0, s, in, dimgs, n_img, (const uint64_t*)hits,
                      n_hits, (const uint32_t*)hit_ranges, N, j0, mark, succ);
-  uint32_t *jin = j0, *jout = j1;
-  for (uint32_t r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(zh_walk_double_kernel, node_grid, wg, 0, s, (const uint32_t*)jin, jout, mark, N);
-    std::swap(jin, jout);
-  }
-  // (the jump arrays are dead from here on: the list of records takes the place of the first)
-  uint32_t* const list = j0;
-  hipLaunchKernelGGL(zh_walk_scan_sums_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, sums);
-  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, sums, n_sums);
-  hipLaunchKernelGGL(zh_walk_scan_write_kernel, dim3(n_sums), wg, 0, s, (const uint32_t*)mark, N, (const uint32_t*)sums,
-                     ord, list);
-  ZH_HIP(ctx, hipGetLastError());
+  walk_double(w, rounds, s);
+  walk_scan(w, s);
   uint32_t n_rec = 0;
-  ZH_HIP(ctx, hipMemcpyAsync(&n_rec, sums + n_sums, 4, hipMemcpyDeviceToHost, s));
-  ZH_HIP(ctx, hipStreamSynchronize(s));
+  if ((st = walk_count(ctx, w, &n_rec))) return st;
   tr.mark(ctx, "zip read: reach + scan");
 
   // ---- 5. the records ----
@@ -522,10 +434,10 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   uint8_t* const rec_p = d_rec.p;
   if (n_rec)
     hipLaunchKernelGGL(zh_zipr_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, in, dimgs, n_img,
-                       (const uint64_t*)hits, (const uint32_t*)list, (const int32_t*)succ, n_rec,
+                       (const uint64_t*)hits, list, (const int32_t*)succ, n_rec,
                        carve<ZhZrRec>(rec_p, o_recs), carve<int32_t>(rec_p, o_rstat));
-  hipLaunchKernelGGL(zh_zipr_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img,
-                     (const uint32_t*)ord, carve<uint32_t>(rec_p, o_ranges));
+  hipLaunchKernelGGL(zh_zipr_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord,
+                     carve<uint32_t>(rec_p, o_ranges));
   hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)carve<uint32_t>(rec_p, o_ranges),
                      (const int32_t*)carve<int32_t>(rec_p, o_rstat), (const uint8_t*)nullptr,
                      carve<uint32_t>(rec_p, o_bad), carve<uint32_t>(rec_p, o_any));
@@ -550,20 +462,15 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   // ---- 6. the tables, from the records in walk order; the layout of the output ----
   // hst[t]: the first failure of the header checks, the central records' lookups and the walk's steps.  A local
   // record in front of it still has its say (decoder, CRC, size): every one of them gets a slot.
-  struct Slot {
-    size_t img;
-    uint32_t rec;
-    uint64_t dst = 0, cap = 0;
-  };
   std::vector<Table> tables(n_zip);
   std::vector<int32_t> hst(n_zip, ZH_OK);
-  std::vector<Slot> slots;
+  std::vector<ZipSlot> slots;
+  std::vector<uint32_t> eranges(2 * n_zip, 0);  // an image's slots
   std::vector<uint64_t> aoff(n_zip, 0), alen(n_zip, 0);
-  std::vector<size_t> slot_lo(n_zip, 0), slot_hi(n_zip, 0);
   std::unordered_map<uint32_t, size_t> slot_of;  // a local record's slot
   uint64_t out_total = 0;
   for (size_t t = 0; t < n_zip; t++) {
-    slot_lo[t] = slot_hi[t] = slots.size();
+    eranges[2 * t] = eranges[2 * t + 1] = (uint32_t)slots.size();
     if (start_st[t] != ZH_OK) {
       hst[t] = start_st[t];
       continue;
@@ -583,13 +490,11 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
         break;
       }
       if (e.kind == kKindLocal) {
-        Slot sl{t, i};
         // never above the stream's expansion bound: a tiny image cannot claim gigabytes
-        sl.cap = e.method == 8 ? std::min<uint64_t>(e.usize, (uint64_t)e.csize * 1032 + 64) : e.csize;
-        sl.dst = out_total;
-        out_total += round_up8(sl.cap);
+        const uint64_t cap = e.method == 8 ? std::min<uint64_t>(e.usize, (uint64_t)e.csize * 1032 + 64) : e.csize;
         slot_of[i] = slots.size();
-        slots.push_back(sl);
+        slots.push_back(ZipSlot{t, i, up_off[t] + e.data_off, e.csize, out_total, cap, e.crc, e.usize, ZH_OK, e.method});
+        out_total += round_up8(cap);
         std::string key((const char*)image + e.name_off, e.name_len);
         if (e.backslash) std::replace(key.begin(), key.end(), '\\', '/');  // toUnixPath
         const auto it = tab.index.find(key);
@@ -618,7 +523,7 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
       ctx->last_error = "zh_zip_read_batch: a walk that ends nowhere";
       return ZH_ERR_DEVICE;
     }
-    slot_hi[t] = slots.size();
+    eranges[2 * t + 1] = (uint32_t)slots.size();
     alen[t] = out_total - aoff[t];
   }
   const size_t n_slot = slots.size();
@@ -626,161 +531,23 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   tr.mark(ctx, "zip read: tables");
 
   // ---- 7. one decode; 8. the stored entries and every verdict ----
-  std::vector<int32_t> est(n_slot, ZH_OK), ast(hst);
+  std::vector<int32_t> est, ast(hst);
   std::vector<void*> blocks(n_zip, nullptr);
-  size_t blocks_at = 0;  // blocks[t] is own.p[blocks_at + t] until a reader takes it
+  size_t blocks_at = 0;
   if (n_slot) {
-    std::vector<ZhZrFin> fins(n_slot);
-    std::vector<ZhZrFinTask> tasks;
-    std::vector<uint64_t> p_soff, p_slen, p_doff, p_dcap;
-    std::vector<ZhPieceDesc> pieces;
-    std::vector<ZhBufDesc> sbufs;
-    std::vector<uint32_t> eranges(2 * n_zip, 0);
-    for (size_t t = 0; t < n_zip; t++) {
-      eranges[2 * t] = (uint32_t)slot_lo[t];
-      eranges[2 * t + 1] = (uint32_t)slot_hi[t];
-    }
-    for (size_t j = 0; j < n_slot; j++) {
-      const Slot& sl = slots[j];
-      const ZhZrRec& e = recs[sl.rec];
-      const uint64_t src = imgs[sl.img].up_off + e.data_off;
-      ZhZrFin& f = fins[j];
-      f = ZhZrFin{src, sl.dst, 0, e.crc, e.usize, 0, 0};
-      uint64_t copy = 0;
-      if (e.method == 8) {
-        f.deflated = 1;
-        f.idx = (uint32_t)p_soff.size();
-        p_soff.push_back(src);
-        p_slen.push_back(e.csize);
-        p_doff.push_back(sl.dst);
-        p_dcap.push_back(sl.cap);
-      } else {
-        f.len = copy = e.csize;
-        f.idx = (uint32_t)sbufs.size();
-        ZhBufDesc b;
-        memset(&b, 0, sizeof(b));
-        b.src_off = src;
-        b.src_len = copy;
-        b.first_piece = (uint32_t)pieces.size();
-        for (uint64_t o = 0; o < copy; o += ZH_FRAG_SIZE)
-          pieces.push_back(ZhPieceDesc{src + o, (uint32_t)std::min<uint64_t>(copy - o, ZH_FRAG_SIZE), f.idx, o});
-        b.npieces = (uint32_t)pieces.size() - b.first_piece;
-        sbufs.push_back(b);
-      }
-      uint32_t first = 1;
-      for (uint64_t o = 0; first || o < copy; o += kSlice, first = 0)
-        tasks.push_back(ZhZrFinTask{o, std::min<uint64_t>(copy, o + kSlice), (uint32_t)j, first});
-    }
-    const size_t n_def = p_soff.size(), n_sto = sbufs.size(), n_piece = pieces.size(), n_task = tasks.size();
-    if (n_task >= 0xffffffffull || n_piece >= 0xffffffffull) return ZH_ERR_ARGUMENT;
-    DevBuf d_out, d_fin;
-    if (dev_alloc(ctx, d_out, out_total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    Arena fa;
-    const size_t o_fins = fa.reserve(n_slot * sizeof(ZhZrFin)), o_tasks = fa.reserve(n_task * sizeof(ZhZrFinTask)),
-                 o_sbufs = fa.reserve(n_sto * sizeof(ZhBufDesc)), o_pieces = fa.reserve(n_piece * sizeof(ZhPieceDesc)),
-                 o_er = fa.reserve(n_zip * 8);
-    const size_t fa_in = fa.size;
-    const size_t o_pcrc = fa.reserve(n_piece * 4), o_pad = fa.reserve(n_piece * 4), o_plen = fa.reserve(n_piece * 4),
-                 o_scrc = fa.reserve(n_sto * 4), o_sad = fa.reserve(n_sto * 4), o_est = fa.reserve(n_slot * 4),
-                 o_ebad = fa.reserve(n_zip * 4), o_eany = fa.reserve(n_zip * 4);
-    if (dev_alloc(ctx, d_fin, fa.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-    uint8_t* const fin_p = d_fin.p;
-    {
-      std::vector<uint8_t> h(fa_in);
-      memcpy(h.data() + o_fins, fins.data(), n_slot * sizeof(ZhZrFin));
-      memcpy(h.data() + o_tasks, tasks.data(), n_task * sizeof(ZhZrFinTask));
-      if (n_sto) memcpy(h.data() + o_sbufs, sbufs.data(), n_sto * sizeof(ZhBufDesc));
-      if (n_piece) memcpy(h.data() + o_pieces, pieces.data(), n_piece * sizeof(ZhPieceDesc));
-      memcpy(h.data() + o_er, eranges.data(), n_zip * 8);
-      const void* src = h.data();
-      if ((st = zhh_upload_slices(ctx, &src, {0}, {(uint64_t)fa_in}, fa_in, fin_p))) return st;
-    }
-    PlanGuard pg;
-    if (n_def) {
-      if ((st = zh_plan_uncompress(ctx, n_def, p_soff.data(), p_slen.data(), p_doff.data(), p_dcap.data(),
-                                   ZH_DF_DEFLATE, &pg.p)) ||
-          (st = zh_plan_request_crc32(pg.p, 1)))
-        return st;
-      if (tr.on) zh_plan_set_profiling(pg.p, 1);
-      if ((st = zh_plan_run(pg.p, d_in.p, d_out.p))) return st;
-      if (tr.on) {
-        const char* names[64];
-        float ms[64];
-        const int nk = zh_plan_kernel_times(pg.p, names, ms, 64);
-        for (int i = 0; i < nk && i < 64; i++) fprintf(stderr, "[zh]   plan kernel %-24s %8.3f ms\n", names[i], ms[i]);
-      }
-    }
-    tr.mark(ctx, "zip read: decode");
-    zh_launch_checksum_pieces(s, ctx->cktabs, d_in.p, carve<ZhPieceDesc>(fin_p, o_pieces), (uint32_t)n_piece, nullptr,
-                              1, 0, carve<uint32_t>(fin_p, o_pcrc), carve<uint32_t>(fin_p, o_pad),
-                              carve<uint32_t>(fin_p, o_plen));
-    zh_launch_checksum_combine(s, ctx->cktabs, carve<ZhBufDesc>(fin_p, o_sbufs), (uint32_t)n_sto,
-                               carve<uint32_t>(fin_p, o_pcrc), carve<uint32_t>(fin_p, o_pad),
-                               carve<uint32_t>(fin_p, o_plen), 1, 0, carve<uint32_t>(fin_p, o_scrc),
-                               carve<uint32_t>(fin_p, o_sad));
-    // (plain pointers: a launch must not take the guard of the plan along)
-    const int32_t* const plan_st = n_def ? zh_plan_device_statuses(pg.p) : nullptr;
-    const uint64_t* const plan_len = n_def ? zh_plan_device_lens(pg.p) : nullptr;
-    const uint32_t* const plan_crc = n_def ? pg.p->buf_crc : nullptr;
-    uint8_t* const outp = d_out.p;
-    hipLaunchKernelGGL(zh_zipr_finish_kernel, dim3(((uint32_t)n_task + 3) / 4), wg, 0, s, in, outp,
-                       (const ZhZrFin*)carve<ZhZrFin>(fin_p, o_fins),
-                       (const ZhZrFinTask*)carve<ZhZrFinTask>(fin_p, o_tasks), (uint32_t)n_task, plan_st, plan_len,
-                       plan_crc, (const uint32_t*)carve<uint32_t>(fin_p, o_scrc), carve<int32_t>(fin_p, o_est));
-    hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)carve<uint32_t>(fin_p, o_er),
-                       (const int32_t*)carve<int32_t>(fin_p, o_est), (const uint8_t*)nullptr,
-                       carve<uint32_t>(fin_p, o_ebad), carve<uint32_t>(fin_p, o_eany));
-    ZH_HIP(ctx, hipGetLastError());
-    std::vector<uint32_t> ebad(n_zip, kNone);
-    ZH_HIP(ctx, hipMemcpyAsync(est.data(), d_fin.p + o_est, n_slot * 4, hipMemcpyDeviceToHost, s));
-    ZH_HIP(ctx, hipMemcpyAsync(ebad.data(), d_fin.p + o_ebad, n_zip * 4, hipMemcpyDeviceToHost, s));
-    ZH_HIP(ctx, hipStreamSynchronize(s));
-    tr.mark(ctx, "zip read: finish");
-
+    DevBuf d_out;
+    std::vector<uint32_t> ebad;
+    if ((st = zip_extract(ctx, tr, "zip read", slots, eranges, in, out_total, true, d_out, est, nullptr, ebad)))
+      return st;
     // A stream that outgrew its slot decodes to more than its header claims: CRC comes before size (:208-217), so it
-    // is decoded again in full, from the host image, all of the call in one batch (rare: the CRC of these is
-    // compared here).  None of them can end well: at best the length is not the header's.
-    {
-      std::vector<size_t> redo;
-      for (size_t j = 0; j < n_slot; j++)
-        if (est[j] == ZH_ERR_DST_TOO_SMALL) redo.push_back(j);
-      if (!redo.empty()) {
-        const size_t nr = redo.size();
-        std::vector<const void*> rsrc(nr);
-        std::vector<size_t> rlen(nr), rout(nr);
-        std::vector<uint64_t> rhint(nr);
-        std::vector<void*> rdst(nr, nullptr);
-        std::vector<int32_t> rst(nr);
-        std::vector<uint32_t> rcrc(nr);
-        for (size_t q = 0; q < nr; q++) {
-          const Slot& sl = slots[redo[q]];
-          rsrc[q] = (const uint8_t*)images[sl.img] + recs[sl.rec].data_off;
-          rlen[q] = recs[sl.rec].csize;
-          rhint[q] = sl.cap;
-        }
-        st = zh_uncompress_batch_sized(ctx, rsrc.data(), rlen.data(), nr, ZH_DF_DEFLATE, rhint.data(), rdst.data(),
-                                       rout.data(), rst.data(), rcrc.data());
-        own.p.insert(own.p.end(), rdst.begin(), rdst.end());
-        if (st) return st;
-        std::vector<char> stale(n_zip, 0);
-        for (size_t q = 0; q < nr; q++) {
-          const size_t j = redo[q];
-          const ZhZrRec& e = recs[slots[j].rec];
-          est[j] = rst[q] != ZH_OK ? rst[q] : rcrc[q] != e.crc ? ZH_ERR_ZIP_CRC : rout[q] != e.usize ? ZH_ERR_ZIP_SIZE : ZH_OK;
-          stale[slots[j].img] = 1;
-        }
-        for (size_t t = 0; t < n_zip; t++) {  // the first failing record of these images, once more
-          if (!stale[t]) continue;
-          ebad[t] = kNone;
-          for (size_t j = slot_lo[t]; j < slot_hi[t]; j++)
-            if (est[j] != ZH_OK) {
-              ebad[t] = (uint32_t)j;
-              break;
-            }
-        }
-        tr.mark(ctx, "zip read: redo");
-      }
-    }
+    // is decoded again in full (zip_redo).  None of them can end well: at best the length is not the header's.
+    if ((st = zip_redo(ctx, tr, "zip read", slots, eranges, images, up_off, own, est, ebad,
+                       [&](size_t j, int32_t rst, uint32_t rcrc, size_t rout, void*&) {
+                         const ZipSlot& sl = slots[j];
+                         return rst != ZH_OK ? rst : rcrc != sl.want_crc ? ZH_ERR_ZIP_CRC
+                                : rout != sl.want_len ? ZH_ERR_ZIP_SIZE : ZH_OK;
+                       })))
+      return st;
     // every verified record stands in front of its image's hst in walk order
     for (size_t t = 0; t < n_zip; t++)
       if (ebad[t] != kNone) ast[t] = est[ebad[t]];
@@ -788,14 +555,7 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
     // ---- 9. one download: the block of every archive that opened ----
     std::vector<char> take(n_zip, 0);
     for (size_t t = 0; t < n_zip; t++) take[t] = ast[t] == ZH_OK && alen[t] ? 1 : 0;
-    std::vector<size_t> blen(n_zip, 0);
-    std::vector<int32_t> bst(n_zip, ZH_OK);
-    st = zhh_download(ctx, d_out.p, n_zip, aoff, alen, take, blocks.data(), blen.data(), bst.data());
-    blocks_at = own.p.size();
-    own.p.insert(own.p.end(), blocks.begin(), blocks.end());
-    if (st) return st;
-    for (size_t t = 0; t < n_zip; t++)
-      if (take[t] && bst[t]) return bst[t];  // (allocation)
+    if ((st = zip_download(ctx, d_out.p, aoff, alen, take, own, blocks, &blocks_at))) return st;
     tr.mark(ctx, "zip read: download");
   }
 

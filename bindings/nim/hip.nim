@@ -543,3 +543,68 @@ proc hipReadTarballs*(images: openArray[string],
   finally:
     for r in readers:
       if r != nil: zh_tar_close(r)
+
+# ---- random access into block-indexed streams (no counterpart in the reference) ----
+type
+  ZhBlockEntry* {.bycopy.} = object
+    bitOff*: uint64                     # the block's first bit, counted from the compressed buffer's first byte
+    outOff*: uint64                     # its first byte in the uncompressed data; the closing entry: the length
+
+proc zh_compress_blocks(ctx: ZhCtx, src: pointer, len: csize_t, level, dataFormat: cint, blockBytes: csize_t,
+                        dst: ptr pointer, dstLen: ptr csize_t, index: ptr ptr ZhBlockEntry,
+                        nEntries: ptr csize_t): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_uncompress_ranges(ctx: ZhCtx, srcs: ptr pointer, lens: ptr csize_t, nStreams: csize_t,
+                          index: ptr ZhBlockEntry, first: ptr csize_t, nRanges: csize_t,
+                          rangeStream, rangeOff, rangeLen: ptr uint64, dsts: ptr pointer, dstLens: ptr csize_t,
+                          statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_plan_uncompress_ranges(ctx: ZhCtx, nStreams: csize_t, srcOff, srcLen: ptr uint64,
+                               index: ptr ZhBlockEntry, first: ptr csize_t, nRanges: csize_t,
+                               rangeStream, rangeOff, rangeLen, dstOff, dstCap: ptr uint64,
+                               plan: ptr ZhPlan): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipCompressBlocks*(src: string, blockBytes = 32768, level = BestSpeed,
+                        dataFormat = dfGzip): (string, seq[ZhBlockEntry]) {.raises: [ZippyError].} =
+  ## compress() with deflate blocks of blockBytes (a multiple of 32768, up to 4 MiB) that no match crosses, and the
+  ## index of their starts: still a stream uncompress() reads, and one hipReadRanges reads bytes out of
+  var dst: pointer; var dstLen, n: csize_t; var idx: ptr ZhBlockEntry
+  let st = zh_compress_blocks(engine(), (if src.len > 0: src[0].unsafeAddr else: nil), src.len.csize_t, level.cint,
+                              ord(dataFormat).cint, blockBytes.csize_t, dst.addr, dstLen.addr, idx.addr, n.addr)
+  if st == 0:
+    result[1] = newSeq[ZhBlockEntry](n.int)
+    copyMem(result[1][0].addr, idx, n.int * sizeof(ZhBlockEntry))
+    zh_free(idx)
+  result[0] = take(dst, dstLen, st)
+
+proc hipReadRanges*(streams: openArray[string], indexes: openArray[seq[ZhBlockEntry]],
+                    ranges: openArray[tuple[stream, off, len: uint64]]): seq[string] {.raises: [ZippyError].} =
+  ## bytes [off, off + len) of the uncompressed data of streams[stream], for every range, in one call: only the
+  ## blocks a range touches are uploaded and decoded.  Ranges read like pread (clipped at the end, empty behind it).
+  ## Raises on the first range that could not be read (a damaged block, an index that does not fit its stream).
+  let n = ranges.len
+  if n == 0: return
+  var
+    ptrs = newSeq[pointer](max(1, streams.len))
+    lens = newSeq[csize_t](max(1, streams.len))
+    flat: seq[ZhBlockEntry]
+    first = @[0.csize_t]
+    rs = newSeq[uint64](n); ro = newSeq[uint64](n); rl = newSeq[uint64](n)
+    dsts = newSeq[pointer](n); dlens = newSeq[csize_t](n); sts = newSeq[int32](n)
+  for i, s in streams:
+    ptrs[i] = if s.len > 0: s[0].unsafeAddr else: nil
+    lens[i] = s.len.csize_t
+    flat.add indexes[i]
+    first.add flat.len.csize_t
+  for i, r in ranges: (rs[i], ro[i], rl[i]) = (r.stream, r.off, r.len)
+  let rc = zh_uncompress_ranges(engine(), ptrs[0].addr, lens[0].addr, streams.len.csize_t,
+                                (if flat.len > 0: flat[0].addr else: nil), first[0].addr, n.csize_t,
+                                rs[0].addr, ro[0].addr, rl[0].addr, dsts[0].addr, dlens[0].addr, sts[0].addr)
+  var firstBad = rc
+  for i in 0 ..< n:                    # copy what came back, free everything, then raise
+    if firstBad == 0 and sts[i] != 0: firstBad = sts[i].cint
+  for i in 0 ..< n:
+    if firstBad != 0:
+      if dsts[i] != nil: zh_free(dsts[i])
+    else:
+      result.add take(dsts[i], dlens[i], 0)
+  if firstBad != 0:
+    raise newException(ZippyError, $zh_strerror(firstBad))

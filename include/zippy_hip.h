@@ -351,6 +351,56 @@ int zh_plan_uncompress_indexed(zh_ctx *ctx, uint64_t src_off, uint64_t src_len, 
                                uint64_t dst_cap, int data_format, const zh_block_entry *index,
                                size_t n_entries, zh_plan **out);
 
+/* Byte ranges of the UNCOMPRESSED data of block-indexed streams, many ranges of many streams in one call: only the
+ * blocks a range touches are decoded (and, from host buffers, only their compressed bytes uploaded).
+ *
+ * Device-resident: stream s is d_src[src_off[s] .. +src_len[s]) with index entries
+ * index[first[s] .. first[s+1]) (each stream's list closed as zh_compress_blocks returns it).
+ * Range r reads bytes [range_off[r], range_off[r]+range_len[r]) of the UNCOMPRESSED data of stream
+ * range_stream[r] into d_dst[dst_off[r] .. +dst_cap[r]).
+ *
+ * Ranges read like pread:
+ *  - a range is clipped at the stream's uncompressed length (the closing entry's out_off); range_off at or beyond it,
+ *    or range_len 0, gives 0 bytes and ZH_OK and touches no block; range_off + range_len beyond 2^64 is clipped too;
+ *  - range_stream[r] >= n_streams and NULL arrays are the caller's bugs: ZH_ERR_ARGUMENT, nothing runs;
+ *  - a stream whose index cannot be right -- fewer than 2 entries, out_off or bit_off falling, index[0].out_off != 0,
+ *    a block's bit_off at or beyond 8 * src_len, a block that promises more than 1032 * (its compressed bytes) + 64
+ *    bytes -- fails every range of THAT stream with ZH_ERR_INVALID_BUFFER; other streams' ranges are not affected.
+ * What is verified: neither the container's header nor its trailer is looked at (a range cannot prove a checksum of
+ * the whole, and bit_off counts from the first byte of the buffer whatever the container).  Every block a range
+ * touches must decode with ZH_OK and make exactly out_off[k+1] - out_off[k] bytes; otherwise the range's status is
+ * that of its lowest such block (ZH_OK and ZH_ERR_DST_TOO_SMALL of a block read ZH_ERR_INVALID_BUFFER, as in
+ * zh_uncompress_indexed), its length 0 and its slot's contents unspecified.  Ranges that touch no bad block succeed.
+ * A match that reaches back before its block's start (a stream not written block-parallel) fails the range the same
+ * way.
+ * A slot smaller than the clipped range (dst_cap[r]): ZH_ERR_DST_TOO_SMALL for that range with out_len the size it
+ * needs; none of its blocks is decoded and its slot is not written.  Slots must not overlap.  Of a slot only
+ * [dst_off, dst_off + out_len) changes where the status is ZH_OK.
+ * Two ranges that share a block decode it twice (no deduplication).  The blocks of all ranges together must stay
+ * below 2^31, else ZH_ERR_ARGUMENT before anything is launched.
+ * Blocks that lie wholly inside their range are decoded in place; the one or two its ends cut into go through
+ * scratch the plan owns (bounded by ZH_SCRATCH_MB: beyond it, groups of ranges take turns) and are clipped into place.
+ *
+ * The plan runs with zh_plan_run(plan, d_src, d_dst) and is re-runnable; zh_plan_results returns n_ranges lengths
+ * and statuses.  zh_plan_pack, zh_plan_unpack, zh_plan_set_src_lens_device, zh_plan_request_crc32 and
+ * zh_plan_block_index return ZH_ERR_ARGUMENT for it. */
+int zh_plan_uncompress_ranges(zh_ctx *ctx, size_t n_streams, const uint64_t *src_off, const uint64_t *src_len,
+                              const zh_block_entry *index, const size_t *first,
+                              size_t n_ranges, const uint64_t *range_stream, const uint64_t *range_off,
+                              const uint64_t *range_len, const uint64_t *dst_off, const uint64_t *dst_cap,
+                              zh_plan **out);
+/* Host buffers in, library-allocated results out (zh_free), like zh_uncompress_batch: dsts[r] / dst_lens[r] where
+ * statuses[r] is ZH_OK (a buffer of its own also for 0 bytes), NULL / 0 otherwise.  Of stream s only the bytes
+ * [bit_off[k0] / 8, ceil(bit_off[k1+1] / 8)) that a range's blocks k0 .. k1 occupy are uploaded, spans of one stream
+ * that overlap or touch once. */
+int zh_uncompress_ranges(zh_ctx *ctx, const void *const *srcs, const size_t *lens, size_t n_streams,
+                         const zh_block_entry *index, const size_t *first,
+                         size_t n_ranges, const uint64_t *range_stream, const uint64_t *range_off,
+                         const uint64_t *range_len, void **dsts, size_t *dst_lens, int32_t *statuses);
+/* Counters of the context's last ranges call / plan run: bytes that went over the link (0 for a plan run: its streams
+ * are on the device), blocks decoded in place, blocks decoded via scratch. */
+int zh_debug_range_stats(zh_ctx *ctx, uint64_t *uploaded_bytes, uint64_t *blocks_in_place, uint64_t *blocks_via_scratch);
+
 /* ------------------------------------------------------------------ *
  * ZIP archives as batch clients of the codec. *
  * Record parsing / assembly of src/zippy/ziparchives.nim on the host, *

@@ -91,6 +91,16 @@ _SIGS = {
     "zh_plan_uncompress_indexed": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_uint64,
                                               _c.c_uint64, _c.c_int, _c.POINTER(_c.c_uint64),
                                               _c.c_size_t, _c.POINTER(_c.c_void_p)]),
+    "zh_plan_uncompress_ranges": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_void_p)]),
+    "zh_uncompress_ranges": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                        _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
+    "zh_debug_range_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                        _c.POINTER(_c.c_uint64)]),
     "zh_crc32_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                   _c.POINTER(_c.c_uint32)]),
     "zh_compress_batch_crc32": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
@@ -814,6 +824,61 @@ class Engine:
             return _c.string_at(dst, dlen.value)
         finally:
             self.lib.zh_free(dst)
+
+    # ---- byte ranges of block-indexed streams ----
+    @staticmethod
+    def _range_tables(indexes, ranges):
+        """The C arrays both ranges calls share: every stream's index back to back with first[], the ranges as three
+        parallel uint64 arrays (values wrap at 2^64 like the C types)."""
+        flat = _u64([v for idx in indexes for e in idx for v in e])
+        first = [0]
+        for idx in indexes:
+            first.append(first[-1] + len(idx))
+        m64 = (1 << 64) - 1
+        cols = [_u64([int(r[k]) & m64 for r in ranges]) for k in range(3)]
+        return flat, (_c.c_size_t * len(first))(*first), cols
+
+    def uncompress_ranges(self, streams, indexes, ranges):
+        """Bytes [off, off + len) of the uncompressed data of streams[stream] for every (stream, off, len) of `ranges`,
+        one call (zh_uncompress_ranges); indexes[s]: stream s's [(bit_off, out_off), ...] as compress_blocks returns it.
+        -> (list of bytes | None, statuses)"""
+        if len(indexes) != len(streams):
+            raise ValueError("indexes: one per stream")
+        ns, nr = len(streams), len(ranges)
+        keep = [bytes(b) for b in streams]
+        srcs = (_c.c_void_p * max(1, ns))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * max(1, ns))(*[len(k) for k in keep])
+        flat, first, (rs, ro, rl) = self._range_tables(indexes, ranges)
+        dsts, dlens, sts = (_c.c_void_p * max(1, nr))(), (_c.c_size_t * max(1, nr))(), (_c.c_int32 * max(1, nr))()
+        rc = self.lib.zh_uncompress_ranges(self._h, srcs, lens, ns, flat, first, nr, rs, ro, rl, dsts, dlens, sts)
+        outs = []
+        try:
+            for r in range(nr):
+                outs.append(_c.string_at(dsts[r], dlens[r]) if dsts[r] and sts[r] == 0 else None)
+        finally:
+            for r in range(nr):
+                if dsts[r]:
+                    self.lib.zh_free(dsts[r])
+        self._check(rc)
+        return outs, list(sts)[:nr]
+
+    def plan_uncompress_ranges(self, src_off, src_len, indexes, ranges, dst_off, dst_cap):
+        """zh_plan_uncompress_ranges: streams d_src[src_off[s] .. + src_len[s]) with indexes[s], ranges as in
+        uncompress_ranges, slots d_dst[dst_off[r] .. + dst_cap[r]) -> a Plan of len(ranges)."""
+        if len(indexes) != len(src_off):
+            raise ValueError("indexes: one per stream")
+        h = _c.c_void_p()
+        flat, first, (rs, ro, rl) = self._range_tables(indexes, ranges)
+        self._check(self.lib.zh_plan_uncompress_ranges(self._h, len(src_off), _u64(src_off), _u64(src_len), flat, first,
+                                                       len(ranges), rs, ro, rl, _u64(dst_off), _u64(dst_cap),
+                                                       _c.byref(h)))
+        return Plan(self, h, len(ranges))
+
+    def debug_range_stats(self):
+        """(uploaded bytes, blocks decoded in place, blocks decoded via scratch) of the last ranges call / plan run."""
+        up, ip, sc = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+        self._check(self.lib.zh_debug_range_stats(self._h, _c.byref(up), _c.byref(ip), _c.byref(sc)))
+        return up.value, ip.value, sc.value
 
     def crc32(self, src):
         src = bytes(src)

@@ -58,6 +58,21 @@ def uncompress_indexed(src, index, dataFormat=dfDetect):
     return engine().uncompress_indexed(src, index, dataFormat)
 
 
+def uncompress_ranges(streams, indexes, ranges):
+    """Random access into streams written by compress_blocks: bytes [off, off + len) of the uncompressed data of
+    streams[stream] for every (stream, off, len) of `ranges`, in one call -- only the blocks a range touches are
+    uploaded and decoded.  Ranges read like pread (clipped at the end, empty beyond it).  -> (outputs, statuses);
+    an output is None where its status is not 0."""
+    return engine().uncompress_ranges(streams, indexes, ranges)
+
+
+def read_range(src, index, off, length):
+    """uncompress_ranges for one range of one stream -> bytes; raises ZippyError where the range cannot be read."""
+    eng = engine()
+    outs, sts = eng.uncompress_ranges([src], [index], [(0, off, length)])
+    return eng._raise_first(outs, sts)[0]
+
+
 def openZipArchive(image):
     """ziparchives.nim:183 openZipArchive on the bytes of an archive -> reader with walk_files(),
     extract_file(path), extract_batch(indices)."""

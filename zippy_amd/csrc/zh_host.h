@@ -1,9 +1,10 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in thirteen files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in fourteen files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
 // wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
-// zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks) the batch writers
+// zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks), zh_ranges.hip (byte-range
+// reads from block-indexed streams: geometry, host call and its two kernels), the batch writers
 // zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
 // zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
 // all four share, zh_tar_dev.h and zh_zip_dev.h what the two of a format share, zh_gather.h the unaligned copy).
@@ -84,6 +85,45 @@ void zh_launch_trailer(hipStream_t, uint8_t* d_dst, ZhCompressArgs a, const uint
 void zh_launch_emit(hipStream_t, const uint8_t* d_src, uint8_t* d_dst, ZhCompressArgs a, int cover_in);
 }
 
+// ---- byte-range reads from block-indexed streams (zh_ranges.hip) ----
+// One piece of at most 16 KiB of an edge block's bytes on its way from the plan's scratch into a range's slot.
+struct ZhClipDesc {
+  uint64_t src;  // byte offset in the scratch
+  uint64_t dst;  // byte offset in d_dst
+  uint32_t len, pad;
+};
+// Device arrays of a ranges plan.  The blocks' arrays hold the blocks decoded in place first, the edge blocks (decoded
+// into scratch) behind them: a group of ranges is a launch over a stretch of either part.
+struct ZhRangesArgs {
+  const ZhBufDesc* bufs;        // [nblocks] src_off / src_len: the compressed bytes; dst_off / dst_cap: slot and promised size
+  const uint64_t* start_bit;    // [nblocks] the block's first bit, counted from src_off
+  uint64_t* blk_len;            // [nblocks] bytes the block's decoder made
+  int32_t* blk_status;          // [nblocks]
+  const uint32_t* first_block;  // [nranges + 1] range r's blocks are order[first_block[r] .. first_block[r + 1]) ...
+  const uint32_t* order;        //   ... positions in the blocks' arrays, in index order
+  const int32_t* fixed_status;  // [nranges] decided when the plan was made (ZH_OK: by the blocks)
+  const uint64_t* clip_len;     // [nranges] the range's length clipped at the stream's end
+  const ZhClipDesc* clips;
+  uint64_t* out_len;            // [nranges]
+  int32_t* status;              // [nranges]
+  uint32_t nranges;
+};
+extern "C" {
+void zh_launch_range_clip(hipStream_t, const uint8_t* d_scratch, uint8_t* d_dst, const ZhClipDesc* clips, uint32_t nclips);
+void zh_launch_ranges_reduce(hipStream_t, ZhRangesArgs a);
+}
+struct ZhRangesPlan {
+  ZhRangesArgs a{};
+  uint8_t* arena = nullptr;
+  uint8_t* scratch = nullptr;
+  uint32_t n_in_place = 0, n_scratch = 0;
+  // the groups of ranges that share the scratch in turn: stretches of the in-place blocks, the edge blocks and the clips
+  struct Group {
+    uint32_t ip0, nip, sc0, nsc, clip0, nclip;
+  };
+  std::vector<Group> groups;
+};
+
 // internal.nim:177-189 configurationTable (good, nice, chain); `lazy` is unused by the reference
 static const int kChainConfig[10][3] = {{0, 0, 0},     {4, 8, 4},      {4, 16, 8},    {4, 32, 32},
                                         {4, 16, 16},   {8, 32, 32},    {8, 128, 128}, {8, 256, 256},
@@ -122,6 +162,8 @@ struct zh_ctx {
     uint64_t stamp;
   };
   std::vector<DevBlock> dev_blocks;
+  // zh_debug_range_stats: the last ranges call / plan run (bytes over the link, blocks decoded in place / via scratch)
+  uint64_t rg_uploaded = 0, rg_in_place = 0, rg_via_scratch = 0;
   size_t dev_cached = 0, dev_cache_max = 0;
   uint64_t dev_stamp = 0;
   bool dev_poison = false;
@@ -234,6 +276,8 @@ struct zh_plan {
   bool tok_borrowed = false;  // the pool belongs to the caller (pipelined groups share one)
   ZhInflateArgs seg{};
   uint8_t* seg_arena = nullptr;
+  // byte-range reads (zh_plan_uncompress_ranges): n ranges; nothing above describes such a plan but ctx, n, out_len, status
+  ZhRangesPlan* rg = nullptr;
   // large streams decoded segment-wise (zh_inflate_seg.hip); the symbol and window buffers come
   // with the token pool
   bool segmented = false;
@@ -264,6 +308,39 @@ struct zh_plan {
 template <class T>
 static inline T* carve(uint8_t* base, size_t off) {
   return reinterpret_cast<T*>(base + off);
+}
+
+// What can be said of a block index without decoding (zh_plan_uncompress_indexed, zh_plan_uncompress_ranges): at
+// least one block, entry 0 at output byte 0, neither offset ever falling, every block's first bit inside the stream.
+static inline bool block_index_sound(const zh_block_entry* index, size_t n_entries, uint64_t src_len) {
+  if (n_entries < 2 || index[0].out_off != 0) return false;
+  for (size_t k = 0; k + 1 < n_entries; k++)
+    if (index[k + 1].out_off < index[k].out_off || index[k + 1].bit_off < index[k].bit_off ||
+        index[k].bit_off >= src_len * 8)
+      return false;
+  return true;
+}
+// One deflate block as the "stream" of a decoder that stops behind one block (zh_inflate_kernel with start_bit)
+static inline ZhBufDesc block_decoder_desc(uint64_t src_off, uint64_t src_len, uint64_t dst_off, uint64_t dst_cap) {
+  ZhBufDesc b;
+  memset(&b, 0, sizeof(b));
+  b.src_off = src_off;
+  b.src_len = src_len;
+  b.dst_off = dst_off;
+  b.dst_cap = dst_cap;
+  return b;
+}
+// ... and the launch of such decoders: `whole` stripped of everything a whole stream has
+static inline ZhInflateArgs block_decoder_args(const ZhBufDesc* bufs, const uint64_t* start_bit, uint32_t n,
+                                               uint64_t* out_len, int32_t* status) {
+  ZhInflateArgs g{};
+  g.bufs = bufs;
+  g.nbufs = n;
+  g.start_bit = start_bit;
+  g.single_block = 1;
+  g.out_len = out_len;
+  g.status = status;
+  return g;
 }
 
 static inline bool valid_block_bytes(size_t bb) {

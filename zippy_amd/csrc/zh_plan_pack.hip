@@ -108,7 +108,7 @@ void piece_geometry(uint64_t max_bytes, uint32_t* pieces, uint64_t* piece) {
 }  // namespace
 
 extern "C" int zh_plan_pack(zh_plan* plan, const void* d_slots, void* d_packed, uint64_t packed_cap, uint64_t* d_offsets) {
-  if (!plan) return ZH_ERR_ARGUMENT;
+  if (!plan || plan->rg) return ZH_ERR_ARGUMENT;
   zh_ctx* ctx = plan->ctx;
   if (!plan->n) {
     if (!d_offsets) return ZH_ERR_ARGUMENT;
@@ -131,7 +131,7 @@ extern "C" int zh_plan_pack(zh_plan* plan, const void* d_slots, void* d_packed, 
 }
 
 extern "C" int zh_plan_unpack(zh_plan* plan, const void* d_packed, const uint64_t* d_offsets, void* d_slots) {
-  if (!plan || plan->is_compress || plan->indexed) return ZH_ERR_ARGUMENT;
+  if (!plan || plan->is_compress || plan->indexed || plan->rg) return ZH_ERR_ARGUMENT;
   zh_ctx* ctx = plan->ctx;
   if (!plan->n) return ZH_OK;
   if (!d_packed || !d_offsets || !d_slots) return ZH_ERR_ARGUMENT;

@@ -67,6 +67,11 @@ extern "C" void zh_plan_destroy(zh_plan* p) {
   if (p->arena) ctx_free(p->ctx, p->arena);
   if (p->l1_pool_own) (void)hipFree(p->l1_pool_own);
   if (p->seg_arena) ctx_free(p->ctx, p->seg_arena);
+  if (p->rg) {
+    if (p->rg->arena) ctx_free(p->ctx, p->rg->arena);
+    if (p->rg->scratch) ctx_free(p->ctx, p->rg->scratch);
+    delete p->rg;
+  }
   if (p->tok_pool && !p->tok_borrowed) ctx_free(p->ctx, p->tok_pool);
   if (p->sg_arena) ctx_free(p->ctx, p->sg_arena);
   if (p->sg_sym) ctx_free(p->ctx, p->sg_sym);
@@ -270,6 +275,38 @@ static void seg_trace(zh_plan* p, hipStream_t s) {
   }
 }
 
+// A ranges plan (zh_ranges.hip), group by group through the scratch: the blocks that lie wholly inside their ranges
+// decode straight into the slots, the edge blocks into scratch, from where the clips take what belongs to the ranges;
+// the reduce kernel folds the blocks' results into the ranges' once every group is through.
+static int run_ranges(zh_plan* p, const uint8_t* d_src, uint8_t* d_dst) {
+  zh_ctx* ctx = p->ctx;
+  hipStream_t s = ctx->stream;
+  const ZhRangesPlan& R = *p->rg;
+  const ZhRangesArgs& a = R.a;
+  for (const ZhRangesPlan::Group& g : R.groups) {
+    const uint32_t sc0 = R.n_in_place + g.sc0;
+    if (g.nip) ZH_HIP(ctx, hipMemsetAsync(a.blk_status + g.ip0, 0, (size_t)g.nip * 4, s));
+    if (g.nsc) ZH_HIP(ctx, hipMemsetAsync(a.blk_status + sc0, 0, (size_t)g.nsc * 4, s));
+    prof_mark(p, "zh_inflate_kernel");
+    zh_launch_inflate(s, d_src, d_dst,
+                      block_decoder_args(a.bufs + g.ip0, a.start_bit + g.ip0, g.nip, a.blk_len + g.ip0, a.blk_status + g.ip0));
+    prof_mark(p, "zh_inflate_kernel");
+    zh_launch_inflate(s, d_src, R.scratch,
+                      block_decoder_args(a.bufs + sc0, a.start_bit + sc0, g.nsc, a.blk_len + sc0, a.blk_status + sc0));
+    prof_mark(p, "zh_range_clip_kernel");
+    zh_launch_range_clip(s, R.scratch, d_dst, a.clips + g.clip0, g.nclip);
+    ZH_HIP(ctx, hipGetLastError());
+  }
+  prof_mark(p, "zh_ranges_reduce_kernel");
+  zh_launch_ranges_reduce(s, a);
+  prof_mark(p, "end");
+  ZH_HIP(ctx, hipGetLastError());
+  ctx->rg_uploaded = 0;
+  ctx->rg_in_place = R.n_in_place;
+  ctx->rg_via_scratch = R.n_scratch;
+  return ZH_OK;
+}
+
 extern "C" int zh_plan_run(zh_plan* p, const void* d_src_v, void* d_dst_v) {
   if (!p) return ZH_ERR_ARGUMENT;
   zh_ctx* ctx = p->ctx;
@@ -280,6 +317,7 @@ extern "C" int zh_plan_run(zh_plan* p, const void* d_src_v, void* d_dst_v) {
   if (!p->n) return ZH_OK;
   // (a caller that drives two contexts' plans from one thread: the launches below go to the current device)
   ZH_HIP(ctx, hipSetDevice(ctx->device));
+  if (p->rg) return run_ranges(p, d_src, d_dst);
   AuxJoinGuard aux{ctx, s};
   if (p->is_compress) {
     const ZhCompressArgs& a = p->ca;
@@ -547,7 +585,7 @@ extern "C" int zh_debug_segment_stats(zh_ctx* ctx, uint64_t* cut, uint64_t* held
   return ZH_OK;
 }
 extern "C" int zh_plan_request_crc32(zh_plan* p, int on) {
-  if (!p) return ZH_ERR_ARGUMENT;
+  if (!p || p->rg) return ZH_ERR_ARGUMENT;
   p->force_crc = on != 0;
   return ZH_OK;
 }

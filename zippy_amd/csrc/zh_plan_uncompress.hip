@@ -308,11 +308,7 @@ extern "C" int zh_plan_uncompress_indexed(zh_ctx* ctx, uint64_t src_off, uint64_
   if (!ctx || !out || !index || n_entries < 2 || n_entries > 0xfffffffeull) return ZH_ERR_ARGUMENT;
   *out = nullptr;
   const size_t nseg = n_entries - 1;
-  for (size_t k = 0; k < nseg; k++)
-    if (index[k + 1].out_off < index[k].out_off || index[k + 1].bit_off < index[k].bit_off ||
-        index[k].bit_off >= src_len * 8)
-      return ZH_ERR_ARGUMENT;
-  if (index[0].out_off != 0) return ZH_ERR_ARGUMENT;
+  if (!block_index_sound(index, n_entries, src_len)) return ZH_ERR_ARGUMENT;
   if (index[nseg].out_off > dst_cap) return ZH_ERR_DST_TOO_SMALL;
   zh_plan* p = nullptr;
   const uint64_t total = index[nseg].out_off;
@@ -321,12 +317,7 @@ extern "C" int zh_plan_uncompress_indexed(zh_ctx* ctx, uint64_t src_off, uint64_
   std::vector<ZhBufDesc> segs(nseg);
   std::vector<uint64_t> start(nseg);
   for (size_t k = 0; k < nseg; k++) {
-    ZhBufDesc& b = segs[k];
-    memset(&b, 0, sizeof(b));
-    b.src_off = src_off;
-    b.src_len = src_len;
-    b.dst_off = dst_off + index[k].out_off;
-    b.dst_cap = index[k + 1].out_off - index[k].out_off;
+    segs[k] = block_decoder_desc(src_off, src_len, dst_off + index[k].out_off, index[k + 1].out_off - index[k].out_off);
     start[k] = index[k].bit_off;
   }
   Arena ar;
@@ -361,7 +352,7 @@ extern "C" int zh_plan_uncompress_indexed(zh_ctx* ctx, uint64_t src_off, uint64_
 }
 
 extern "C" int zh_plan_set_src_lens_device(zh_plan* plan, const uint64_t* d_lens) {
-  if (!plan || plan->is_compress) return ZH_ERR_ARGUMENT;
+  if (!plan || plan->is_compress || plan->rg) return ZH_ERR_ARGUMENT;
   plan->ia.src_len_dev = d_lens;
   // The segment geometry of a plan (zh_inflate_seg.hip: where block starts are searched for, where
   // the last block may begin, the token regions) was laid over the HOST lengths -- here the slots'

@@ -1,14 +1,16 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
 // The host side lives in fourteen files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
-// zh_plan_run.hip (kernel sequencing, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
+// zh_plan_run.hip (kernel sequencing -- run_compress, run_uncompress with run_segmented, run_ranges; work beside a run
+// on the context's second stream: SideLane --, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
 // wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
 // zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks), zh_ranges.hip (byte-range
 // reads from block-indexed streams: geometry, host call and its two kernels), the batch writers
 // zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
 // zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
 // all four share, zh_tar_dev.h and zh_zip_dev.h what the two of a format share, zh_gather.h the unaligned copy).
-// No compute happens on the host.
+// No compute happens on the host.  This header also holds what those files build their device memory with: DevMem /
+// DevBuf (owners that free through the context's cache) and Arena (the device arrays of a plan or call, each declared once).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -18,9 +20,11 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "zh_common.h"
@@ -112,18 +116,6 @@ extern "C" {
 void zh_launch_range_clip(hipStream_t, const uint8_t* d_scratch, uint8_t* d_dst, const ZhClipDesc* clips, uint32_t nclips);
 void zh_launch_ranges_reduce(hipStream_t, ZhRangesArgs a);
 }
-struct ZhRangesPlan {
-  ZhRangesArgs a{};
-  uint8_t* arena = nullptr;
-  uint8_t* scratch = nullptr;
-  uint32_t n_in_place = 0, n_scratch = 0;
-  // the groups of ranges that share the scratch in turn: stretches of the in-place blocks, the edge blocks and the clips
-  struct Group {
-    uint32_t ip0, nip, sc0, nsc, clip0, nclip;
-  };
-  std::vector<Group> groups;
-};
-
 // internal.nim:177-189 configurationTable (good, nice, chain); `lazy` is unused by the reference
 static const int kChainConfig[10][3] = {{0, 0, 0},     {4, 8, 4},      {4, 16, 8},    {4, 32, 32},
                                         {4, 16, 16},   {8, 32, 32},    {8, 128, 128}, {8, 256, 256},
@@ -194,13 +186,89 @@ static inline size_t typical_cap(size_t len, int fmt) {
 // ---------------------------------------------------------------------------
 // plans
 // ---------------------------------------------------------------------------
+// Device memory from the context's cache that goes back to it with its owner (ctx_malloc / ctx_free)
+template <class T>
+struct DevMem {
+  T* p = nullptr;
+  zh_ctx* ctx = nullptr;
+  DevMem() = default;
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  void release() {
+    if (p) ctx_free(ctx, p);
+    p = nullptr;
+  }
+  ~DevMem() { release(); }
+};
+using DevBuf = DevMem<uint8_t>;
+template <class T>
+static inline hipError_t dev_alloc(zh_ctx* ctx, DevMem<T>& b, size_t bytes) {
+  void* q = nullptr;
+  const hipError_t e = ctx_malloc(ctx, &q, bytes);
+  b.ctx = ctx;
+  b.p = e == hipSuccess ? static_cast<T*>(q) : nullptr;
+  return e;
+}
+
+// The device arrays of a plan or a call in one allocation, each declared once: add() takes the pointer to set, the
+// number of elements (their size is the pointee's) and, for an array that is uploaded, its host source.  Every array
+// starts at the next multiple of 256, in the order of the add() calls; an empty one still has its place, and its
+// pointer is not null.  alloc() takes `size` bytes from the context's cache, bind() sets every pointer, upload() sends
+// every source.  The pointers registered stay where they are until bind(), the sources until upload() has been waited for.
 struct Arena {
+  struct Slot {
+    void* target;
+    void (*set)(void* target, uint8_t* at);
+    size_t off, bytes;
+    const void* src;
+  };
+  std::vector<Slot> slots;
   size_t size = 0;
   uint8_t* base = nullptr;
-  size_t reserve(size_t bytes) {
-    size_t off = (size + 255) & ~(size_t)255;
+  template <class T>
+  void add(T*& ptr, size_t count, const typename std::remove_const<T>::type* src = nullptr) {
+    const size_t bytes = count * sizeof(T);
+    slots.push_back(Slot{(void*)&ptr, [](void* target, uint8_t* at) { *static_cast<T**>(target) = reinterpret_cast<T*>(at); },
+                         pad(bytes), bytes, src});
+  }
+  // bytes nothing points at (a tail behind the last array for kernels that read whole words or vectors) -> their offset
+  size_t pad(size_t bytes) {
+    const size_t off = (size + 255) & ~(size_t)255;
     size = off + bytes;
     return off;
+  }
+  hipError_t alloc(zh_ctx* ctx, DevBuf& mem, size_t extra = 0) {
+    const hipError_t e = dev_alloc(ctx, mem, size + extra);
+    base = mem.p;
+    return e;
+  }
+  void bind() const {
+    for (const Slot& s : slots) s.set(s.target, base + s.off);
+  }
+  hipError_t upload(hipStream_t stream) const {  // (the first error ends it)
+    for (const Slot& s : slots) {
+      if (!s.src || !s.bytes) continue;
+      const hipError_t e = hipMemcpyAsync(base + s.off, s.src, s.bytes, hipMemcpyHostToDevice, stream);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  // ... or copies them into a host image of the arena's first bytes, which the caller uploads in one piece
+  void gather(uint8_t* image) const {
+    for (const Slot& s : slots)
+      if (s.src && s.bytes) memcpy(image + s.off, s.src, s.bytes);
+  }
+  // the bound array `dev` in a host copy `image` of the arena's first bytes (a download of the caller's)
+  template <class T>
+  const T* host(const void* image, const T* dev) const {
+    return reinterpret_cast<const T*>(static_cast<const uint8_t*>(image) + (reinterpret_cast<const uint8_t*>(dev) - base));
+  }
+  // the array declared for `ptr`, all zero (its size is the declaration's)
+  template <class T>
+  hipError_t clear(T*& ptr, hipStream_t stream) const {
+    for (const Slot& s : slots)
+      if (s.target == (void*)&ptr) return hipMemsetAsync(base + s.off, 0, s.bytes, stream);
+    return hipErrorInvalidValue;
   }
 };
 
@@ -216,16 +284,33 @@ static inline uint64_t scratch_budget() {
   return (mb ? mb : 1ull) << 20;
 }
 
+// (zh_ranges.hip)
+struct ZhRangesPlan {
+  ZhRangesArgs a{};
+  DevBuf arena, scratch;
+  uint32_t n_in_place = 0, n_scratch = 0;
+  // the groups of ranges that share the scratch in turn: stretches of the in-place blocks, the edge blocks and the clips
+  struct Group {
+    uint32_t ip0, nip, sc0, nsc, clip0, nclip;
+  };
+  std::vector<Group> groups;
+};
+
 struct ZhPlanRange {
   uint32_t b0, nb, f0, nf;
+};
+// The timing events of a profiled run on one stream and the names of the launches they were recorded in front of
+// (prof_mark, zh_plan_kernel_times)
+struct ProfLane {
+  std::vector<const char*> names;
+  std::vector<hipEvent_t> events;
 };
 struct zh_plan {
   zh_ctx* ctx = nullptr;
   bool is_compress = true;
   size_t n = 0;
   int level = 0, fmt = 0;
-  int count_only = 0;
-  uint8_t* arena = nullptr;
+  DevBuf arena;
   ZhCompressArgs ca{};
   ZhInflateArgs ia{};
   ZhBufDesc* d_bufs = nullptr;
@@ -233,8 +318,8 @@ struct zh_plan {
   uint32_t npieces = 0;
   uint32_t *piece_crc = nullptr, *piece_adler = nullptr, *piece_len = nullptr;
   uint32_t *buf_crc = nullptr, *buf_adler = nullptr;
-  uint32_t* head_scratch = nullptr;  // chain levels: `head` per block, previous-position links and
-  size_t head_bytes = 0;             // best match per position (zh_chain_match.hip)
+  // chain levels: `head` per block, previous-position links and best match per position (zh_chain_match.hip)
+  uint32_t* head_scratch = nullptr;
   uint16_t* l1_tables = nullptr;  // BestSpeed: pool of per-wave hash tables (zh_l1_match.hip)
   void* l1_pool_own = nullptr;    // ... when it is an allocation of its own (ZH_L1_POOL: uncached / fine-grained memory)
   uint32_t* l1_counter = nullptr; // ... and the counter its waves draw fragments from
@@ -248,19 +333,15 @@ struct zh_plan {
   // run clears it before anything reads it
   bool chain_best_dirty = false;
   // chain levels: the ranges of blocks (first block, blocks, first fragment, fragments) that share the scratch in turn
-  struct ChainRange {
-    uint32_t b0, nb, f0, nf;
-  };
-  std::vector<ChainRange> chain_ranges;
+  std::vector<ZhPlanRange> chain_ranges;
   size_t chain_scratch_frags = 0;  // fragments the scratch holds (the largest range)
   // split inflate: the groups of streams (first, count) that share the token pool in turn
   std::vector<std::pair<uint32_t, uint32_t>> tok_groups;
   uint64_t dst_max_cap = 0;
   uint64_t* out_len = nullptr;
   int32_t* status = nullptr;
-  const uint64_t* src_len_dev = nullptr;
-  uint64_t src_max_len = 0;         // uncompress plans: the longest source slot (zh_plan_unpack's grid)
-  uint64_t* unpack_lens = nullptr;  // ... and the device-side lengths zh_plan_unpack leaves (allocated by its first call)
+  uint64_t src_max_len = 0;      // uncompress plans: the longest source slot (zh_plan_unpack's grid)
+  DevMem<uint64_t> unpack_lens;  // ... and the device-side lengths zh_plan_unpack leaves (allocated by its first call)
   // block index (zh_plan_block_index): host copies of the geometry
   std::vector<ZhBufDesc> h_bufs;
   uint32_t half_piece = 0;  // uncompress plans: the first checksum piece of buffer n / 2 (the batch as two halves, zh_plan_run)
@@ -268,16 +349,17 @@ struct zh_plan {
   // block-parallel decode (zh_plan_uncompress_indexed): `ia` describes the one stream, `seg` its blocks
   bool force_crc = false;  // CRC-32 of the uncompressed side whatever the container (ZIP entries)
   bool indexed = false;
-  // split inflate (zh_inflate_split.hip): per-stream token buffers, allocated on the first run
+  // split inflate (zh_inflate_split.hip): per-stream token buffers, allocated on the first run (tok_own) or the
+  // caller's (pipelined groups share one: plan_lend_token_pool)
   uint32_t* tok_pool = nullptr;
+  DevMem<uint32_t> tok_own;
   uint64_t tok_words = 0;
   const uint64_t *tok_off = nullptr, *tok_cap = nullptr;
   bool tok_failed = false;
-  bool tok_borrowed = false;  // the pool belongs to the caller (pipelined groups share one)
   ZhInflateArgs seg{};
-  uint8_t* seg_arena = nullptr;
+  DevBuf seg_arena;
   // byte-range reads (zh_plan_uncompress_ranges): n ranges; nothing above describes such a plan but ctx, n, out_len, status
-  ZhRangesPlan* rg = nullptr;
+  std::unique_ptr<ZhRangesPlan> rg;
   // large streams decoded segment-wise (zh_inflate_seg.hip); the symbol and window buffers come
   // with the token pool
   bool segmented = false;
@@ -286,29 +368,20 @@ struct zh_plan {
   bool sg_trace = false;
   int sg_repair_rounds = 1;  // zh_seg_repair_kernel: twice where there is a lot to go wrong (plan_segments)
   ZhSegArgs sg{};
-  uint8_t* sg_arena = nullptr;
-  uint16_t* sg_sym = nullptr;
-  uint8_t* sg_windows = nullptr;
-  uint16_t* sg_winsym = nullptr;
+  DevBuf sg_arena;
+  DevMem<uint16_t> sg_sym;
+  DevBuf sg_windows;
+  DevMem<uint16_t> sg_winsym;
   uint64_t sg_sym_count = 0;
   // profiling
   bool profiling = false;
-  bool trailer_late = false;
-  uint32_t halves_min = 0;    // uncompress: batches of at least this many streams go as two halves on two streams (0: never; zh_plan_run.hip)  // compress: the checksum joins behind the emission (large batches; zh_plan_run.hip)
-  std::vector<const char*> k_names;
-  std::vector<hipEvent_t> k_events;
-  std::vector<float> k_ms;
-  // kernels on the context's second stream (the checksum of a compress run): start / between / end
-  hipEvent_t k_aux[3] = {nullptr, nullptr, nullptr};
-  bool k_aux_used = false;
-  hipEvent_t k_half[3] = {nullptr, nullptr, nullptr};  // ... of the second half's tokens kernel and writer (uncompress plans)
-  bool k_half_used = false;
+  bool trailer_late = false;  // compress: the checksum joins behind the emission (large batches; zh_plan_run.hip)
+  // uncompress: batches of at least this many streams go as two halves on two streams (0: never; zh_plan_run.hip)
+  uint32_t halves_min = 0;
+  // the launches on the context's stream, and those beside them on its second stream (the checksum of a compress
+  // run, the second half of an uncompress batch): reported behind the others
+  ProfLane k_main, k_side;
 };
-
-template <class T>
-static inline T* carve(uint8_t* base, size_t off) {
-  return reinterpret_cast<T*>(base + off);
-}
 
 // What can be said of a block index without decoding (zh_plan_uncompress_indexed, zh_plan_uncompress_ranges): at
 // least one block, entry 0 at output byte 0, neither offset ever falling, every block's first bit inside the stream.
@@ -357,17 +430,6 @@ static inline void plan_set_count_only(zh_plan* plan, int on) { plan->ia.count_o
 // ---------------------------------------------------------------------------
 // host-buffer API: device buffers of a call, plans that go away with their scope, phase timing
 // ---------------------------------------------------------------------------
-struct DevBuf {
-  uint8_t* p = nullptr;
-  zh_ctx* ctx = nullptr;
-  ~DevBuf() {
-    if (p) ctx_free(ctx, p);
-  }
-};
-static inline hipError_t dev_alloc(zh_ctx* ctx, DevBuf& b, size_t bytes) {
-  b.ctx = ctx;
-  return ctx_malloc(ctx, (void**)&b.p, bytes);
-}
 struct PlanGuard {
   zh_plan* p = nullptr;
   ~PlanGuard() { zh_plan_destroy(p); }

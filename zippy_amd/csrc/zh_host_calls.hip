@@ -140,24 +140,28 @@ static int checksum_host(zh_ctx* ctx, const void* const* srcs, const size_t* len
   }
   const size_t np = pieces.size();
   if (np >= 0xffffffffull) return ZH_ERR_ARGUMENT;
+  const ZhBufDesc* d_bufs;
+  const ZhPieceDesc* d_pieces;
+  uint32_t *piece_crc, *piece_len, *piece_adler, *out_crc, *out_adler;
   Arena ar;
-  const size_t o_b = ar.reserve(n * sizeof(ZhBufDesc)), o_p = ar.reserve(np * sizeof(ZhPieceDesc)),
-               o_pc = ar.reserve(np * 4), o_pl = ar.reserve(np * 4), o_pa = ar.reserve(np * 4),
-               o_oc = ar.reserve(n * 4), o_oa = ar.reserve(n * 4);
-  ar.reserve(256);
+  ar.add(d_bufs, n, bufs.data());
+  ar.add(d_pieces, np, pieces.data());
+  ar.add(piece_crc, np);
+  ar.add(piece_len, np);
+  ar.add(piece_adler, np);
+  ar.add(out_crc, n);
+  ar.add(out_adler, n);
+  ar.pad(256);
   DevBuf scratch;
-  if (dev_alloc(ctx, scratch, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
-  uint8_t* base = scratch.p;
+  if (ar.alloc(ctx, scratch) != hipSuccess) return ZH_ERR_NOMEM;
+  ar.bind();
   hipStream_t s = ctx->stream;
-  ZH_HIP(ctx, hipMemcpyAsync(base + o_b, bufs.data(), n * sizeof(ZhBufDesc), hipMemcpyHostToDevice, s));
-  if (np) ZH_HIP(ctx, hipMemcpyAsync(base + o_p, pieces.data(), np * sizeof(ZhPieceDesc), hipMemcpyHostToDevice, s));
-  zh_launch_checksum_pieces(s, ctx->cktabs, d.p, carve<ZhPieceDesc>(base, o_p), (uint32_t)np, nullptr, want_crc,
-                            !want_crc, carve<uint32_t>(base, o_pc), carve<uint32_t>(base, o_pa),
-                            carve<uint32_t>(base, o_pl));
-  zh_launch_checksum_combine(s, ctx->cktabs, carve<ZhBufDesc>(base, o_b), (uint32_t)n, carve<uint32_t>(base, o_pc),
-                             carve<uint32_t>(base, o_pa), carve<uint32_t>(base, o_pl), want_crc, !want_crc,
-                             carve<uint32_t>(base, o_oc), carve<uint32_t>(base, o_oa));
-  ZH_HIP(ctx, hipMemcpyAsync(out, base + (want_crc ? o_oc : o_oa), n * 4, hipMemcpyDeviceToHost, s));
+  ZH_HIP(ctx, ar.upload(s));
+  zh_launch_checksum_pieces(s, ctx->cktabs, d.p, d_pieces, (uint32_t)np, nullptr, want_crc, !want_crc, piece_crc,
+                            piece_adler, piece_len);
+  zh_launch_checksum_combine(s, ctx->cktabs, d_bufs, (uint32_t)n, piece_crc, piece_adler, piece_len, want_crc,
+                             !want_crc, out_crc, out_adler);
+  ZH_HIP(ctx, hipMemcpyAsync(out, want_crc ? out_crc : out_adler, n * 4, hipMemcpyDeviceToHost, s));
   ZH_HIP(ctx, hipStreamSynchronize(s));
   return ZH_OK;
 }

@@ -74,26 +74,41 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
   const bool chain = level == -1 || level >= 2;
   const bool need_matches = level != 0;
 
+  ZhCompressArgs& a = p->ca;
   Arena ar;
-  const size_t o_bufs = ar.reserve(n * sizeof(ZhBufDesc));
-  const size_t o_blocks = ar.reserve(nb * sizeof(ZhBlockDesc));
-  const size_t o_frags = ar.reserve(nf * sizeof(ZhFragDesc));
-  const size_t o_pieces = ar.reserve(nf * sizeof(ZhPieceDesc));
+  ar.add(p->d_bufs, n, bufs.data());
+  ar.add(a.blocks, nb, blocks.data());
+  ar.add(a.frags, nf, frags.data());
+  ar.add(p->d_pieces, nf, pieces.data());
   const size_t mslots = need_matches ? nf * ZH_MAX_MATCHES_PER_FRAG : 0;
-  const size_t o_mpos = ar.reserve(mslots * 2), o_mlen = ar.reserve(mslots * 2), o_moff = ar.reserve(mslots * 2);
-  const size_t o_fnm = ar.reserve(nf * 4), o_fsp = ar.reserve(nf * 4), o_fnl = ar.reserve(nf * 4),
-               o_fex = ar.reserve(nf * 4), o_fhist = ar.reserve(nf * ZH_HIST_STRIDE * 2),
-               o_fbits = ar.reserve(nf * 4), o_fstart = ar.reserve(nf * 8);
-  const size_t o_pcrc = ar.reserve(nf * 4), o_pad = ar.reserve(nf * 4), o_plen = ar.reserve(nf * 4);
+  ar.add(a.m_pos, mslots);
+  ar.add(a.m_len, mslots);
+  ar.add(a.m_off, mslots);
+  ar.add(a.f_nmatch, nf);
+  ar.add(a.f_spill, nf);
+  ar.add(a.f_nlit, nf);
+  ar.add(a.f_extra_bits, nf);
+  ar.add(a.f_hist, nf * ZH_HIST_STRIDE);
+  ar.add(a.f_bits, nf);
+  ar.add(a.f_bit_start, nf);
+  ar.add(p->piece_crc, nf);
+  ar.add(p->piece_adler, nf);
+  ar.add(p->piece_len, nf);
   // (the exact BestSpeed parse and level -2 hand the emission their coverage bitmap: 4 KiB a fragment)
   const bool cover_out = level == 1 || level == -2;
-  const size_t o_fcov = ar.reserve(cover_out ? nf * 4096 : 0);
-  const size_t o_bmode = ar.reserve(nb * 4), o_blit = ar.reserve(nb * 288 * 4),
-               o_bdist = ar.reserve(nb * 32 * 4), o_bhdr = ar.reserve(nb * ZH_HDR_WORDS * 4),
-               o_bhb = ar.reserve(nb * 4), o_bbits = ar.reserve(nb * 8), o_bd0 = ar.reserve(nb * 8),
-               o_bst = ar.reserve((nb + n) * 8);
-  const size_t o_bcrc = ar.reserve(n * 4), o_bad = ar.reserve(n * 4), o_olen = ar.reserve(n * 8),
-               o_st = ar.reserve(n * 4);
+  ar.add(a.f_cover, cover_out ? nf * 1024 : 0);
+  ar.add(a.b_mode, nb);
+  ar.add(a.b_litcode, nb * 288);
+  ar.add(a.b_distcode, nb * 32);
+  ar.add(a.b_hdr, nb * ZH_HDR_WORDS);
+  ar.add(a.b_hdr_bits, nb);
+  ar.add(a.b_bits, nb);
+  ar.add(a.b_stored_d0, nb);
+  ar.add(a.b_start, nb + n);
+  ar.add(p->buf_crc, n);
+  ar.add(p->buf_adler, n);
+  ar.add(p->out_len, n);
+  ar.add(p->status, n);
   // chain levels: ranges of whole blocks whose scratch (12 bytes a position + the links' tables) fits the budget
   size_t range_blocks = 0, range_frags = 0;
   if (chain && nb) {
@@ -104,7 +119,7 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
     for (size_t b = 0; b < nb; b++) {
       const uint64_t need = blocks[b].nfrag * per_frag + per_block;
       if (cur.nb && cur_bytes + need > budget) {
-        p->chain_ranges.push_back({cur.b0, cur.nb, cur.f0, cur.nf});
+        p->chain_ranges.push_back(cur);
         cur = ZhPlanRange{(uint32_t)b, 0, blocks[b].first_frag, 0};
         cur_bytes = 0;
       }
@@ -112,7 +127,7 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
       cur.nf += blocks[b].nfrag;
       cur_bytes += need;
     }
-    p->chain_ranges.push_back({cur.b0, cur.nb, cur.f0, cur.nf});
+    p->chain_ranges.push_back(cur);
     for (const auto& r : p->chain_ranges) {
       range_blocks = std::max<size_t>(range_blocks, r.nb);
       range_frags = std::max<size_t>(range_frags, r.nf);
@@ -121,10 +136,10 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
   p->chain_scratch_frags = range_frags;
   if (p->chain_ranges.size() > 1 && getenv("ZH_TRACE"))
     fprintf(stderr, "zippy_hip: chain scratch for %zu of %zu fragments: %zu ranges of blocks\n", range_frags, nf, p->chain_ranges.size());
-  p->head_bytes = !chain ? 0
-                  : range_blocks <= zh_chain_prev_slice() ? range_blocks * ((size_t)ZH_CHAIN_HEAD_WORDS * 4)
-                                                          : range_blocks * ((size_t)2 << 17);  // (zh_launch_chain_prev)
-  const size_t o_head = ar.reserve(p->head_bytes);
+  const size_t head_words = !chain ? 0
+                            : range_blocks <= zh_chain_prev_slice() ? range_blocks * (size_t)ZH_CHAIN_HEAD_WORDS
+                                                                    : range_blocks * ((size_t)2 << 15);  // (zh_launch_chain_prev)
+  ar.add(p->head_scratch, head_words);
   // one 32 KiB hash table per persistent matcher wave (zh_launch_l1_match: min(fragments, slots) waves)
   // (the parallel parse, zh_launch_l1p_match, keeps 128 KiB of table results per workgroup there instead)
   const size_t l1tab_bytes = level == 1 ? std::max(std::min<size_t>(nf, zh_l1_table_slots()) * 32768,
@@ -137,15 +152,17 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
     return !e ? 0 : strcmp(e, "uncached") == 0 ? 1 : strcmp(e, "fine") == 0 ? 2 : 0;
   }();
   const bool l1_pool_own = l1_pool_mode != 0 && l1tab_bytes != 0;
-  const size_t o_l1tab = ar.reserve(l1_pool_own ? 0 : l1tab_bytes);
-  const size_t o_l1ctr = ar.reserve(256);
+  ar.add(p->l1_tables, l1_pool_own ? 0 : l1tab_bytes / 2);
+  ar.add(p->l1_counter, 64);
   const bool l1 = level == 1 || level == -2;
-  const size_t o_l1cost = ar.reserve(l1 ? nf * 4 : 4), o_l1order = ar.reserve(l1 ? nf * 4 : 4), o_l1hist = ar.reserve(512 + (l1 ? (nf / 256 + 2) * 4 : 0));
-  const size_t o_cprev = ar.reserve(chain ? range_frags * (size_t)ZH_FRAG_SIZE * 8 : 0);
-  const size_t o_cbest = ar.reserve(chain ? range_frags * (size_t)ZH_FRAG_SIZE * 4 : 0);
-  ar.reserve(256);
+  ar.add(p->l1_cost, l1 ? nf : 1);
+  ar.add(p->l1_order, l1 ? nf : 1);
+  ar.add(p->l1_hist, 128 + (l1 ? nf / 256 + 2 : 0));
+  ar.add(p->chain_prev, chain ? range_frags * (size_t)ZH_FRAG_SIZE : 0);
+  ar.add(p->chain_best, chain ? range_frags * (size_t)ZH_FRAG_SIZE : 0);
+  ar.pad(256);
 
-  if (ctx_malloc(p->ctx, (void**)&p->arena, ar.size) != hipSuccess) {
+  if (ar.alloc(ctx, p->arena) != hipSuccess) {
     ctx->last_error = "hipMalloc(plan arena, " + std::to_string(ar.size) + " bytes)";
     delete p;
     return ZH_ERR_NOMEM;
@@ -164,24 +181,19 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
     return ZH_ERR_NOMEM;
   }
 #endif
-  uint8_t* base = p->arena;
   hipStream_t s = ctx->stream;
-  hipError_t up = hipSuccess;
+  hipError_t up = ar.upload(s);
   auto chk = [&](hipError_t e) {
     if (up == hipSuccess) up = e;
   };
-  chk(hipMemcpyAsync(base + o_bufs, bufs.data(), n * sizeof(ZhBufDesc), hipMemcpyHostToDevice, s));
-  chk(hipMemcpyAsync(base + o_blocks, blocks.data(), nb * sizeof(ZhBlockDesc), hipMemcpyHostToDevice, s));
-  chk(hipMemcpyAsync(base + o_frags, frags.data(), nf * sizeof(ZhFragDesc), hipMemcpyHostToDevice, s));
-  chk(hipMemcpyAsync(base + o_pieces, pieces.data(), nf * sizeof(ZhPieceDesc), hipMemcpyHostToDevice, s));
-  chk(hipMemsetAsync(base + o_fnm, 0, nf * 4, s));
-  chk(hipMemsetAsync(base + o_fsp, 0, nf * 4, s));
-  chk(hipMemsetAsync(base + o_fhist, 0, nf * ZH_HIST_STRIDE * 2, s));
-  chk(hipMemsetAsync(base + o_fnl, 0, nf * 4, s));
-  chk(hipMemsetAsync(base + o_fex, 0, nf * 4, s));
+  chk(ar.clear(a.f_nmatch, s));
+  chk(ar.clear(a.f_spill, s));
+  chk(ar.clear(a.f_hist, s));
+  chk(ar.clear(a.f_nlit, s));
+  chk(ar.clear(a.f_extra_bits, s));
   // best[] starts out all "not worked out" -- once: every run leaves it that way again (the links kernel
   // clears the sorted positions it has borrowed the array for, zh_chain_class_links_kernel)
-  if (chain && nf) chk(hipMemsetAsync(base + o_cbest, 0, range_frags * (size_t)ZH_FRAG_SIZE * 4, s));
+  if (chain && nf) chk(ar.clear(p->chain_best, s));
   chk(hipStreamSynchronize(s));  // host vectors go out of scope
   if (up != hipSuccess) {
     ctx->last_error = std::string("plan upload: ") + hipGetErrorString(up);
@@ -189,11 +201,15 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
     return ZH_ERR_DEVICE;
   }
 
-  ZhCompressArgs& a = p->ca;
-  a.bufs = p->d_bufs = carve<ZhBufDesc>(base, o_bufs);
-  a.blocks = carve<ZhBlockDesc>(base, o_blocks);
-  a.frags = carve<ZhFragDesc>(base, o_frags);
-  p->d_pieces = carve<ZhPieceDesc>(base, o_pieces);
+  ar.bind();
+  a.bufs = p->d_bufs;
+  a.f_crc = p->piece_crc;
+  a.f_adler = p->piece_adler;
+  a.out_len = p->out_len;
+  a.status = p->status;
+  if (!cover_out) a.f_cover = nullptr;
+  if (p->l1_pool_own) p->l1_tables = static_cast<uint16_t*>(p->l1_pool_own);
+  if (!l1) p->l1_cost = p->l1_order = p->l1_hist = nullptr;
   p->npieces = (uint32_t)nf;
   // the checksum beside the emission as well, the trailer by a kernel of its own behind it: worth its launch from
   // 256 MiB of input on (4096 x 1 MiB: 0.25 ms of 73; 1024 x 64 KiB: 0.5 % slower).  ZH_TRAILER_LATE=0 / 1: never / always.
@@ -204,42 +220,6 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
   a.nbufs = (uint32_t)n;
   a.level = level;
   a.data_format = data_format;
-  a.m_pos = carve<uint16_t>(base, o_mpos);
-  a.m_len = carve<uint16_t>(base, o_mlen);
-  a.m_off = carve<uint16_t>(base, o_moff);
-  a.f_nmatch = carve<uint32_t>(base, o_fnm);
-  a.f_spill = carve<uint32_t>(base, o_fsp);
-  a.f_nlit = carve<uint32_t>(base, o_fnl);
-  a.f_extra_bits = carve<uint32_t>(base, o_fex);
-  a.f_hist = carve<uint16_t>(base, o_fhist);
-  a.f_cover = cover_out ? carve<uint32_t>(base, o_fcov) : nullptr;
-  a.f_crc = p->piece_crc = carve<uint32_t>(base, o_pcrc);
-  a.f_adler = p->piece_adler = carve<uint32_t>(base, o_pad);
-  p->piece_len = carve<uint32_t>(base, o_plen);
-  a.f_bits = carve<uint32_t>(base, o_fbits);
-  a.f_bit_start = carve<uint64_t>(base, o_fstart);
-  a.b_mode = carve<uint32_t>(base, o_bmode);
-  a.b_litcode = carve<uint32_t>(base, o_blit);
-  a.b_distcode = carve<uint32_t>(base, o_bdist);
-  a.b_hdr = carve<uint32_t>(base, o_bhdr);
-  a.b_hdr_bits = carve<uint32_t>(base, o_bhb);
-  a.b_bits = carve<uint64_t>(base, o_bbits);
-  a.b_stored_d0 = carve<uint64_t>(base, o_bd0);
-  a.b_start = carve<uint64_t>(base, o_bst);
-  p->buf_crc = carve<uint32_t>(base, o_bcrc);
-  p->buf_adler = carve<uint32_t>(base, o_bad);
-  a.out_len = p->out_len = carve<uint64_t>(base, o_olen);
-  a.status = p->status = carve<int32_t>(base, o_st);
-  p->head_scratch = carve<uint32_t>(base, o_head);
-  p->l1_tables = p->l1_pool_own ? static_cast<uint16_t*>(p->l1_pool_own) : carve<uint16_t>(base, o_l1tab);
-  p->l1_counter = carve<uint32_t>(base, o_l1ctr);
-  if (l1) {
-    p->l1_cost = carve<uint32_t>(base, o_l1cost);
-    p->l1_order = carve<uint32_t>(base, o_l1order);
-    p->l1_hist = carve<uint32_t>(base, o_l1hist);
-  }
-  p->chain_prev = carve<uint64_t>(base, o_cprev);
-  p->chain_best = carve<uint32_t>(base, o_cbest);
   p->h_bufs.swap(bufs);
   p->h_blocks.swap(blocks);
   *out = p;

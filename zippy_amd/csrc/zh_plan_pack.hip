@@ -140,16 +140,13 @@ extern "C" int zh_plan_unpack(zh_plan* plan, const void* d_packed, const uint64_
   uint64_t piece;
   piece_geometry(plan->src_max_len, &pieces, &piece);
   if ((uint64_t)plan->n * pieces > 0x7fffffffull) return ZH_ERR_ARGUMENT;  // (before anything is launched or written)
-  if (!plan->unpack_lens) {
-    void* p = nullptr;
-    ZH_HIP(ctx, ctx_malloc(ctx, &p, plan->n * sizeof(uint64_t)));
-    plan->unpack_lens = static_cast<uint64_t*>(p);
-  }
+  if (!plan->unpack_lens.p) ZH_HIP(ctx, dev_alloc(ctx, plan->unpack_lens, plan->n * sizeof(uint64_t)));
+  uint64_t* const lens = plan->unpack_lens.p;  // (a plain pointer: a launch must not take the owner along)
   hipLaunchKernelGGL(zh_unpack_lens_kernel, dim3(((uint32_t)plan->n + 255u) / 256u), dim3(256), 0, ctx->stream,
-                     (uint32_t)plan->n, plan->d_bufs, d_offsets, plan->unpack_lens);
+                     (uint32_t)plan->n, plan->d_bufs, d_offsets, lens);
   hipLaunchKernelGGL((zh_pack_copy_kernel<true>), dim3((uint32_t)plan->n * pieces), dim3(256), 0, ctx->stream,
                      static_cast<const uint8_t*>(d_packed), static_cast<uint8_t*>(d_slots), plan->d_bufs, d_offsets, pieces,
                      piece, ~0ull);
   ZH_HIP(ctx, hipGetLastError());
-  return zh_plan_set_src_lens_device(plan, plan->unpack_lens);
+  return zh_plan_set_src_lens_device(plan, lens);
 }

@@ -86,84 +86,61 @@ static void plan_segments(zh_plan* p, const std::vector<ZhBufDesc>& bufs, uint64
   first_seg[n] = (uint32_t)parent.size();
   const size_t ns = parent.size();
   if (ns > 0x7fffffffu) return;
-  Arena ar;
-  const size_t o_parent = ar.reserve(ns * 4), o_first = ar.reserve((n + 1) * 4), o_nom = ar.reserve(ns * 8),
-               o_search = ar.reserve(ns * 8), o_toff = ar.reserve(ns * 8), o_tcap = ar.reserve(ns * 8),
-               o_symb = ar.reserve(n * 8), o_start = ar.reserve(ns * 8), o_start2 = ar.reserve(ns * 8), o_end = ar.reserve(ns * 8),
-               o_final = ar.reserve(ns * 4), o_sst = ar.reserve(ns * 4), o_sout = ar.reserve(ns * 8),
-               o_wlen = ar.reserve(ns * 8), o_valid = ar.reserve(ns * 4), o_prev = ar.reserve(ns * 4),
-               o_ostart = ar.reserve(ns * 8), o_sok = ar.reserve(n * 4), o_order = ar.reserve(ns * 4),
-               o_nchain = ar.reserve(n * 4), o_repair = ar.reserve(n * 4), o_ordinal = ar.reserve(ns * 4), o_go = ar.reserve(n * 4), o_etoff = ar.reserve(ns * 8), o_etcap = ar.reserve(ns * 8), o_substart = ar.reserve(ns * 8), o_subhdr = ar.reserve(ns * 8),
-               o_issub = ar.reserve(ns * 4), o_held = ar.reserve(ns * 8), o_stored = ar.reserve(ns * 8);
   const size_t nfind = find_seg.size();
-  const size_t o_fseg = ar.reserve(nfind * 4), o_fbatch = ar.reserve(nfind * 4), o_cn = ar.reserve(nfind * 4),
-               o_coff = ar.reserve(nfind * (size_t)kSegFindSlots * 4);
-  ar.reserve(256);
-  if (ctx_malloc(p->ctx, (void**)&p->sg_arena, ar.size) != hipSuccess) {
+  ZhSegArgs& g = p->sg;
+  Arena ar;
+  ar.add(g.parent, ns, parent.data());
+  ar.add(g.first_seg, n + 1, first_seg.data());
+  ar.add(g.nominal_bit, ns, nominal.data());
+  ar.add(g.search_bits, ns, search.data());
+  ar.add(g.tok_off, ns, toff.data());
+  ar.add(g.tok_cap, ns, tcap.data());
+  ar.add(g.sym_base, n, sym_base.data());
+  ar.add(g.start_bit, ns);
+  ar.add(g.start2_bit, ns);
+  ar.add(g.end_bit, ns);
+  ar.add(g.final_block, ns);
+  ar.add(g.seg_status, ns);
+  ar.add(g.seg_out, ns);
+  ar.add(g.wr_len, ns);
+  ar.add(g.valid, ns);
+  ar.add(g.prev, ns);
+  ar.add(g.out_start, ns);
+  ar.add(g.stream_ok, n);
+  ar.add(g.order, ns);
+  ar.add(g.nchain, n);
+  ar.add(g.repair, n);
+  ar.add(g.ordinal, ns);
+  ar.add(g.go, n);
+  ar.add(g.eff_tok_off, ns);
+  ar.add(g.eff_tok_cap, ns);
+  ar.add(g.sub_start, ns);
+  ar.add(g.sub_hdr, ns);
+  ar.add(g.is_sub, ns);
+  ar.add(g.held_start, ns);
+  ar.add(g.stored_bit, ns);
+  ar.add(g.find_seg, nfind, find_seg.data());
+  ar.add(g.find_batch, nfind, find_batch.data());
+  ar.add(g.cand_n, nfind);
+  ar.add(g.cand_off, nfind * (size_t)kSegFindSlots);
+  ar.pad(256);
+  if (ar.alloc(ctx, p->sg_arena) != hipSuccess) {
     (void)hipGetLastError();
-    p->sg_arena = nullptr;
     return;
   }
-  uint8_t* base = p->sg_arena;
   hipStream_t s = ctx->stream;
-  hipError_t up = hipMemsetAsync(base, 0, ar.size, s);
-  auto put = [&](size_t off, const void* src, size_t bytes) {
-    if (up == hipSuccess) up = hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, s);
-  };
-  put(o_parent, parent.data(), ns * 4);
-  put(o_first, first_seg.data(), (n + 1) * 4);
-  put(o_nom, nominal.data(), ns * 8);
-  put(o_search, search.data(), ns * 8);
-  put(o_toff, toff.data(), ns * 8);
-  put(o_tcap, tcap.data(), ns * 8);
-  put(o_symb, sym_base.data(), n * 8);
-  put(o_fseg, find_seg.data(), nfind * 4);
-  put(o_fbatch, find_batch.data(), nfind * 4);
+  hipError_t up = hipMemsetAsync(ar.base, 0, ar.size, s);
+  if (up == hipSuccess) up = ar.upload(s);
   if (up == hipSuccess) up = hipStreamSynchronize(s);
   if (up != hipSuccess) {
     (void)hipGetLastError();
-    ctx_free(p->ctx, p->sg_arena);
-    p->sg_arena = nullptr;
+    p->sg_arena.release();
     return;
   }
-  ZhSegArgs& g = p->sg;
+  ar.bind();
   g.nsegs = (uint32_t)ns;
   g.nstreams = (uint32_t)n;
-  g.parent = carve<uint32_t>(base, o_parent);
-  g.first_seg = carve<uint32_t>(base, o_first);
-  g.nominal_bit = carve<uint64_t>(base, o_nom);
-  g.search_bits = carve<uint64_t>(base, o_search);
-  g.tok_off = carve<uint64_t>(base, o_toff);
-  g.tok_cap = carve<uint64_t>(base, o_tcap);
-  g.sym_base = carve<uint64_t>(base, o_symb);
-  g.start_bit = carve<uint64_t>(base, o_start);
-  g.start2_bit = carve<uint64_t>(base, o_start2);
-  g.stored_bit = carve<uint64_t>(base, o_stored);
-  g.end_bit = carve<uint64_t>(base, o_end);
-  g.final_block = carve<uint32_t>(base, o_final);
-  g.seg_status = carve<int32_t>(base, o_sst);
-  g.seg_out = carve<uint64_t>(base, o_sout);
-  g.wr_len = carve<uint64_t>(base, o_wlen);
-  g.valid = carve<uint32_t>(base, o_valid);
-  g.prev = carve<uint32_t>(base, o_prev);
-  g.out_start = carve<uint64_t>(base, o_ostart);
-  g.stream_ok = carve<uint32_t>(base, o_sok);
-  g.order = carve<uint32_t>(base, o_order);
-  g.nchain = carve<uint32_t>(base, o_nchain);
-  g.repair = carve<uint32_t>(base, o_repair);
-  g.ordinal = carve<uint32_t>(base, o_ordinal);
-  g.go = carve<uint32_t>(base, o_go);
-  g.eff_tok_off = carve<uint64_t>(base, o_etoff);
-  g.eff_tok_cap = carve<uint64_t>(base, o_etcap);
-  g.sub_start = carve<uint64_t>(base, o_substart);
-  g.sub_hdr = carve<uint64_t>(base, o_subhdr);
-  g.is_sub = carve<uint32_t>(base, o_issub);
-  g.held_start = carve<uint64_t>(base, o_held);
   g.nfind = (uint32_t)nfind;
-  g.find_seg = carve<uint32_t>(base, o_fseg);
-  g.find_batch = carve<uint32_t>(base, o_fbatch);
-  g.cand_n = carve<uint32_t>(base, o_cn);
-  g.cand_off = carve<uint32_t>(base, o_coff);
   p->sg_sym_count = nsym + 64;
   {  // (a false start a GiB or so: a second round of repairs only pays where the first is likely to leave something)
     uint64_t cut_bytes = 0;
@@ -205,24 +182,34 @@ extern "C" int zh_plan_uncompress(zh_ctx* ctx, size_t n, const uint64_t* src_off
     p->src_max_len = std::max<uint64_t>(p->src_max_len, b.src_len);
     p->dst_max_cap = std::max<uint64_t>(p->dst_max_cap, b.dst_cap);
   }
+  // Token buffers of the split decode (filled in below)
+  std::vector<uint64_t> toff(n), tcap(n);
   const size_t np = pieces.size();
+  ZhInflateArgs& a = p->ia;
   Arena ar;
-  const size_t o_bufs = ar.reserve(n * sizeof(ZhBufDesc)), o_pieces = ar.reserve(np * sizeof(ZhPieceDesc));
-  const size_t o_pcrc = ar.reserve(np * 4), o_pad = ar.reserve(np * 4), o_plen = ar.reserve(np * 4);
-  const size_t o_bp = ar.reserve(n * 4), o_fmt = ar.reserve(n * 4), o_es = ar.reserve(n * 4),
-               o_ei = ar.reserve(n * 4), o_bcrc = ar.reserve(n * 4), o_bad = ar.reserve(n * 4),
-               o_olen = ar.reserve(n * 8), o_st = ar.reserve(n * 4);
-  const size_t o_toff = ar.reserve(n * 8), o_tcap = ar.reserve(n * 8);
-  ar.reserve(256);
-  if (ctx_malloc(p->ctx, (void**)&p->arena, ar.size) != hipSuccess) {
+  ar.add(p->d_bufs, n, bufs.data());
+  ar.add(p->d_pieces, np, pieces.data());
+  ar.add(p->piece_crc, np);
+  ar.add(p->piece_adler, np);
+  ar.add(p->piece_len, np);
+  ar.add(a.body_pos, n);
+  ar.add(a.fmt, n);
+  ar.add(a.expect_sum, n);
+  ar.add(a.expect_isize, n);
+  ar.add(p->buf_crc, n);
+  ar.add(p->buf_adler, n);
+  ar.add(p->out_len, n);
+  ar.add(p->status, n);
+  ar.add(p->tok_off, n, toff.data());
+  ar.add(p->tok_cap, n, tcap.data());
+  ar.pad(256);
+  if (ar.alloc(ctx, p->arena) != hipSuccess) {
     ctx->last_error = "hipMalloc(plan arena)";
     delete p;
     return ZH_ERR_NOMEM;
   }
-  uint8_t* base = p->arena;
-  // Token buffers of the split decode: a token makes at least one output byte and takes at least
-  // one input bit; a stored block takes five input bytes and two more records than a token.
-  std::vector<uint64_t> toff(n), tcap(n);
+  // a token makes at least one output byte and takes at least one input bit; a stored block takes five input bytes
+  // and two more records than a token.
   uint64_t twords = 0;
   for (size_t i = 0; i < n; i++) {
     const uint64_t bits = bufs[i].src_len > (~0ull >> 3) ? ~0ull : bufs[i].src_len * 8;
@@ -259,40 +246,22 @@ extern "C" int zh_plan_uncompress(zh_ctx* ctx, size_t n, const uint64_t* src_off
       fprintf(stderr, "zippy_hip: token pool for %zu groups of streams (%zu streams)\n", p->tok_groups.size(), n);
   }
   p->tok_words = twords + 32768;  // (... and stages them up to 8192 at a time, two stagings ahead)
-  hipError_t up = hipMemcpyAsync(base + o_toff, toff.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (up == hipSuccess) up = hipMemcpyAsync(base + o_tcap, tcap.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (up == hipSuccess)
-    up = hipMemcpyAsync(base + o_bufs, bufs.data(), n * sizeof(ZhBufDesc), hipMemcpyHostToDevice, ctx->stream);
-  if (up == hipSuccess)
-    up = hipMemcpyAsync(base + o_pieces, pieces.data(), np * sizeof(ZhPieceDesc), hipMemcpyHostToDevice, ctx->stream);
+  hipError_t up = ar.upload(ctx->stream);
   if (up == hipSuccess) up = hipStreamSynchronize(ctx->stream);
   if (up != hipSuccess) {
     ctx->last_error = std::string("plan upload: ") + hipGetErrorString(up);
     zh_plan_destroy(p);
     return ZH_ERR_DEVICE;
   }
-  p->d_bufs = carve<ZhBufDesc>(base, o_bufs);
-  p->d_pieces = carve<ZhPieceDesc>(base, o_pieces);
-  p->tok_off = carve<uint64_t>(base, o_toff);
-  p->tok_cap = carve<uint64_t>(base, o_tcap);
+  ar.bind();
   p->npieces = (uint32_t)np;
-  p->piece_crc = carve<uint32_t>(base, o_pcrc);
-  p->piece_adler = carve<uint32_t>(base, o_pad);
-  p->piece_len = carve<uint32_t>(base, o_plen);
-  p->buf_crc = carve<uint32_t>(base, o_bcrc);
-  p->buf_adler = carve<uint32_t>(base, o_bad);
-  ZhInflateArgs& a = p->ia;
   a.bufs = p->d_bufs;
   a.src_len_dev = nullptr;
   a.nbufs = (uint32_t)n;
   a.data_format = data_format;
   a.count_only = 0;
-  a.body_pos = carve<uint32_t>(base, o_bp);
-  a.fmt = carve<uint32_t>(base, o_fmt);
-  a.expect_sum = carve<uint32_t>(base, o_es);
-  a.expect_isize = carve<uint32_t>(base, o_ei);
-  a.out_len = p->out_len = carve<uint64_t>(base, o_olen);
-  a.status = p->status = carve<int32_t>(base, o_st);
+  a.out_len = p->out_len;
+  a.status = p->status;
   a.start_bit = nullptr;
   a.single_block = 0;
   a.skip = nullptr;
@@ -320,32 +289,29 @@ extern "C" int zh_plan_uncompress_indexed(zh_ctx* ctx, uint64_t src_off, uint64_
     segs[k] = block_decoder_desc(src_off, src_len, dst_off + index[k].out_off, index[k + 1].out_off - index[k].out_off);
     start[k] = index[k].bit_off;
   }
+  ZhInflateArgs& g = p->seg;
+  g = p->ia;
   Arena ar;
-  const size_t o_bufs = ar.reserve(nseg * sizeof(ZhBufDesc)), o_start = ar.reserve(nseg * 8),
-               o_olen = ar.reserve(nseg * 8), o_st = ar.reserve(nseg * 4);
-  ar.reserve(256);
-  if (ctx_malloc(p->ctx, (void**)&p->seg_arena, ar.size) != hipSuccess) {
+  ar.add(g.bufs, nseg, segs.data());
+  ar.add(g.start_bit, nseg, start.data());
+  ar.add(g.out_len, nseg);
+  ar.add(g.status, nseg);
+  ar.pad(256);
+  if (ar.alloc(ctx, p->seg_arena) != hipSuccess) {
     zh_plan_destroy(p);
     return ZH_ERR_NOMEM;
   }
-  uint8_t* base = p->seg_arena;
-  hipError_t up = hipMemcpyAsync(base + o_bufs, segs.data(), nseg * sizeof(ZhBufDesc), hipMemcpyHostToDevice, ctx->stream);
-  if (up == hipSuccess) up = hipMemcpyAsync(base + o_start, start.data(), nseg * 8, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t up = ar.upload(ctx->stream);
   if (up == hipSuccess) up = hipStreamSynchronize(ctx->stream);
   if (up != hipSuccess) {
     ctx->last_error = std::string("plan upload: ") + hipGetErrorString(up);
     zh_plan_destroy(p);
     return ZH_ERR_DEVICE;
   }
-  ZhInflateArgs& g = p->seg;
-  g = p->ia;
-  g.bufs = carve<ZhBufDesc>(base, o_bufs);
+  ar.bind();
   g.src_len_dev = nullptr;
   g.nbufs = (uint32_t)nseg;
-  g.start_bit = carve<uint64_t>(base, o_start);
   g.single_block = 1;
-  g.out_len = carve<uint64_t>(base, o_olen);
-  g.status = carve<int32_t>(base, o_st);
   p->indexed = true;
   *out = p;
   return ZH_OK;

@@ -232,56 +232,43 @@ int ranges_build(zh_ctx* ctx, const zh_block_entry* index, const size_t* first, 
   p->ctx = ctx;
   p->is_compress = false;
   p->n = n_ranges;
-  p->rg = new ZhRangesPlan;
+  p->rg.reset(new ZhRangesPlan);
   ZhRangesPlan& R = *p->rg;
   R.n_in_place = (uint32_t)nip;
   R.n_scratch = (uint32_t)nsc;
   R.groups = std::move(groups);
+  ZhRangesArgs& a = R.a;
   Arena ar;
-  const size_t o_bufs = ar.reserve(nb * sizeof(ZhBufDesc)), o_bit = ar.reserve(nb * 8), o_blen = ar.reserve(nb * 8),
-               o_bst = ar.reserve(nb * 4), o_first = ar.reserve((n_ranges + 1) * 4), o_order = ar.reserve(nb * 4),
-               o_fixed = ar.reserve(n_ranges * 4), o_clen = ar.reserve(n_ranges * 8),
-               o_clips = ar.reserve(nc * sizeof(ZhClipDesc)), o_olen = ar.reserve(n_ranges * 8),
-               o_st = ar.reserve(n_ranges * 4);
-  ar.reserve(256);
-  if (ctx_malloc(ctx, (void**)&R.arena, ar.size) != hipSuccess ||
-      (gmax && ctx_malloc(ctx, (void**)&R.scratch, gmax + 256) != hipSuccess)) {
+  ar.add(a.bufs, nb, ip.data());
+  ar.add(a.start_bit, nb, ip_bit.data());
+  ar.add(a.blk_len, nb);
+  ar.add(a.blk_status, nb);
+  ar.add(a.first_block, n_ranges + 1, first_block.data());
+  ar.add(a.order, nb, order.data());
+  ar.add(a.fixed_status, n_ranges, fixed.data());
+  ar.add(a.clip_len, n_ranges, clip_len.data());
+  ar.add(a.clips, nc, clips.data());
+  ar.add(p->out_len, n_ranges);
+  ar.add(p->status, n_ranges);
+  ar.pad(256);
+  if (ar.alloc(ctx, R.arena) != hipSuccess || (gmax && dev_alloc(ctx, R.scratch, gmax + 256) != hipSuccess)) {
     (void)hipGetLastError();
     ctx->last_error = "hipMalloc(ranges plan)";
     zh_plan_destroy(p);
     return ZH_ERR_NOMEM;
   }
-  uint8_t* base = R.arena;
   hipStream_t s = ctx->stream;
-  hipError_t up = hipMemsetAsync(base, 0, ar.size, s);
-  auto put = [&](size_t off, const void* from, size_t bytes) {
-    if (up == hipSuccess && bytes) up = hipMemcpyAsync(base + off, from, bytes, hipMemcpyHostToDevice, s);
-  };
-  put(o_bufs, ip.data(), nb * sizeof(ZhBufDesc));
-  put(o_bit, ip_bit.data(), nb * 8);
-  put(o_first, first_block.data(), (n_ranges + 1) * 4);
-  put(o_order, order.data(), nb * 4);
-  put(o_fixed, fixed.data(), n_ranges * 4);
-  put(o_clen, clip_len.data(), n_ranges * 8);
-  put(o_clips, clips.data(), nc * sizeof(ZhClipDesc));
+  hipError_t up = hipMemsetAsync(ar.base, 0, ar.size, s);
+  if (up == hipSuccess) up = ar.upload(s);
   if (up == hipSuccess) up = hipStreamSynchronize(s);
   if (up != hipSuccess) {
     ctx->last_error = std::string("plan upload: ") + hipGetErrorString(up);
     zh_plan_destroy(p);
     return ZH_ERR_DEVICE;
   }
-  ZhRangesArgs& a = R.a;
-  a.bufs = carve<ZhBufDesc>(base, o_bufs);
-  a.start_bit = carve<uint64_t>(base, o_bit);
-  a.blk_len = carve<uint64_t>(base, o_blen);
-  a.blk_status = carve<int32_t>(base, o_bst);
-  a.first_block = carve<uint32_t>(base, o_first);
-  a.order = carve<uint32_t>(base, o_order);
-  a.fixed_status = carve<int32_t>(base, o_fixed);
-  a.clip_len = carve<uint64_t>(base, o_clen);
-  a.clips = carve<ZhClipDesc>(base, o_clips);
-  a.out_len = p->out_len = carve<uint64_t>(base, o_olen);
-  a.status = p->status = carve<int32_t>(base, o_st);
+  ar.bind();
+  a.out_len = p->out_len;
+  a.status = p->status;
   a.nranges = (uint32_t)n_ranges;
   *out = p;
   return ZH_OK;

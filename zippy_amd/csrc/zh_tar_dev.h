@@ -221,19 +221,21 @@ struct TarResults {
 template <class Rec, class Parse>
 inline int tar_results(zh_ctx* ctx, TarStage& s, const Walk& w, const ZhTarImg* dimgs, size_t n_walk, uint32_t n_hdr,
                        Parse launch_parse, TarResults<Rec>& r) {
+  Rec* d_recs;
+  uint32_t *d_pool, *d_ranges;
+  int32_t *d_tstat, *d_hstat;
   Arena out;
-  const size_t o_recs = out.reserve((size_t)n_hdr * sizeof(Rec)), o_pool = out.reserve((size_t)n_hdr * 256),
-               o_ranges = out.reserve(n_walk * 8), o_tstat = out.reserve(n_walk * 4);
-  const size_t out_bytes = out.size;
-  const size_t o_hstat = out.reserve((size_t)n_hdr * 4);
+  out.add(d_recs, n_hdr);
+  out.add(d_pool, (size_t)n_hdr * 64);
+  out.add(d_ranges, n_walk * 2);
+  out.add(d_tstat, n_walk);
+  const size_t out_bytes = out.size;  // (what comes back: the arrays so far)
+  out.add(d_hstat, n_hdr);
   DevBuf d_out;
-  if (dev_alloc(ctx, d_out, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  // (plain pointers for the launches: a launch must not take the DevBuf itself along)
-  uint32_t* const d_ranges = carve<uint32_t>(d_out.p, o_ranges);
-  int32_t* const d_tstat = carve<int32_t>(d_out.p, o_tstat);
-  int32_t* const d_hstat = carve<int32_t>(d_out.p, o_hstat);
+  if (out.alloc(ctx, d_out, 256) != hipSuccess) return ZH_ERR_NOMEM;
+  out.bind();
   const uint32_t* const ord = w.ord;
-  if (n_hdr) launch_parse(carve<Rec>(d_out.p, o_recs), carve<uint32_t>(d_out.p, o_pool), d_hstat);
+  if (n_hdr) launch_parse(d_recs, d_pool, d_hstat);
   hipLaunchKernelGGL(zh_tar_reduce_kernel, dim3((uint32_t)n_walk), dim3(256), 0, ctx->stream, dimgs, ord,
                      (const int32_t*)d_hstat, d_ranges, d_tstat);
   ZH_HIP(ctx, hipGetLastError());
@@ -246,9 +248,8 @@ inline int tar_results(zh_ctx* ctx, TarStage& s, const Walk& w, const ZhTarImg* 
   }
   s.own.p.push_back(h_out);
   if (dst_st) return dst_st;
-  const uint8_t* const ho = (const uint8_t*)h_out;
-  r = TarResults<Rec>{reinterpret_cast<const Rec*>(ho + o_recs), ho + o_pool,
-                      reinterpret_cast<const uint32_t*>(ho + o_ranges), reinterpret_cast<const int32_t*>(ho + o_tstat)};
+  r = TarResults<Rec>{out.host(h_out, d_recs), reinterpret_cast<const uint8_t*>(out.host(h_out, d_pool)),
+                      out.host(h_out, d_ranges), out.host(h_out, d_tstat)};
   return ZH_OK;
 }
 

@@ -103,15 +103,15 @@ inline int walk_alloc(zh_ctx* ctx, Walk& w, uint32_t n_nodes, size_t extra = 0) 
   const size_t N = w.N = n_nodes;
   w.n_sums = (n_nodes + kScanItems - 1) / kScanItems;
   Arena ar;
-  const size_t o_j0 = ar.reserve(N * 4), o_j1 = ar.reserve(N * 4), o_mark = ar.reserve(N * 4), o_ord = ar.reserve(N * 4),
-               o_sums = ar.reserve(((size_t)w.n_sums + 1) * 4), o_extra = ar.reserve(extra);
-  if (dev_alloc(ctx, w.scr, ar.size) != hipSuccess) return ZH_ERR_NOMEM;
-  w.list = w.j0 = carve<uint32_t>(w.scr.p, o_j0);
-  w.j1 = carve<uint32_t>(w.scr.p, o_j1);
-  w.mark = carve<uint32_t>(w.scr.p, o_mark);
-  w.ord = carve<uint32_t>(w.scr.p, o_ord);
-  w.sums = carve<uint32_t>(w.scr.p, o_sums);
-  w.extra = w.scr.p + o_extra;
+  ar.add(w.j0, N);
+  ar.add(w.j1, N);
+  ar.add(w.mark, N);
+  ar.add(w.ord, N);
+  ar.add(w.sums, (size_t)w.n_sums + 1);
+  ar.add(w.extra, extra);
+  if (ar.alloc(ctx, w.scr) != hipSuccess) return ZH_ERR_NOMEM;
+  ar.bind();
+  w.list = w.j0;
   return ZH_OK;
 }
 // `rounds` rounds of doubling on stream s: every node up to 2^rounds - 1 steps from a start is marked.

@@ -189,27 +189,40 @@ inline int zip_extract(zh_ctx* ctx, Trace& tr, const char* what, const std::vect
   if (n_task >= 0xffffffffull || n_piece >= 0xffffffffull) return ZH_ERR_ARGUMENT;
   DevBuf d_fin;
   if (dev_alloc(ctx, d_out, out_total + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  const ZhZipFin* d_fins;
+  const ZhZipFinTask* d_tasks;
+  const ZhBufDesc* d_sbufs;
+  const ZhPieceDesc* d_pieces;
+  const uint32_t* d_er;
+  uint32_t *d_pcrc, *d_pad, *d_plen, *d_scrc, *d_sad, *d_ebad, *d_eany;
+  int32_t* d_est;
+  uint64_t* d_elen;
   Arena fa;
-  const size_t o_fins = fa.reserve(n_slot * sizeof(ZhZipFin)), o_tasks = fa.reserve(n_task * sizeof(ZhZipFinTask)),
-               o_sbufs = fa.reserve(n_sto * sizeof(ZhBufDesc)), o_pieces = fa.reserve(n_piece * sizeof(ZhPieceDesc)),
-               o_er = fa.reserve(n_img * 8);
-  const size_t fa_in = fa.size;
-  const size_t o_pcrc = fa.reserve(n_piece * 4), o_pad = fa.reserve(n_piece * 4), o_plen = fa.reserve(n_piece * 4),
-               o_scrc = fa.reserve(n_sto * 4), o_sad = fa.reserve(n_sto * 4), o_est = fa.reserve(n_slot * 4),
-               o_elen = fa.reserve(elen ? n_slot * 8 : 0), o_ebad = fa.reserve(n_img * 4), o_eany = fa.reserve(n_img * 4);
-  if (dev_alloc(ctx, d_fin, fa.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  fa.add(d_fins, n_slot, fins.data());
+  fa.add(d_tasks, n_task, tasks.data());
+  fa.add(d_sbufs, n_sto, sbufs.data());
+  fa.add(d_pieces, n_piece, pieces.data());
+  fa.add(d_er, n_img * 2, eranges.data());
+  const size_t fa_in = fa.size;  // (what is uploaded: the arrays so far)
+  fa.add(d_pcrc, n_piece);
+  fa.add(d_pad, n_piece);
+  fa.add(d_plen, n_piece);
+  fa.add(d_scrc, n_sto);
+  fa.add(d_sad, n_sto);
+  fa.add(d_est, n_slot);
+  fa.add(d_elen, elen ? n_slot : 0);
+  fa.add(d_ebad, n_img);
+  fa.add(d_eany, n_img);
+  if (fa.alloc(ctx, d_fin, 256) != hipSuccess) return ZH_ERR_NOMEM;
+  fa.bind();
+  if (!elen) d_elen = nullptr;
   // (plain pointers from here on: a launch must not take the guard of a buffer or of the plan along)
-  uint8_t* const fin_p = d_fin.p;
   uint8_t* const outp = d_out.p;
   {
     std::vector<uint8_t> h(fa_in);
-    memcpy(h.data() + o_fins, fins.data(), n_slot * sizeof(ZhZipFin));
-    memcpy(h.data() + o_tasks, tasks.data(), n_task * sizeof(ZhZipFinTask));
-    if (n_sto) memcpy(h.data() + o_sbufs, sbufs.data(), n_sto * sizeof(ZhBufDesc));
-    if (n_piece) memcpy(h.data() + o_pieces, pieces.data(), n_piece * sizeof(ZhPieceDesc));
-    memcpy(h.data() + o_er, eranges.data(), n_img * 8);
+    fa.gather(h.data());
     const void* src = h.data();
-    if ((st = zhh_upload_slices(ctx, &src, {0}, {(uint64_t)fa_in}, fa_in, fin_p))) return st;
+    if ((st = zhh_upload_slices(ctx, &src, {0}, {(uint64_t)fa_in}, fa_in, fa.base))) return st;
   }
   const std::string mark = std::string(what) + ": ";
   PlanGuard pg;
@@ -228,34 +241,25 @@ inline int zip_extract(zh_ctx* ctx, Trace& tr, const char* what, const std::vect
     }
   }
   tr.mark(ctx, (mark + "decode").c_str());
-  zh_launch_checksum_pieces(s, ctx->cktabs, in, carve<ZhPieceDesc>(fin_p, o_pieces), (uint32_t)n_piece, nullptr, 1, 0,
-                            carve<uint32_t>(fin_p, o_pcrc), carve<uint32_t>(fin_p, o_pad),
-                            carve<uint32_t>(fin_p, o_plen));
-  zh_launch_checksum_combine(s, ctx->cktabs, carve<ZhBufDesc>(fin_p, o_sbufs), (uint32_t)n_sto,
-                             carve<uint32_t>(fin_p, o_pcrc), carve<uint32_t>(fin_p, o_pad),
-                             carve<uint32_t>(fin_p, o_plen), 1, 0, carve<uint32_t>(fin_p, o_scrc),
-                             carve<uint32_t>(fin_p, o_sad));
+  zh_launch_checksum_pieces(s, ctx->cktabs, in, d_pieces, (uint32_t)n_piece, nullptr, 1, 0, d_pcrc, d_pad, d_plen);
+  zh_launch_checksum_combine(s, ctx->cktabs, d_sbufs, (uint32_t)n_sto, d_pcrc, d_pad, d_plen, 1, 0, d_scrc, d_sad);
   const int32_t* const plan_st = n_def ? zh_plan_device_statuses(pg.p) : nullptr;
   const uint64_t* const plan_len = n_def ? zh_plan_device_lens(pg.p) : nullptr;
   const uint32_t* const plan_crc = n_def ? pg.p->buf_crc : nullptr;
-  uint64_t* const d_elen = elen ? carve<uint64_t>(fin_p, o_elen) : nullptr;
-  hipLaunchKernelGGL(zh_zip_finish_kernel, dim3(((uint32_t)n_task + 3) / 4), wg, 0, s, in, outp,
-                     (const ZhZipFin*)carve<ZhZipFin>(fin_p, o_fins),
-                     (const ZhZipFinTask*)carve<ZhZipFinTask>(fin_p, o_tasks), (uint32_t)n_task, plan_st, plan_len,
-                     plan_crc, (const uint32_t*)carve<uint32_t>(fin_p, o_scrc), check_len ? 1u : 0u,
-                     carve<int32_t>(fin_p, o_est), d_elen);
-  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3((uint32_t)n_img), wg, 0, s,
-                     (const uint32_t*)carve<uint32_t>(fin_p, o_er), (const int32_t*)carve<int32_t>(fin_p, o_est),
-                     (const uint8_t*)nullptr, carve<uint32_t>(fin_p, o_ebad), carve<uint32_t>(fin_p, o_eany));
+  hipLaunchKernelGGL(zh_zip_finish_kernel, dim3(((uint32_t)n_task + 3) / 4), wg, 0, s, in, outp, d_fins, d_tasks,
+                     (uint32_t)n_task, plan_st, plan_len, plan_crc, (const uint32_t*)d_scrc, check_len ? 1u : 0u, d_est,
+                     d_elen);
+  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3((uint32_t)n_img), wg, 0, s, d_er, (const int32_t*)d_est,
+                     (const uint8_t*)nullptr, d_ebad, d_eany);
   ZH_HIP(ctx, hipGetLastError());
   est.assign(n_slot, ZH_OK);
   ebad.assign(n_img, kNone);
-  ZH_HIP(ctx, hipMemcpyAsync(est.data(), fin_p + o_est, n_slot * 4, hipMemcpyDeviceToHost, s));
+  ZH_HIP(ctx, hipMemcpyAsync(est.data(), d_est, n_slot * 4, hipMemcpyDeviceToHost, s));
   if (elen) {
     elen->assign(n_slot, 0);
-    ZH_HIP(ctx, hipMemcpyAsync(elen->data(), fin_p + o_elen, n_slot * 8, hipMemcpyDeviceToHost, s));
+    ZH_HIP(ctx, hipMemcpyAsync(elen->data(), d_elen, n_slot * 8, hipMemcpyDeviceToHost, s));
   }
-  ZH_HIP(ctx, hipMemcpyAsync(ebad.data(), fin_p + o_ebad, n_img * 4, hipMemcpyDeviceToHost, s));
+  ZH_HIP(ctx, hipMemcpyAsync(ebad.data(), d_ebad, n_img * 4, hipMemcpyDeviceToHost, s));
   ZH_HIP(ctx, hipStreamSynchronize(s));
   tr.mark(ctx, (mark + "finish").c_str());
   return ZH_OK;

@@ -337,23 +337,28 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
   tr.mark(ctx, "zip open: reach + scan");
 
   // ---- 4. the records ----
+  ZhZipRec* d_recs;
+  uint32_t *d_ranges, *d_bad, *d_unsafe;
+  int32_t* d_rstat;
+  uint8_t* d_rflag;
   Arena out;
-  const size_t o_recs = out.reserve((size_t)n_rec * sizeof(ZhZipRec)), o_ranges = out.reserve(n_walk * 8),
-               o_bad = out.reserve(n_walk * 4), o_unsafe = out.reserve(n_walk * 4);
-  const size_t out_bytes = out.size;
-  const size_t o_rstat = out.reserve((size_t)n_rec * 4), o_rflag = out.reserve((size_t)n_rec);
+  out.add(d_recs, n_rec);
+  out.add(d_ranges, n_walk * 2);
+  out.add(d_bad, n_walk);
+  out.add(d_unsafe, n_walk);
+  const size_t out_bytes = out.size;  // (what comes back: the arrays so far)
+  out.add(d_rstat, n_rec);
+  out.add(d_rflag, n_rec);
   DevBuf d_rec;
-  if (dev_alloc(ctx, d_rec, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
+  if (out.alloc(ctx, d_rec, 256) != hipSuccess) return ZH_ERR_NOMEM;
+  out.bind();
   if (n_rec)
     hipLaunchKernelGGL(zh_zip_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, dimgs, (uint32_t)n_walk,
-                       ord, list, n_rec, carve<ZhZipRec>(d_rec.p, o_recs),
-                       carve<int32_t>(d_rec.p, o_rstat), carve<uint8_t>(d_rec.p, o_rflag));
+                       ord, list, n_rec, d_recs, d_rstat, d_rflag);
   hipLaunchKernelGGL(zh_zip_ranges_kernel, dim3(((uint32_t)n_walk + 255) / 256), wg, 0, s, dimgs, (uint32_t)n_walk,
-                     ord, carve<uint32_t>(d_rec.p, o_ranges));
-  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s,
-                     (const uint32_t*)carve<uint32_t>(d_rec.p, o_ranges), (const int32_t*)carve<int32_t>(d_rec.p, o_rstat),
-                     (const uint8_t*)carve<uint8_t>(d_rec.p, o_rflag), carve<uint32_t>(d_rec.p, o_bad),
-                     carve<uint32_t>(d_rec.p, o_unsafe));
+                     ord, d_ranges);
+  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3((uint32_t)n_walk), wg, 0, s, (const uint32_t*)d_ranges,
+                     (const int32_t*)d_rstat, (const uint8_t*)d_rflag, d_bad, d_unsafe);
   ZH_HIP(ctx, hipGetLastError());
   HostBufs own;
   void* h_rec = nullptr;
@@ -364,11 +369,10 @@ extern "C" int zh_zip_open_all_batch(zh_ctx* ctx, const void* const* images, con
     own.p.push_back(h_rec);
     if (st || dst_st) return st ? st : dst_st;
   }
-  const uint8_t* const hr = (const uint8_t*)h_rec;
-  const ZhZipRec* const recs = reinterpret_cast<const ZhZipRec*>(hr + o_recs);
-  const uint32_t* const ranges = reinterpret_cast<const uint32_t*>(hr + o_ranges);
-  const uint32_t* const first_bad = reinterpret_cast<const uint32_t*>(hr + o_bad);
-  const uint32_t* const any_unsafe = reinterpret_cast<const uint32_t*>(hr + o_unsafe);
+  const ZhZipRec* const recs = out.host(h_rec, d_recs);
+  const uint32_t* const ranges = out.host(h_rec, d_ranges);
+  const uint32_t* const first_bad = out.host(h_rec, d_bad);
+  const uint32_t* const any_unsafe = out.host(h_rec, d_unsafe);
   tr.mark(ctx, "zip open: parse + reduce");
 
   // ---- 5. the readers, from the records: string building, the duplicate check, the serial loop's precedence ----

@@ -398,15 +398,18 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   while ((1ull << rounds) < max_chain + 1) rounds++;
   // behind the walk's scratch: what the loop finds behind every hit (succ), every image's range of hits
   const uint32_t N = n_hits + n_img;
+  int32_t* succ;
+  uint32_t* hit_ranges;
   Arena ex;
-  const size_t o_succ = ex.reserve((size_t)n_hits * 4), o_hr = ex.reserve((size_t)n_img * 8);
+  ex.add(succ, n_hits);
+  ex.add(hit_ranges, (size_t)n_img * 2);
   Walk w;
   if ((st = walk_alloc(ctx, w, N, ex.size + 256))) return st;
+  ex.base = w.extra;
+  ex.bind();
   // (plain pointers for the launches: a launch must not take a DevBuf, or the Walk that holds one, along)
   uint32_t *const j0 = w.j0, *const mark = w.mark;
   const uint32_t *const ord = w.ord, *const list = w.list;
-  int32_t* const succ = carve<int32_t>(w.extra, o_succ);
-  uint32_t* const hit_ranges = carve<uint32_t>(w.extra, o_hr);
   // the per-image outputs live in the block that is downloaded with the records (below); the start statuses are
   // written now, so they get a place of their own here
   DevBuf d_start;
@@ -424,25 +427,28 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   tr.mark(ctx, "zip read: reach + scan");
 
   // ---- 5. the records ----
+  ZhZrRec* d_recs;
+  uint32_t *d_ranges, *d_bad, *d_any;
+  int32_t *d_start_st, *d_rstat;
   Arena out;
-  const size_t o_recs = out.reserve((size_t)n_rec * sizeof(ZhZrRec)), o_ranges = out.reserve((size_t)n_img * 8),
-               o_bad = out.reserve((size_t)n_img * 4), o_start = out.reserve((size_t)n_img * 4);
-  const size_t out_bytes = out.size;
-  const size_t o_rstat = out.reserve((size_t)n_rec * 4), o_any = out.reserve((size_t)n_img * 4);
+  out.add(d_recs, n_rec);
+  out.add(d_ranges, (size_t)n_img * 2);
+  out.add(d_bad, n_img);
+  out.add(d_start_st, n_img);
+  const size_t out_bytes = out.size;  // (what comes back: the arrays so far)
+  out.add(d_rstat, n_rec);
+  out.add(d_any, n_img);
   DevBuf d_rec;
-  if (dev_alloc(ctx, d_rec, out.size + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  uint8_t* const rec_p = d_rec.p;
+  if (out.alloc(ctx, d_rec, 256) != hipSuccess) return ZH_ERR_NOMEM;
+  out.bind();
   if (n_rec)
     hipLaunchKernelGGL(zh_zipr_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, in, dimgs, n_img,
-                       (const uint64_t*)hits, list, (const int32_t*)succ, n_rec,
-                       carve<ZhZrRec>(rec_p, o_recs), carve<int32_t>(rec_p, o_rstat));
-  hipLaunchKernelGGL(zh_zipr_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord,
-                     carve<uint32_t>(rec_p, o_ranges));
-  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)carve<uint32_t>(rec_p, o_ranges),
-                     (const int32_t*)carve<int32_t>(rec_p, o_rstat), (const uint8_t*)nullptr,
-                     carve<uint32_t>(rec_p, o_bad), carve<uint32_t>(rec_p, o_any));
+                       (const uint64_t*)hits, list, (const int32_t*)succ, n_rec, d_recs, d_rstat);
+  hipLaunchKernelGGL(zh_zipr_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord, d_ranges);
+  hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)d_ranges, (const int32_t*)d_rstat,
+                     (const uint8_t*)nullptr, d_bad, d_any);
   ZH_HIP(ctx, hipGetLastError());
-  ZH_HIP(ctx, hipMemcpyAsync(rec_p + o_start, start, (size_t)n_img * 4, hipMemcpyDeviceToDevice, s));
+  ZH_HIP(ctx, hipMemcpyAsync(d_start_st, start, (size_t)n_img * 4, hipMemcpyDeviceToDevice, s));
   HostBufs own;
   void* h_rec = nullptr;
   {
@@ -452,11 +458,10 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
     own.p.push_back(h_rec);
     if (st || dst_st) return st ? st : dst_st;
   }
-  const uint8_t* const hr = (const uint8_t*)h_rec;
-  const ZhZrRec* const recs = reinterpret_cast<const ZhZrRec*>(hr + o_recs);
-  const uint32_t* const ranges = reinterpret_cast<const uint32_t*>(hr + o_ranges);
-  const uint32_t* const first_bad = reinterpret_cast<const uint32_t*>(hr + o_bad);
-  const int32_t* const start_st = reinterpret_cast<const int32_t*>(hr + o_start);
+  const ZhZrRec* const recs = out.host(h_rec, d_recs);
+  const uint32_t* const ranges = out.host(h_rec, d_ranges);
+  const uint32_t* const first_bad = out.host(h_rec, d_bad);
+  const int32_t* const start_st = out.host(h_rec, d_start_st);
   tr.mark(ctx, "zip read: parse + reduce");
 
   // ---- 6. the tables, from the records in walk order; the layout of the output ----

@@ -322,12 +322,12 @@ extern "C" int zh_zip_write_batch(zh_ctx* ctx, const zh_zip_new_entry* entries, 
   tr.mark(ctx, "zip: layout");
 
   uint8_t* const img = d_img.p;  // (plain pointers into the launch: a DevBuf is not to be copied)
-  const uint8_t* const mp = d_meta.p;
+  const uint8_t *const mp = d_meta.p, *const slots = d_slots.p;
   constexpr uint64_t kGridTasks = 4ull << 22;  // tasks a launch: 2^22 workgroups
   for (uint64_t t0 = 0; t0 < tasks.size(); t0 += kGridTasks) {
     const uint64_t nt = std::min<uint64_t>(kGridTasks, tasks.size() - t0);
     hipLaunchKernelGGL(zh_zip_write_kernel, dim3((uint32_t)((nt + 3) / 4)), dim3(256), 0, ctx->stream, img,
-                       static_cast<const uint8_t*>(d_slots.p), reinterpret_cast<const ZhZipEntryDesc*>(mp + moff[0]),
+                       slots, reinterpret_cast<const ZhZipEntryDesc*>(mp + moff[0]),
                        reinterpret_cast<const ZhZipTask*>(mp + moff[1]) + t0, nt,
                        reinterpret_cast<const ZhZipEocdDesc*>(mp + moff[2]), mp + moff[3]);
     ZH_HIP(ctx, hipGetLastError());
@@ -629,12 +629,12 @@ extern "C" int zh_zip_create_batch(zh_ctx* ctx, const zh_zip_new_entry* entries,
   tr.mark(ctx, "zip64: layout");
 
   uint8_t* const img = d_img.p;
-  const uint8_t* const mp = d_meta.p;
+  const uint8_t *const mp = d_meta.p, *const slots = d_slots.p;
   constexpr uint64_t kGridTasks = 4ull << 22;  // tasks a launch: 2^22 workgroups
   for (uint64_t t0 = 0; t0 < tasks.size(); t0 += kGridTasks) {
     const uint64_t nt = std::min<uint64_t>(kGridTasks, tasks.size() - t0);
     hipLaunchKernelGGL(zh_zip_create_kernel, dim3((uint32_t)((nt + 3) / 4)), dim3(256), 0, ctx->stream, img,
-                       static_cast<const uint8_t*>(d_slots.p), reinterpret_cast<const ZhZip64EntryDesc*>(mp + moff[0]),
+                       slots, reinterpret_cast<const ZhZip64EntryDesc*>(mp + moff[0]),
                        reinterpret_cast<const ZhZip64Task*>(mp + moff[1]) + t0, nt,
                        reinterpret_cast<const ZhZip64EndDesc*>(mp + moff[2]), mp + moff[3]);
     ZH_HIP(ctx, hipGetLastError());

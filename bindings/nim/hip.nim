@@ -608,3 +608,66 @@ proc hipReadRanges*(streams: openArray[string], indexes: openArray[seq[ZhBlockEn
       result.add take(dsts[i], dlens[i], 0)
   if firstBad != 0:
     raise newException(ZippyError, $zh_strerror(firstBad))
+
+# ---- BGZF: the blocked gzip of bgzip / htslib (no counterpart in the reference) ----
+type
+  ZhBgzfEntry* {.bycopy.} = object
+    coff*: uint64                       # the member's first byte in the file; the closing entry: the file's end
+    uoff*: uint64                       # its first byte in the uncompressed data; the closing entry: the total
+
+proc zh_bgzf_write_batch(ctx: ZhCtx, srcs: ptr pointer, lens: ptr csize_t, n: csize_t, level: cint,
+                         blockBytes: csize_t, dsts: ptr pointer, dstLens: ptr csize_t,
+                         statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_bgzf_read_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, n: csize_t, dsts: ptr pointer,
+                        dstLens: ptr csize_t, statuses: ptr int32,
+                        hasEof: ptr uint8): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_bgzf_index_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, n: csize_t,
+                         index: ptr ptr ZhBgzfEntry, first: ptr csize_t, statuses: ptr int32,
+                         hasEof: ptr uint8): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_bgzf_read_ranges(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, nImages: csize_t,
+                         index: ptr ZhBgzfEntry, first: ptr csize_t, nRanges: csize_t,
+                         rangeImage, rangeOff, rangeLen: ptr uint64, dsts: ptr pointer, dstLens: ptr csize_t,
+                         statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc compressBgzf*(src: string, level = DefaultCompression, blockBytes = 0): string {.raises: [ZippyError].} =
+  ## src as a BGZF file: gzip members of blockBytes (0: 65280) uncompressed bytes each and the EOF marker;
+  ## uncompress() of any gunzip reads it, and its index is in the file (hipBgzfIndex)
+  var p = if src.len > 0: src[0].unsafeAddr.pointer else: nil
+  var len = src.len.csize_t
+  var dst: pointer; var dstLen: csize_t; var st: int32
+  let rc = zh_bgzf_write_batch(engine(), p.addr, len.addr, 1, level.cint, blockBytes.csize_t, dst.addr, dstLen.addr,
+                               st.addr)
+  take(dst, dstLen, if rc != 0: rc else: st.cint)
+
+proc uncompressBgzf*(image: string): string {.raises: [ZippyError].} =
+  ## the uncompressed data of a BGZF file, every member verified by its CRC-32 and ISIZE
+  var p = if image.len > 0: image[0].unsafeAddr.pointer else: nil
+  var len = image.len.csize_t
+  var dst: pointer; var dstLen: csize_t; var st: int32
+  let rc = zh_bgzf_read_batch(engine(), p.addr, len.addr, 1, dst.addr, dstLen.addr, st.addr, nil)
+  take(dst, dstLen, if rc != 0: rc else: st.cint)
+
+proc hipBgzfIndex*(image: string): seq[ZhBgzfEntry] {.raises: [ZippyError].} =
+  ## the members of a BGZF file from its headers and trailers alone, closed by (the file's end, the total)
+  var p = if image.len > 0: image[0].unsafeAddr.pointer else: nil
+  var len = image.len.csize_t
+  var idx: ptr ZhBgzfEntry; var first: array[2, csize_t]; var st: int32; var eof: uint8
+  let rc = zh_bgzf_index_batch(engine(), p.addr, len.addr, 1, idx.addr, first[0].addr, st.addr, eof.addr)
+  if rc == 0 and st == 0:
+    result = newSeq[ZhBgzfEntry](first[1].int)
+    copyMem(result[0].addr, idx, first[1].int * sizeof(ZhBgzfEntry))
+  if idx != nil: zh_free(idx)
+  if rc != 0 or st != 0:
+    raise newException(ZippyError, $zh_strerror(if rc != 0: rc else: st.cint))
+
+proc hipBgzfReadRange*(image: string, index: seq[ZhBgzfEntry], off, len: uint64): string {.raises: [ZippyError].} =
+  ## bytes [off, off + len) of the uncompressed data: only the members the range touches are uploaded and decoded,
+  ## each verified by its checksum.  Reads like pread (clipped at the end, empty behind it).
+  var p = if image.len > 0: image[0].unsafeAddr.pointer else: nil
+  var ilen = image.len.csize_t
+  var first = [0.csize_t, index.len.csize_t]
+  var ri = 0'u64; var ro = off; var rl = len
+  var dst: pointer; var dstLen: csize_t; var st: int32
+  let rc = zh_bgzf_read_ranges(engine(), p.addr, ilen.addr, 1, (if index.len > 0: index[0].unsafeAddr else: nil),
+                               first[0].addr, 1, ri.addr, ro.addr, rl.addr, dst.addr, dstLen.addr, st.addr)
+  take(dst, dstLen, if rc != 0: rc else: st.cint)

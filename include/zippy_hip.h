@@ -90,7 +90,10 @@ enum {
   ZH_ERR_TAR_FORMAT = 46,          /* tarballs_v1.nim:86 */
   ZH_ERR_TAR_OPEN = 47,            /* tarballs_v1.nim:118,124 (size or mtime that parseOctInt rejects) */
   ZH_ERR_TAR_OPEN_MODE = 48,       /* tarballs_v1.nim:131 */
-  ZH_ERR_TAR_EOF = 49              /* tarballs_v1.nim:61-64 failEOF */
+  ZH_ERR_TAR_EOF = 49,             /* tarballs_v1.nim:61-64 failEOF */
+  /* BGZF (zh_bgzf_*): SAM specification, section 4.1 */
+  ZH_ERR_BGZF_HEADER = 50          /* extra field without a BC subfield, subfields that do not tile XLEN, BSIZE too
+                                      small for the member's own header + trailer, ISIZE > 65536 */
 };
 
 /* Engine context: one GPU, one HIP stream, reusable scratch. Thread-compatible
@@ -400,6 +403,73 @@ int zh_uncompress_ranges(zh_ctx *ctx, const void *const *srcs, const size_t *len
 /* Counters of the context's last ranges call / plan run: bytes that went over the link (0 for a plan run: its streams
  * are on the device), blocks decoded in place, blocks decoded via scratch. */
 int zh_debug_range_stats(zh_ctx *ctx, uint64_t *uploaded_bytes, uint64_t *blocks_in_place, uint64_t *blocks_via_scratch);
+
+/* ------------------------------------------------------------------ *
+ * BGZF, the blocked gzip of the SAM specification (section 4.1), as   *
+ * written by bgzip and htslib: a series of gzip members of at most    *
+ * 64 KiB, each with its total size in a `BC` extra subfield and its   *
+ * CRC-32 and ISIZE in its trailer, closed by an empty 28-byte member. *
+ * Any gunzip reads such a file; its index is in the file itself (a    *
+ * walk over headers and trailers, nothing decoded), and a byte range  *
+ * is verified by the checksums of the members it touches.             *
+ * zh_uncompress* still rejects FEXTRA and multi-member input as the   *
+ * reference does: these calls are the way to read and write BGZF.     *
+ * Host buffers in, library-allocated results out (zh_free); statuses  *
+ * per image or per range; the return value is ZH_OK unless the call   *
+ * as a whole could not run, and then nothing is handed out.           *
+ * ------------------------------------------------------------------ */
+#define ZH_BGZF_BLOCK 65280     /* bgzip's payload per member (0xff00) */
+#define ZH_BGZF_MAX_BLOCK 65505 /* largest payload whose stored form (5 + n) still fits a member */
+#define ZH_BGZF_MAX_CDATA 65510 /* 65536 - 18 - 8 */
+
+/* Member k starts at byte coff of the file and at byte uoff of the uncompressed data; a list is closed by one
+ * entry: coff = the byte behind the last member that holds data or the EOF marker (= where the walk ended), uoff =
+ * the total.  The virtual offset of htslib is coff << 16 | offset within the member. */
+typedef struct zh_bgzf_entry {
+  uint64_t coff, uoff;
+} zh_bgzf_entry;
+
+/* Image i = ceil(lens[i] / block_bytes) members and the EOF marker (a source of 0 bytes: the marker alone, as bgzip
+ * writes it).  block_bytes: 0 means ZH_BGZF_BLOCK, else 1 .. ZH_BGZF_MAX_BLOCK (anything else: ZH_ERR_ARGUMENT).  A
+ * bad level is ZH_ERR_INVALID_LEVEL for every image and the call, as in zh_compress_batch.  A member's CDATA is the
+ * engine's raw deflate of its piece at `level` -- the bytes zh_compress gives for ZH_DF_DEFLATE -- except where that
+ * stream is longer than ZH_BGZF_MAX_CDATA (the reference chooses stored blocks by a heuristic, never by size): such a
+ * piece is written in its level-0 form, 5 + n bytes. */
+int zh_bgzf_write_batch(zh_ctx *ctx, const void *const *srcs, const size_t *lens, size_t n, int level,
+                        size_t block_bytes, void **dsts, size_t *dst_lens, int32_t *statuses);
+/* The uncompressed data of every image.  The members are found by a walk from byte 0; the checks of the member at a
+ * position, in this order, the first failure decides: fewer than 12 bytes left ZH_ERR_INVALID_BUFFER; ID bytes
+ * ZH_ERR_GZIP_ID; CM != 8 ZH_ERR_UNSUPPORTED_METHOD; FLG & 0xe0 ZH_ERR_RESERVED_FLAGS; FLG != 4
+ * ZH_ERR_UNSUPPORTED_FLAGS; 12 + XLEN beyond the image ZH_ERR_INVALID_BUFFER; subfields that do not tile XLEN or
+ * hold no BC of two bytes ZH_ERR_BGZF_HEADER; BSIZE + 1 < 12 + XLEN + 8 ZH_ERR_BGZF_HEADER; the member beyond the
+ * image ZH_ERR_INVALID_BUFFER; ISIZE > 65536 ZH_ERR_BGZF_HEADER.  The walk ends cleanly where a member ends with the
+ * image (an image of 0 bytes: ZH_OK, 0 bytes); bytes behind an EOF marker are members like any others (cat a.gz
+ * b.gz); a missing marker is no error (has_eof[i], if given: 1 when the walk ended cleanly and its last member is
+ * byte for byte the marker).  Every member is decoded and settled: the decoder's status (more bytes than ISIZE:
+ * ZH_ERR_SIZE), then its CRC-32 against the trailer (ZH_ERR_CHECKSUM), then its length against ISIZE (ZH_ERR_SIZE).
+ * An image's status is that of its first failing member in file order, a header that fails counting at its own
+ * position; such an image gives NULL / 0 and does not disturb its neighbours. */
+int zh_bgzf_read_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n, void **dsts,
+                       size_t *dst_lens, int32_t *statuses, uint8_t *has_eof);
+/* The walk alone: *index (zh_free) holds the lists of all images back to back, image i's entries are
+ * index[first[i] .. first[i + 1]) (first: n + 1 values; an image that failed has none).  Nothing is decoded. */
+int zh_bgzf_index_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n, zh_bgzf_entry **index,
+                        size_t *first, int32_t *statuses, uint8_t *has_eof);
+/* Byte ranges of the uncompressed data, like pread and like zh_uncompress_ranges: range r reads bytes
+ * [range_off[r], + range_len[r]) of image range_image[r]; it is clipped at the total, a range at or beyond it or of
+ * length 0 gives 0 bytes and ZH_OK; range_image[r] >= n_images and NULL arrays are ZH_ERR_ARGUMENT; two ranges that
+ * share a member decode it twice.  An index that cannot be right -- no entry, uoff[0] != 0, coff or uoff falling, a
+ * member of more than 65536 bytes, coff beyond the image -- fails every range of THAT image with
+ * ZH_ERR_INVALID_BUFFER.  Of an image only the bytes [coff[k0], coff[k1 + 1]) of the members k0 .. k1 a range
+ * touches are uploaded, spans that overlap or touch once.  Every touched member's header is checked as above; it
+ * must end at coff[k + 1] and its ISIZE be uoff[k + 1] - uoff[k], else ZH_ERR_INVALID_BUFFER; it is decoded whole
+ * (into the range's slot when it lies inside the range, else into scratch of up to 64 KiB and clipped) and verified
+ * by CRC-32 and ISIZE.  A range's status is that of its lowest failing member.  zh_debug_range_stats counts the
+ * call's uploaded bytes and its members decoded in place / via scratch. */
+int zh_bgzf_read_ranges(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n_images,
+                        const zh_bgzf_entry *index, const size_t *first, size_t n_ranges,
+                        const uint64_t *range_image, const uint64_t *range_off, const uint64_t *range_len,
+                        void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
  * ZIP archives as batch clients of the codec. *

@@ -101,6 +101,19 @@ _SIGS = {
                                         _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
     "zh_debug_range_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
                                         _c.POINTER(_c.c_uint64)]),
+    "zh_bgzf_write_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.c_int, _c.c_size_t, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                       _c.POINTER(_c.c_int32)]),
+    "zh_bgzf_read_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                      _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32),
+                                      _c.POINTER(_c.c_uint8)]),
+    "zh_bgzf_index_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.POINTER(_c.POINTER(_c.c_uint64)), _c.POINTER(_c.c_size_t),
+                                       _c.POINTER(_c.c_int32), _c.POINTER(_c.c_uint8)]),
+    "zh_bgzf_read_ranges": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
     "zh_crc32_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                   _c.POINTER(_c.c_uint32)]),
     "zh_compress_batch_crc32": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
@@ -879,6 +892,64 @@ class Engine:
         up, ip, sc = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
         self._check(self.lib.zh_debug_range_stats(self._h, _c.byref(up), _c.byref(ip), _c.byref(sc)))
         return up.value, ip.value, sc.value
+
+    # ---- BGZF (blocked gzip) ----
+    def bgzf_compress_batch(self, bufs, level=DefaultCompression, block_bytes=0):
+        """One BGZF file per buffer (zh_bgzf_write_batch): members of block_bytes (0: 65280) and the EOF marker.
+        -> (list of bytes | None, statuses)"""
+        return self._batch(self.lib.zh_bgzf_write_batch, bufs, level, block_bytes)
+
+    def bgzf_uncompress_batch(self, images, want_eof=False):
+        """The uncompressed data of BGZF files (zh_bgzf_read_batch) -> (list of bytes | None, statuses), with
+        want_eof also the list of has_eof flags."""
+        eof = (_c.c_uint8 * max(1, len(images)))()
+        outs, sts = self._batch(lambda *a: self.lib.zh_bgzf_read_batch(*a, eof), images)
+        return (outs, sts, list(eof)[:len(images)]) if want_eof else (outs, sts)
+
+    def bgzf_index_batch(self, images):
+        """The members of BGZF files from their headers alone (zh_bgzf_index_batch) -> (indexes, statuses, has_eof);
+        indexes[i]: [(coff, uoff), ...] closed by (end of the walk, total), None where the image failed."""
+        n = len(images)
+        keep = [bytes(b) for b in images]
+        srcs = (_c.c_void_p * max(1, n))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * max(1, n))(*[len(k) for k in keep])
+        idx, first = _c.POINTER(_c.c_uint64)(), (_c.c_size_t * (n + 1))()
+        sts, eof = (_c.c_int32 * max(1, n))(), (_c.c_uint8 * max(1, n))()
+        rc = self.lib.zh_bgzf_index_batch(self._h, srcs, lens, n, _c.byref(idx), first, sts, eof)
+        try:
+            self._check(rc)
+            out = [[(idx[2 * k], idx[2 * k + 1]) for k in range(first[i], first[i + 1])] if sts[i] == 0 else None
+                   for i in range(n)]
+        finally:
+            if idx:
+                self.lib.zh_free(idx)
+        return out, list(sts)[:n], list(eof)[:n]
+
+    def bgzf_read_ranges(self, images, indexes, ranges):
+        """Bytes [off, off + len) of the uncompressed data of images[image] for every (image, off, len) of `ranges`, one
+        call (zh_bgzf_read_ranges); indexes[i]: image i's [(coff, uoff), ...] as bgzf_index_batch returns it (None, what
+        it returns for an image that failed, is an index of no entries: that image's ranges fail with status 13).
+        -> (list of bytes | None, statuses)"""
+        if len(indexes) != len(images):
+            raise ValueError("indexes: one per image")
+        indexes = [idx if idx is not None else [] for idx in indexes]
+        ns, nr = len(images), len(ranges)
+        keep = [bytes(b) for b in images]
+        srcs = (_c.c_void_p * max(1, ns))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * max(1, ns))(*[len(k) for k in keep])
+        flat, first, (rs, ro, rl) = self._range_tables(indexes, ranges)
+        dsts, dlens, sts = (_c.c_void_p * max(1, nr))(), (_c.c_size_t * max(1, nr))(), (_c.c_int32 * max(1, nr))()
+        rc = self.lib.zh_bgzf_read_ranges(self._h, srcs, lens, ns, flat, first, nr, rs, ro, rl, dsts, dlens, sts)
+        outs = []
+        try:
+            for r in range(nr):
+                outs.append(_c.string_at(dsts[r], dlens[r]) if dsts[r] and sts[r] == 0 else None)
+        finally:
+            for r in range(nr):
+                if dsts[r]:
+                    self.lib.zh_free(dsts[r])
+        self._check(rc)
+        return outs, list(sts)[:nr]
 
     def crc32(self, src):
         src = bytes(src)

@@ -73,6 +73,55 @@ def read_range(src, index, off, length):
     return eng._raise_first(outs, sts)[0]
 
 
+def bgzf_compress_batch(srcs, level=DefaultCompression, block_bytes=0):
+    """One BGZF file (the blocked gzip of bgzip / htslib: any gunzip reads it) per buffer, in one call: members of
+    block_bytes (0: 65280) uncompressed bytes each and the EOF marker.  -> (outputs, statuses)"""
+    return engine().bgzf_compress_batch(srcs, level, block_bytes)
+
+
+def bgzf_compress(src, level=DefaultCompression, block_bytes=0):
+    """bgzf_compress_batch for one buffer -> bytes; raises ZippyError."""
+    eng = engine()
+    outs, sts = eng.bgzf_compress_batch([src], level, block_bytes)
+    return eng._raise_first(outs, sts)[0]
+
+
+def bgzf_uncompress_batch(images):
+    """The uncompressed data of BGZF files, every member verified by its CRC-32 and ISIZE.  -> (outputs, statuses); an
+    output is None where its status is not 0."""
+    return engine().bgzf_uncompress_batch(images)
+
+
+def bgzf_uncompress(image):
+    """bgzf_uncompress_batch for one file -> bytes; raises ZippyError."""
+    eng = engine()
+    outs, sts = eng.bgzf_uncompress_batch([image])
+    return eng._raise_first(outs, sts)[0]
+
+
+def bgzf_index(image):
+    """The members of a BGZF file from its headers and trailers alone: [(coff, uoff), ...], closed by (the file's end,
+    the uncompressed total).  Raises ZippyError where the file cannot be walked."""
+    eng = engine()
+    idx, sts, _ = eng.bgzf_index_batch([image])
+    return eng._raise_first(idx, sts)[0]
+
+
+def bgzf_read_ranges(images, indexes, ranges):
+    """Random access into BGZF files: bytes [off, off + len) of the uncompressed data of images[image] for every
+    (image, off, len) of `ranges`, in one call -- only the members a range touches are uploaded and decoded, each
+    verified by its checksum.  Ranges read like pread.  -> (outputs, statuses); an output is None where its status is
+    not 0."""
+    return engine().bgzf_read_ranges(images, indexes, ranges)
+
+
+def bgzf_read_range(image, index, off, length):
+    """bgzf_read_ranges for one range of one file -> bytes; raises ZippyError where the range cannot be read."""
+    eng = engine()
+    outs, sts = eng.bgzf_read_ranges([image], [index], [(0, off, length)])
+    return eng._raise_first(outs, sts)[0]
+
+
 def openZipArchive(image):
     """ziparchives.nim:183 openZipArchive on the bytes of an archive -> reader with walk_files(),
     extract_file(path), extract_batch(indices)."""

@@ -130,6 +130,7 @@ extern "C" const char* zh_strerror(int status) {
     case ZH_ERR_TAR_OPEN: return "Unexpected error while opening tarball";
     case ZH_ERR_TAR_OPEN_MODE: return "Unexpected error while opening tarball (mode)";
     case ZH_ERR_TAR_EOF: return "Attempted to read past end of file, corrupted tarball?";
+    case ZH_ERR_BGZF_HEADER: return "Invalid BGZF member header";
     default: return "Unknown status";
   }
 }

@@ -19,6 +19,8 @@ __device__ __forceinline__ Chunk16 funnel(const uint32_t (&w)[8], uint32_t b) {
   return r;
 }
 
+constexpr uint64_t kGatherSlack = 31;  // gather16 reads at most this far past its last source byte
+
 // Sixteen source bytes at s (any alignment) from two aligned 16-byte loads, recombined.  s & 15 is the same for every
 // chunk of a range (source and destination advance together), so the branches are uniform across the wave.  The
 // second load reads at most 31 bytes past s: the caller keeps that much readable behind its last source byte (an

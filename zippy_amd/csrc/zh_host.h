@@ -1,5 +1,5 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in fourteen files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in fifteen files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing -- run_compress, run_uncompress with run_segmented, run_ranges; work beside a run
 // on the context's second stream: SideLane --, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
@@ -8,7 +8,9 @@
 // reads from block-indexed streams: geometry, host call and its two kernels), the batch writers
 // zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
 // zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
-// all four share, zh_tar_dev.h and zh_zip_dev.h what the two of a format share, zh_gather.h the unaligned copy).
+// all four share, zh_scan.h the signature scan of zh_zip_read_batch.hip and zh_bgzf.hip, zh_tar_dev.h and zh_zip_dev.h
+// what the two of a format share, zh_gather.h the unaligned copy), and zh_bgzf.hip (BGZF written, read, indexed and
+// read by range).
 // No compute happens on the host.  This header also holds what those files build their device memory with: DevMem /
 // DevBuf (owners that free through the context's cache) and Arena (the device arrays of a plan or call, each declared once).
 #pragma once
@@ -90,7 +92,9 @@ void zh_launch_emit(hipStream_t, const uint8_t* d_src, uint8_t* d_dst, ZhCompres
 }
 
 // ---- byte-range reads from block-indexed streams (zh_ranges.hip) ----
-// One piece of at most 16 KiB of an edge block's bytes on its way from the plan's scratch into a range's slot.
+// One piece of at most kClipChunk bytes of an edge block's (zh_ranges.hip) or edge member's (zh_bgzf.hip) bytes on its
+// way from the scratch into a range's slot.
+constexpr uint32_t kClipChunk = 16384;  // bytes of a clip a workgroup moves
 struct ZhClipDesc {
   uint64_t src;  // byte offset in the scratch
   uint64_t dst;  // byte offset in d_dst

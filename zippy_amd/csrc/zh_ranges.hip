@@ -7,13 +7,6 @@
 #include "zh_gather.h"
 #include "zh_host.h"
 
-namespace {
-
-constexpr uint32_t kClipChunk = 16384;   // bytes of a clip a workgroup moves
-constexpr uint64_t kGatherSlack = 31;    // gather16 reads at most this far past its last source byte
-
-}  // namespace
-
 // One workgroup per piece of a clip: scratch[src, src + len) -> d_dst[dst, dst + len).  Stores of 16 bytes to aligned
 // addresses, the source gathered at whatever alignment it has (src & 15 is one value for the whole piece); byte
 // stores for the up to 15 bytes in front of the first aligned address and behind the last.  Runs whether or not the

@@ -1,7 +1,7 @@
 // Reading zip archives the v1 way: ZipArchive.open (src/zippy/ziparchives_v1.nim:105-349 openStreamImpl) for many
 // images a call.  The walk starts at byte 0 of an image and goes from record to record over the image's own bytes, so
 // the candidates of the walk are found first:
-//   zh_zipr_scan_kernel   every 16-byte chunk of the upload is read once a pass (count, then write): the positions
+//   zh_sig_scan_kernel    every 16-byte chunk of the upload is read once a pass (count, then write): the positions
 //                         whose four bytes are one of the three signatures and lie inside ONE image are the hits,
 //                         sorted by position
 //   zh_zipr_ranges_kernel per image: its range of hits; an image whose byte 0 is no hit is settled here
@@ -27,20 +27,13 @@
 // the next image, is no hit.
 #include <unordered_map>
 
-#include "zh_walk.h"
+#include "zh_scan.h"
 #include "zh_zip_dev.h"
 
 namespace {
 
 constexpr uint32_t kLocalSig = 0x04034b50u, kCentralSig = 0x02014b50u, kEndSig = 0x06054b50u;
-// the scan: a lane reads 16 bytes, a wave 1024 contiguous bytes, a workgroup 4096 a step, kScanSteps steps
-constexpr uint32_t kScanSteps = 4;
-constexpr uint64_t kScanStepBytes = 256 * 16, kScanGroupBytes = kScanStepBytes * kScanSteps;
 enum : uint8_t { kKindLocal = 1, kKindCentral = 2, kKindEnd = 3 };
-
-struct ZhZrImg {
-  uint64_t up_off, len;  // where the image lies in the upload buffer
-};
 
 // What stands at a position if a record starts there: the checks of openStreamImpl's loop body up to the decoder
 // (:115-200, :228-269, :296-319) in their order.  status: the first that failed; next: the position behind the record.
@@ -61,50 +54,12 @@ struct ZhZrRec {
   uint8_t kind, method, backslash, pad;
 };
 
-// the last image whose up_off <= p
-__device__ __forceinline__ uint32_t find_img(const ZhZrImg* __restrict__ imgs, uint32_t n_img, uint64_t p) {
-  uint32_t lo = 0, hi = n_img;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (imgs[mid].up_off <= p)
-      lo = mid;
-    else
-      hi = mid;
+// the scan's predicate (zh_scan.h)
+struct ZipSignature {
+  static __device__ __forceinline__ bool match(uint32_t v) {
+    return (v & 0xffffu) == 0x4b50u && (v == kLocalSig || v == kCentralSig || v == kEndSig);
   }
-  return lo;
-}
-// the first of hits[lo, hi) that is >= p (hi if there is none)
-__device__ __forceinline__ uint32_t lower_bound(const uint64_t* __restrict__ hits, uint32_t lo, uint32_t hi, uint64_t p) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (hits[mid] < p)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ bool is_signature(uint32_t v) {
-  return (v & 0xffffu) == 0x4b50u && (v == kLocalSig || v == kCentralSig || v == kEndSig);
-}
-
-// The 16 positions of the chunk at `at` (a multiple of 16) as a mask of hits: x = the chunk's words, nw = the word
-// behind it.  A candidate counts only inside one image.
-__device__ __forceinline__ uint32_t chunk_hits(const Chunk16& x, uint32_t nw, uint64_t at,
-                                               const ZhZrImg* __restrict__ imgs, uint32_t n_img) {
-  const uint32_t w[5] = {x.w[0], x.w[1], x.w[2], x.w[3], nw};
-  uint32_t m = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 16; j++)
-    if (is_signature(__builtin_amdgcn_alignbyte(w[(j >> 2) + 1], w[j >> 2], j & 3))) m |= 1u << j;
-  for (uint32_t rest = m; rest; rest &= rest - 1) {  // (rare: a handful a record)
-    const uint32_t j = (uint32_t)__ffs(rest) - 1;
-    const ZhZrImg g = imgs[find_img(imgs, n_img, at + j)];
-    if (at + j + 4 > g.up_off + g.len) m &= ~(1u << j);
-  }
-  return m;
-}
+};
 
 // a record's header at image position pos (p = the image, len its length); see ZhZrHead
 __device__ __forceinline__ ZhZrHead read_head(const uint8_t* __restrict__ p, uint64_t len, uint64_t pos) {
@@ -160,44 +115,6 @@ __device__ __forceinline__ ZhZrHead read_head(const uint8_t* __restrict__ p, uin
 }
 
 }  // namespace
-
-// The signature scan over the upload's bytes [0, n_bytes), n_bytes a multiple of 16.  A workgroup covers
-// kScanGroupBytes in kScanSteps steps; in a step a wave reads 1024 contiguous bytes, one aligned 16-byte load a lane.
-// The three bytes behind a lane's chunk come from its neighbour's registers (lane 63: one more word, of a line the
-// wave's next step reads anyway).  WRITE = false: sums[group] = the group's hits.  WRITE = true: sums[group] = the
-// hits before the group (sums[groups] = all hits); the positions go to hits[] in ascending order, and only the groups
-// that hold a hit read their bytes a second time.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void zh_zipr_scan_kernel(const uint8_t* __restrict__ d_in, uint64_t n_bytes,
-                                                           const ZhZrImg* __restrict__ imgs, uint32_t n_img,
-                                                           uint32_t* __restrict__ sums, uint64_t* __restrict__ hits) {
-  const uint64_t base = (uint64_t)blockIdx.x * kScanGroupBytes + 16ull * threadIdx.x;
-  uint32_t carry = WRITE ? sums[blockIdx.x] : 0u, count = 0;
-  if (WRITE && sums[blockIdx.x + 1] == carry) return;  // no hit in this group: its bytes are not read again
-#pragma unroll
-  for (uint32_t step = 0; step < kScanSteps; step++) {
-    const uint64_t at = base + step * kScanStepBytes;
-    const bool live = at < n_bytes;
-    Chunk16 x{};
-    if (live) x = *reinterpret_cast<const Chunk16*>(d_in + at);
-    uint32_t nw = (uint32_t)__shfl_down(x.w[0], 1);
-    if (live && zh_lane() == 63) nw = *reinterpret_cast<const uint32_t*>(d_in + at + 16);  // (the spare bytes at the latest)
-    const uint32_t m = live ? chunk_hits(x, nw, at, imgs, n_img) : 0u;
-    if (!WRITE) {
-      count += (uint32_t)__popc(m);
-    } else {
-      uint32_t total;
-      uint32_t k = carry + block_scan((uint32_t)__popc(m), &total);
-      for (uint32_t rest = m; rest; rest &= rest - 1) hits[k++] = at + (uint32_t)__ffs(rest) - 1;
-      carry += total;
-    }
-  }
-  if (!WRITE) {
-    uint32_t total;
-    (void)block_scan(count, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-  }
-}
 
 // Per image: ranges[2t .. 2t + 1] = its hits; start[t] = ZH_OK when its byte 0 is a hit, else what the loop's first
 // trip says (:115-116, :328-329)
@@ -367,7 +284,7 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   Events evs;
   if (tr.on) evs.create();
   if (evs.ok) (void)hipEventRecord(evs.e[0], s);
-  hipLaunchKernelGGL(zh_zipr_scan_kernel<false>, dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums,
+  hipLaunchKernelGGL((zh_sig_scan_kernel<false, ZipSignature>), dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums,
                      (uint64_t*)nullptr);
   if (evs.ok) (void)hipEventRecord(evs.e[1], s);
   hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, gsums, n_groups);
@@ -379,7 +296,7 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   uint64_t* const hits = reinterpret_cast<uint64_t*>(d_hits.p);
   if (evs.ok) (void)hipEventRecord(evs.e[2], s);
   if (n_hits)
-    hipLaunchKernelGGL(zh_zipr_scan_kernel<true>, dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums, hits);
+    hipLaunchKernelGGL((zh_sig_scan_kernel<true, ZipSignature>), dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums, hits);
   if (evs.ok) {
     (void)hipEventRecord(evs.e[3], s);
     fprintf(stderr, "[zh] %-28s %8.3f ms (HIP events; count pass: %llu bytes read)\n", "zip read: scan kernel 1",

@@ -93,6 +93,14 @@ struct ZhCompressArgs {
   int32_t* status;
 };
 
+// One launch of the exact BestSpeed matcher (zh_l1_match.hip), as zh_l1_match_prepare decided it: `pooled` waves with
+// their tables in the pool and `lds` waves with theirs in LDS share the fragments -- both > 0: the mixed launch, two
+// kernels side by side --; `order`: the fragments' order (null: as numbered)
+struct ZhL1Launch {
+  uint32_t pooled, lds;
+  const uint32_t* order;
+};
+
 // Checksum piece: d_data[off .. off+len), len <= 32768.  With a device-side length
 // array (inflate output) len = clamp(dyn_len[buf] - rel_off, 0, len): `len` is then the
 // piece's share of the slot capacity.

@@ -66,9 +66,10 @@ void zh_launch_seg_stats(hipStream_t, ZhSegArgs g, uint64_t* stats);
 void zh_launch_seg_write(hipStream_t, const uint8_t* d_src, ZhInflateArgs a, const uint32_t* tok_pool, ZhSegArgs g);
 void zh_launch_seg_windows(hipStream_t, ZhInflateArgs a, ZhSegArgs g);
 void zh_launch_seg_finish(hipStream_t, uint8_t* d_dst, ZhInflateArgs a, ZhSegArgs g);
+ZhL1Launch zh_l1_match_prepare(hipStream_t, uint32_t nfrags, uint32_t* next_frag, uint32_t* cost, uint32_t* order,
+                               uint32_t* hist, int use_order, int side_ok);
 void zh_launch_l1_match(hipStream_t, const uint8_t* d_src, ZhCompressArgs a, int huffman_only,
-                        uint16_t* table_pool, uint32_t* next_frag, uint32_t* cost, uint32_t* order, uint32_t* hist,
-                        int use_order);
+                        uint16_t* table_pool, uint32_t* next_frag, uint32_t* cost, ZhL1Launch l, int lds_part);
 uint32_t zh_l1_table_slots(void);
 void zh_launch_l1p_match(hipStream_t, const uint8_t* d_src, ZhCompressArgs a, uint16_t* link_pool,
                          uint32_t* next_frag);
@@ -427,6 +428,7 @@ static inline bool valid_block_bytes(size_t bb) {
 // (zh_plan_run.hip)
 ZH_INTERNAL bool inflate_split_enabled(const zh_ctx* ctx);
 ZH_INTERNAL bool l1_parallel(const zh_ctx* ctx);
+ZH_INTERNAL int run_l1_match(zh_plan* p, const uint8_t* d_src, bool with_order);
 ZH_INTERNAL bool plan_token_pool(zh_plan* p);
 ZH_INTERNAL void plan_lend_token_pool(zh_plan* p, uint32_t* pool, uint64_t words);
 static inline void plan_set_count_only(zh_plan* plan, int on) { plan->ia.count_only = on; }

@@ -231,7 +231,8 @@ extern "C" int zh_debug_tokens(zh_ctx* ctx, const void* src, size_t len, int lev
   hipStream_t s = ctx->stream;
   const ZhCompressArgs& a = p->ca;
   if (level == 1 || level == -2) {
-    zh_launch_l1_match(s, d_src.p, a, level == -2, p->l1_tables, p->l1_counter, nullptr, nullptr, nullptr, 0);
+    st = run_l1_match(p, d_src.p, false);  // (a single run: nothing to order the fragments by)
+    if (st) return st;
   } else {
     const int* cfg = kChainConfig[level == -1 ? 6 : level];
     for (const auto& r : p->chain_ranges) {

@@ -37,15 +37,16 @@ struct __attribute__((packed)) Bytes16 {
 }  // namespace
 
 // kLdsTable: the wave's hash table in LDS (32 KiB: four waves per CU, no table traffic at all)
-// instead of the HBM pool.  A measurement aid for the trade DESIGN.md 4.1 describes -- with one
-// wave per fragment the pooled form is the faster one by far -- selected with ZH_L1_TABLE=lds.
+// instead of the HBM pool.  Alone it loses by far (the test build's ZH_L1_TABLE=lds);
+// a few such waves BESIDE the pooled ones, in the LDS those leave over, share the batch with them
+// (zh_l1_match_prepare: the mixed launch).  `ticket_base`: the first ticket of this launch's wave 0.
 template <bool kLdsTable>
 __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restrict__ d_src,
                                                          ZhCompressArgs a, int huffman_only,
                                                          uint16_t* __restrict__ table_pool,
                                                          uint32_t* __restrict__ next_frag,
                                                          const uint32_t* __restrict__ order,
-                                                         uint32_t* __restrict__ cost) {
+                                                         uint32_t* __restrict__ cost, uint32_t ticket_base) {
   __shared__ uint32_t s_hist[ZH_HIST_STRIDE];
   // parse: 4096 byte-wide counters (4 per dword) of the probes per table slot in one step,
   // all zero between steps; afterwards the first 4 KiB are the coverage bitmap (bit p set:
@@ -62,13 +63,14 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
   // L1-bypassing loads, written through, re-zeroed for every fragment the wave takes
   __shared__ uint16_t s_table_lds[kLdsTable ? 16384 : 2];
   uint16_t* const s_table = kLdsTable ? s_table_lds : table_pool + (size_t)blockIdx.x * 16384u;
-  // fragments are handed out first come, first served (`next_frag` starts at gridDim.x): they cost
+  // fragments are handed out first come, first served (`next_frag` starts behind every wave's own first ticket): they cost
   // very different amounts of time, and a fixed share per wave leaves the last ones running alone
   // ... and from a plan's second run on the cheapest ones last: `order` (null: as numbered) is the fragments as numbered
   // but for the cheapest two rounds' worth, which go to the end -- by what they cost the run before (`cost`: this
-  // run's, for the next; zh_launch_l1_match) --, so that what is still running when waves fall idle is short.  Which
+  // run's, for the next; zh_l1_match_prepare) --, so that what is still running when waves fall idle is short.  Which
   // wave takes which fragment when decides nothing of what comes out.
-  for (uint32_t ticket = blockIdx.x; ticket < a.nfrags;) {
+  uint32_t taken = 0;  // (fragments this wave parsed: next_frag[1] the pooled waves' sum, next_frag[2] the LDS-table waves')
+  for (uint32_t ticket = ticket_base + blockIdx.x; ticket < a.nfrags; taken++) {
   const uint32_t f = order ? order[ticket] : ticket;
   const uint64_t t_start = zh_clock();
   KPROF_DECL(16);  // cycles: 0 stage-in, 1 vector part, 2 fast walk, 3 slow walk, 4 inserts, 5 stats; counts: 6..12
@@ -615,6 +617,7 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
     ticket = zh_bcast(nf);
   }
   }  // next fragment of this wave
+  if (lane == 0 && taken) atomicAdd(next_frag + (kLdsTable ? 2 : 1), taken);
 }
 
 // ---- the cheap ones last: from a plan's second run on the fragments are handed out as numbered -- the mix of kinds
@@ -712,68 +715,128 @@ __global__ __launch_bounds__(256) void zh_l1_cost_scatter_kernel(const uint32_t*
   if (i < n) order[last ? (n - ntail) + before : i - before] = i;
 }
 
+namespace {
+// ZH_L1_SLOTS (tuning override): the pooled waves of every launch, and the tables of the pool
+long l1_slots_env() {
+  static const long v = [] {
+    const char* e = getenv("ZH_L1_SLOTS");
+    const long v = e ? atol(e) : 0;
+    return v >= 1 && v <= 16384 ? v : 0;
+  }();
+  return v;
+}
+// the LDS-table waves of a mixed launch (ZH_L1_LDS_WAVES; 0: none, every launch is the pooled kernel alone)
+uint32_t l1_lds_waves() {
+  static const uint32_t waves = [] {
+    const char* e = getenv("ZH_L1_LDS_WAVES");
+    const long v = e ? atol(e) : -1;
+    return v >= 0 && v <= 1024 ? (uint32_t)v : 256u;
+  }();
+  return waves;
+}
+}  // namespace
+
 // waves that share the table pool: 19 per CU on 256 CUs, LDS 7.4 KiB each (ZH_L1_SLOTS: tuning override).  The kernel's
 // throughput is the fabric's, not its waves': 4096 .. 5376 of them are within 2 %; three rounds on one box,
 // ms for 4096 x 1 MiB: 4608 waves 63.7, 4864 63.5, 5120 (rounds 2-5) 64.4; one GPU's share (16 384 fragments) the same
-extern "C" uint32_t zh_l1_table_slots(void) {
-  static const uint32_t slots = [] {
-    const char* e = getenv("ZH_L1_SLOTS");
-    const long v = e ? atol(e) : 0;
-    return v >= 64 && v <= 16384 ? (uint32_t)v : 4864u;
-  }();
-  return slots;
+extern "C" uint32_t zh_l1_table_slots(void) { return l1_slots_env() ? (uint32_t)l1_slots_env() : 4864u; }
+
+// next_frag[0]: the next ticket; [1], [2]: the fragments the pooled / the LDS-table waves parsed (ZH_TRACE)
+__global__ void zh_l1_set_counter_kernel(uint32_t* next_frag, uint32_t v) {
+  next_frag[0] = v;
+  next_frag[1] = next_frag[2] = 0;
 }
 
-__global__ void zh_l1_set_counter_kernel(uint32_t* next_frag, uint32_t v) { *next_frag = v; }
+__global__ void zh_l1_head_start_kernel() {}
 
+// What a run's launch looks like, and everything in front of it on `stream`: the order and the counter.
+// The mixed launch (`side_ok`: the caller has a second stream for it; batches of at least a fragment a wave): 16 pooled
+// waves a CU instead of 19 -- past 16 the memory system is the limit, DESIGN.md 4.1 -- and in the LDS the other three
+// leave (3 x 7.4 KiB beside 17.5 KiB nobody had) one wave a CU with its table there, 40 KiB, which asks a tenth of
+// the fabric.  A wave's first ticket is its own index, the pooled ones' 0 .. P-1, the others' P .. P+L-1; the counter
+// starts behind them and every later ticket is drawn from it by both kernels, first come, first served: neither
+// waits for the other, and an LDS-table wave that finds no room while pooled waves hold the CU only comes later.
 // `cost` / `order` / `hist` (each may be null): this run's cycles a fragment; the order made of LAST run's (built here
 // when `use_order`: the plan has run before); 128 words + a word a 256 fragments of scratch for that
-extern "C" void zh_launch_l1_match(hipStream_t stream, const uint8_t* d_src, ZhCompressArgs a,
-                                   int huffman_only, uint16_t* table_pool, uint32_t* next_frag, uint32_t* cost,
-                                   uint32_t* order, uint32_t* hist, int use_order) {
-  if (!a.nfrags) return;
-#ifdef ZH_XCHECK  // the test / measurement build only: the same kernel with its table in LDS (ZH_L1_TABLE=lds)
+extern "C" ZhL1Launch zh_l1_match_prepare(hipStream_t stream, uint32_t nfrags, uint32_t* next_frag, uint32_t* cost,
+                                          uint32_t* order, uint32_t* hist, int use_order, int side_ok) {
+  ZhL1Launch l = {0, 0, nullptr};
+  if (!nfrags) return l;
+#ifdef ZH_XCHECK  // the test / measurement build only: every fragment on the LDS-table form (ZH_L1_TABLE=lds)
   static const bool lds = [] {
     const char* e = getenv("ZH_L1_TABLE");
     return e && strcmp(e, "lds") == 0;
   }();
   if (lds) {
-    const uint32_t grid = a.nfrags < 1024u ? a.nfrags : 1024u;  // (39.4 KiB of LDS: four waves per CU)
-    hipLaunchKernelGGL(zh_l1_set_counter_kernel, dim3(1), dim3(1), 0, stream, next_frag, grid);
-    hipLaunchKernelGGL(zh_l1_match_kernel<true>, dim3(grid), dim3(64), 0, stream, d_src, a, huffman_only,
-                       table_pool, next_frag, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    return;
+    l.lds = nfrags < 1024u ? nfrags : 1024u;  // (39.4 KiB of LDS: four waves per CU)
+    hipLaunchKernelGGL(zh_l1_set_counter_kernel, dim3(1), dim3(1), 0, stream, next_frag, l.lds);
+    return l;
   }
 #endif
-  const uint32_t slots = zh_l1_table_slots();
-  const uint32_t grid = a.nfrags < slots ? a.nfrags : slots;
-  const bool sorted = use_order && cost && order && hist && a.nfrags > grid;  // (one round of the machine: nothing to order)
+  const uint32_t mixed_pooled = l1_slots_env() ? (uint32_t)l1_slots_env() : 4096u;
+  if (side_ok && l1_lds_waves() && nfrags >= mixed_pooled + l1_lds_waves()) {
+    l.pooled = mixed_pooled;
+    l.lds = l1_lds_waves();
+  } else {
+    l.pooled = nfrags < zh_l1_table_slots() ? nfrags : zh_l1_table_slots();
+  }
+  const uint32_t grid = l.pooled + l.lds;
+  const bool sorted = use_order && cost && order && hist && nfrags > grid;  // (one round of the machine: nothing to order)
   if (sorted) {
-    const uint32_t g = (a.nfrags + 255u) / 256u;
+    const uint32_t g = (nfrags + 255u) / 256u;
     static const uint32_t rounds = [] {  // (ZH_L1_TAIL_ROUNDS: measurement)
       const char* e = getenv("ZH_L1_TAIL_ROUNDS");
       const long v = e ? atol(e) : 0;
       return v >= 1 && v <= 64 ? (uint32_t)v : 2u;
     }();
-    const uint32_t tail = a.nfrags / 2u < rounds * grid ? a.nfrags / 2u : rounds * grid;  // two rounds' worth, half of all at most
+    const uint32_t tail = nfrags / 2u < rounds * grid ? nfrags / 2u : rounds * grid;  // two rounds' worth, half of all at most
     uint32_t* blk = hist + 128;  // (hist: 128 words + a word a block of 256 fragments)
     (void)hipMemsetAsync(hist, 0, 128u * sizeof(uint32_t), stream);
-    hipLaunchKernelGGL(zh_l1_cost_hist_kernel, dim3(g), dim3(256), 0, stream, cost, a.nfrags, hist);
-    if (a.nfrags < 8u * grid) {
+    hipLaunchKernelGGL(zh_l1_cost_hist_kernel, dim3(g), dim3(256), 0, stream, cost, nfrags, hist);
+    if (nfrags < 8u * grid) {
       // a few rounds of the machine (one GPU's share of eight: 3.2): the dearest first -- what starts last then is
       // short (512 x 1 MiB: 9.41 -> 8.97 ms, against 9.33 with only the cheapest moved)
       hipLaunchKernelGGL(zh_l1_cost_places_kernel, dim3(1), dim3(64), 0, stream, hist);
-      hipLaunchKernelGGL(zh_l1_cost_sort_kernel, dim3(g), dim3(256), 0, stream, cost, a.nfrags, hist, order);
+      hipLaunchKernelGGL(zh_l1_cost_sort_kernel, dim3(g), dim3(256), 0, stream, cost, nfrags, hist, order);
     } else {
       // many rounds (4096 x 1 MiB: 25.6): the order the batch came in, the cheapest two rounds' worth last (65.57 ->
       // 65.22 ms; all of them sorted: 66.4, see above)
       hipLaunchKernelGGL(zh_l1_cost_cut_kernel, dim3(1), dim3(64), 0, stream, hist, tail);
-      hipLaunchKernelGGL(zh_l1_cost_count_kernel, dim3(g), dim3(256), 0, stream, cost, a.nfrags, hist, blk);
+      hipLaunchKernelGGL(zh_l1_cost_count_kernel, dim3(g), dim3(256), 0, stream, cost, nfrags, hist, blk);
       hipLaunchKernelGGL(zh_l1_cost_scan_kernel, dim3(1), dim3(1024), 0, stream, blk, g);
-      hipLaunchKernelGGL(zh_l1_cost_scatter_kernel, dim3(g), dim3(256), 0, stream, cost, a.nfrags, hist, blk, order);
+      hipLaunchKernelGGL(zh_l1_cost_scatter_kernel, dim3(g), dim3(256), 0, stream, cost, nfrags, hist, blk, order);
     }
+    l.order = order;
   }
   hipLaunchKernelGGL(zh_l1_set_counter_kernel, dim3(1), dim3(1), 0, stream, next_frag, grid);
-  hipLaunchKernelGGL(zh_l1_match_kernel<false>, dim3(grid), dim3(64), 0, stream, d_src, a, huffman_only,
-                     table_pool, next_frag, sorted ? order : (const uint32_t*)nullptr, cost);
+  return l;
 }
+
+// One of the launch's kernels on `stream`, behind what zh_l1_match_prepare put on its stream: the pooled waves, or
+// (`lds_part`) the LDS-table waves.  `table_pool` holds l.pooled tables at least (zh_plan_compress: zh_l1_table_slots).
+extern "C" void zh_launch_l1_match(hipStream_t stream, const uint8_t* d_src, ZhCompressArgs a, int huffman_only,
+                                   uint16_t* table_pool, uint32_t* next_frag, uint32_t* cost, ZhL1Launch l,
+                                   int lds_part) {
+  if (lds_part) {
+    if (l.lds)
+      hipLaunchKernelGGL(zh_l1_match_kernel<true>, dim3(l.lds), dim3(64), 0, stream, d_src, a, huffman_only, table_pool,
+                         next_frag, l.order, cost, l.pooled);
+  } else if (l.pooled) {
+    // (a mixed launch: the two kernels' streams become ready together, and whichever is dispatched first takes the
+    // CUs: pooled waves that come first do not spread evenly, many CUs hold more than 16 and have no 40 KiB left, and
+    // the LDS-table waves start when those retire -- at worst for their first tickets only.  Nothing waits for anything:
+    // a few empty launches in front of the pooled kernel merely let the other stream's 256 workgroups go first.
+    // Fragments of 131 072 the LDS-table waves took, eight runs each: no such launch 256 (seven times) and 8859; one:
+    // 256 .. 379 six times, 8866, 8883; three: 8890 .. 8968 every time; eight: 8853 .. 8930.  DESIGN.md 4.1)
+    static const uint32_t head_start = [] {  // (ZH_L1_HEAD_START: measurement)
+      const char* e = getenv("ZH_L1_HEAD_START");
+      const long v = e ? atol(e) : -1;
+      return v >= 0 && v <= 16 ? (uint32_t)v : 3u;
+    }();
+    for (uint32_t i = 0; l.lds && i < head_start; i++)
+      hipLaunchKernelGGL(zh_l1_head_start_kernel, dim3(1), dim3(1), 0, stream);
+    hipLaunchKernelGGL(zh_l1_match_kernel<false>, dim3(l.pooled), dim3(64), 0, stream, d_src, a, huffman_only,
+                       table_pool, next_frag, l.order, cost, 0u);
+  }
+}
+

@@ -140,7 +140,8 @@ extern "C" int zh_plan_compress_blocks(zh_ctx* ctx, size_t n, const uint64_t* sr
                             : range_blocks <= zh_chain_prev_slice() ? range_blocks * (size_t)ZH_CHAIN_HEAD_WORDS
                                                                     : range_blocks * ((size_t)2 << 15);  // (zh_launch_chain_prev)
   ar.add(p->head_scratch, head_words);
-  // one 32 KiB hash table per persistent matcher wave (zh_launch_l1_match: min(fragments, slots) waves)
+  // one 32 KiB hash table per persistent pooled matcher wave (zh_l1_match_prepare: min(fragments, slots) waves at most;
+  // the mixed launch has fewer pooled waves than that, and its LDS-table waves need none)
   // (the parallel parse, zh_launch_l1p_match, keeps 128 KiB of table results per workgroup there instead)
   const size_t l1tab_bytes = level == 1 ? std::max(std::min<size_t>(nf, zh_l1_table_slots()) * 32768,
                                                    std::min<size_t>(nf, zh_l1p_slots()) * 131072)

@@ -141,6 +141,40 @@ static bool l1_longest_first() {
   }();
   return on;
 }
+// The exact BestSpeed matcher of a compress plan on the context's stream (zh_l1_match.hip).  Its mixed launch is two
+// kernels that share the fragments: the ordering and the counter in front of the fork, the LDS-table waves on the
+// second stream beside the pooled ones, and the join behind both -- whatever follows (the code builder reads every
+// fragment's histograms) sees all of it, and the main lane's interval of the matcher covers both kernels; the second
+// stream's gets no entry of its own in zh_plan_kernel_times.  `use_order`: the cheapest fragments of the last run last.
+int run_l1_match(zh_plan* p, const uint8_t* d_src, bool use_order) {
+  zh_ctx* ctx = p->ctx;
+  hipStream_t s = ctx->stream;
+  const ZhCompressArgs& a = p->ca;
+  const int huffman_only = p->level == -2;
+  const ZhL1Launch l = zh_l1_match_prepare(s, a.nfrags, p->l1_counter, p->l1_cost, p->l1_order, p->l1_hist, use_order,
+                                           second_stream(ctx));
+  SideLane aux(p, s);
+  if (l.pooled && l.lds) {
+    ZH_TRY(aux.fork());
+    zh_launch_l1_match(aux.side, d_src, a, huffman_only, p->l1_tables, p->l1_counter, p->l1_cost, l, 1);
+    ZH_HIP(ctx, hipEventRecord(ctx->aux_join, aux.side));
+    zh_launch_l1_match(s, d_src, a, huffman_only, p->l1_tables, p->l1_counter, p->l1_cost, l, 0);
+    ZH_TRY(aux.join());
+  } else {
+    zh_launch_l1_match(s, d_src, a, huffman_only, p->l1_tables, p->l1_counter, p->l1_cost, l, l.lds != 0);
+  }
+  ZH_HIP(ctx, hipGetLastError());
+  static const bool trace = getenv("ZH_TRACE") != nullptr;
+  if (trace && a.nfrags) {  // (waits for the run: a tuning aid)
+    uint32_t c[3] = {0, 0, 0};
+    ZH_HIP(ctx, hipMemcpyAsync(c, p->l1_counter, sizeof(c), hipMemcpyDeviceToHost, s));
+    ZH_HIP(ctx, hipStreamSynchronize(s));
+    fprintf(stderr, "zippy_hip: exact matcher: %u pooled waves took %u fragments, %u LDS-table waves %u, of %u\n", l.pooled,
+            c[1], l.lds, c[2], a.nfrags);
+  }
+  return ZH_OK;
+}
+
 // BestSpeed parse: 0 the reference's (snappy.nim:12-136, byte-identical streams), 1 the parallel
 // parse of zh_l1p_match.hip (valid streams of about the same size, not the reference's bytes)
 bool l1_parallel(const zh_ctx* ctx) {
@@ -314,8 +348,7 @@ static int run_compress(zh_plan* p, const uint8_t* d_src, uint8_t* d_dst) {
   } else if (p->level == 1 || p->level == -2) {
     prof_mark(p, "zh_l1_match_kernel");
     // (from the second run on the cheapest fragments -- by what they cost the run before -- are handed out last)
-    zh_launch_l1_match(s, d_src, a, p->level == -2, p->l1_tables, p->l1_counter, p->l1_cost, p->l1_order, p->l1_hist,
-                       p->l1_runs > 0 && l1_longest_first());
+    ZH_TRY(run_l1_match(p, d_src, p->l1_runs > 0 && l1_longest_first()));
     p->l1_runs++;
   } else if (p->level != 0) {
     const int* cfg = kChainConfig[p->level == -1 ? 6 : p->level];

@@ -20,7 +20,7 @@
 #include "zh_common.h"
 #include "zh_kprof.h"
 #include "zh_tables.h"
-#include "zh_inflate_tables.h"
+#include "zh_inflate_header.h"
 
 
 // ---------------------------------------------------------------------------
@@ -373,12 +373,7 @@ __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __res
   // input: the stream is addressed in bits from the 4-byte aligned base below `src`; 64 dwords
   // at a time go through a 512-byte LDS ring (bitstreams.nim:22-49's refill)
   const uint64_t end = mis + src_len;  // first byte offset (from asrc) past the stream
-  auto load_dword = [&](uint64_t off) -> uint32_t {  // bytes past the end read as zero
-    if (off >= end) return 0u;
-    uint32_t v = asrc[off >> 2];
-    if (off + 4 > end) v &= (1u << (8 * (uint32_t)(end - off))) - 1u;
-    return v;
-  };
+  auto load_dword = [&](uint64_t off) -> uint32_t { return load_dword_end(asrc, off, end); };
   uint64_t bp = 0;      // stream position in bits (from asrc)
   uint64_t in_hi = 0;   // dwords below in_hi are staged (the ring holds the last kInWords of them)
   uint32_t wnxt = 0;    // lane l: dword in_hi + l, loaded ahead of its use
@@ -405,7 +400,10 @@ __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __res
                    d2 = zh_bcast(s_in[(wi + 2u) & (kInWords - 1u)]);
     return (uint64_t)zh_alignbit(d1, d0, sh) | ((uint64_t)zh_alignbit(d2, d1, sh) << 32);
   };
-  // header bit reader: hb caches the bits at bp
+  // The header bit reader (hb caches the bits at bp) and, in the block loop below, the header itself: a copy of
+  // BlockHeaderReader (zh_inflate_header.h: the same checks in the same order; keep the two alike).  With the shared
+  // reader this kernel took 3 % longer on the indexed form, where a block's latency is the kernel's time
+  // (profiles/inflate_header_ab.json), so it keeps its own.
   uint64_t hb = 0;
   uint32_t hc = 0;
   auto need = [&]() {
@@ -422,21 +420,6 @@ __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __res
     return v;
   };
   auto past_end = [&]() -> bool { return bp > end * 8; };  // the role of `bitsBuffered < 0`
-  // inflate.nim:67-91 decodeSymbolSlow for codes longer than the LUT on the bits in `bits`;
-  // returns the symbol (0xffff = unassigned code) and its length in *nb
-  auto decode_slow = [&](uint32_t bits, uint32_t lut_bits, const HuffTab* tab, const uint16_t* values,
-                         uint32_t* nb) -> uint32_t {
-    const uint32_t k = __brev(bits) >> 16;
-    uint32_t cl = lut_bits + 1;
-    while (cl < 16 && k >= zh_bcast(tab->max_codes[cl])) cl++;
-    *nb = 0;
-    if (cl >= 16) return 0xffffu;
-    const uint32_t id = ((k >> (16 - cl)) - zh_bcast(tab->first_code[cl]) +
-                         zh_bcast(tab->first_symbol[cl])) & 0xffffu;
-    *nb = cl;
-    return zh_bcast(values[id]);
-  };
-
   KPROF_DECL(8);  // decode wave: 0 waiting for the output wave, 1 other work; 2 rounds; 3 waves; 4 vector decode; 5 chain walks; 6 staging
   uint32_t rk = 0;  // rounds handed over so far
   int st = ZH_OK;
@@ -514,7 +497,7 @@ __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __res
           sym = e >> 16;
         } else {
           uint32_t nb;
-          sym = decode_slow((uint32_t)hb, 7, &s_tab_cl, s_val_cl, &nb);
+          sym = decode_symbol_slow<true>((uint32_t)hb, 7, &s_tab_cl, s_val_cl, &nb);
           take(nb);
         }
         if (past_end()) { st = ZH_ERR_END_OF_BUFFER; break; }
@@ -699,7 +682,7 @@ __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __res
         uint32_t used;
         if (se == 0) {  // longer than the LUT, or unassigned
           uint32_t nb;
-          const uint32_t sym = decode_slow((uint32_t)sv, kLitBits, &s_tab_lit, s_val_lit, &nb);
+          const uint32_t sym = decode_symbol_slow<true>((uint32_t)sv, kLitBits, &s_tab_lit, s_val_lit, &nb);
           se = litlen_entry(sym, 0);
           used = nb;
         } else {
@@ -722,7 +705,7 @@ __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __res
           uint32_t sde = zh_bcast(s_dst[(uint32_t)sv & ((1u << kDistBits) - 1u)]);
           uint32_t dnb;
           if (sde == 0) {
-            const uint32_t dsym = decode_slow((uint32_t)sv, kDistBits, &s_tab_dist, s_val_dist, &dnb);
+            const uint32_t dsym = decode_symbol_slow<true>((uint32_t)sv, kDistBits, &s_tab_dist, s_val_dist, &dnb);
             sde = dist_entry(dsym, 0);
           } else {
             dnb = sde & 15u;

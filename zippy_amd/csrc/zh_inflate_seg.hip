@@ -53,7 +53,7 @@
 #include "zh_common.h"
 #include "zh_kprof.h"
 #include "zh_tables.h"
-#include "zh_inflate_tables.h"
+#include "zh_inflate_header.h"
 
 namespace {
 
@@ -69,30 +69,11 @@ constexpr uint32_t kSegCandStored = 0x80000000u;  // a queued candidate that rea
 // staged in LDS as dwords.
 constexpr uint32_t kFindStage = kFindBatch / 32u + 8u;  // (a thread reads five dwords from its 64 positions' first)
 
-// the 32 bits at bit `rel` of the staged bytes
-__device__ __forceinline__ uint32_t seg_peek(const uint32_t* s_buf, uint32_t rel) {
-  const uint32_t i = rel >> 5;
-  return zh_alignbit(s_buf[i + 1u], s_buf[i], rel);
-}
-// the 32 bits at bit p of the stream itself (bits behind its end read as zero)
-__device__ __forceinline__ uint32_t seg_peek_stream(const uint8_t* src, uint64_t len, uint64_t p) {
-  const uint64_t b = p >> 3;
-  uint64_t v = 0;
-  if (b + 8 <= len) {
-    struct __attribute__((packed)) U64 { uint64_t v; };
-    v = reinterpret_cast<const U64*>(src + b)->v;
-  } else {
-    for (uint32_t i = 0; i < 8; i++)
-      if (b + i < len) v |= (uint64_t)src[b + i] << (8 * i);
-  }
-  return (uint32_t)(v >> ((uint32_t)p & 7u));
-}
-
 // The code-length code of a dynamic header at staged bit p (whose first 13 bits have passed): 3
 // bits per entry, HCLEN + 4 entries; it must be complete.  Branch-free: most candidates end here.
 __device__ __forceinline__ bool seg_precode_complete(const uint32_t* s_buf, uint32_t p) {
-  const uint32_t hclen = ((seg_peek(s_buf, p + 13u) & 15u) + 4u) * 3u;  // bits
-  uint32_t w0 = seg_peek(s_buf, p + 17u), w1 = seg_peek(s_buf, p + 47u);  // entries 0-9, 10-18
+  const uint32_t hclen = ((bits_at(s_buf, p + 13u) & 15u) + 4u) * 3u;  // bits
+  uint32_t w0 = bits_at(s_buf, p + 17u), w1 = bits_at(s_buf, p + 47u);  // entries 0-9, 10-18
   w0 &= hclen >= 30u ? 0x3fffffffu : (1u << hclen) - 1u;
   w1 &= hclen > 30u ? (1u << (hclen - 30u)) - 1u : 0u;
   uint32_t kraft = 0;
@@ -112,17 +93,7 @@ __device__ __forceinline__ bool seg_precode_complete(const uint32_t* s_buf, uint
 // The rest of a dynamic header at bit p of the stream whose code-length code is complete.  The
 // bits come through a 128-bit window; the load of the next 64 is in flight while these are used.
 __device__ bool seg_lengths_ok(const uint8_t* src, uint64_t len, uint64_t p) {
-  auto load64 = [&](uint64_t b) -> uint64_t {  // stream bytes b .. b + 7 (zeros behind the end)
-    uint64_t v = 0;
-    if (b + 8 <= len) {
-      struct __attribute__((packed)) U64 { uint64_t v; };
-      v = reinterpret_cast<const U64*>(src + b)->v;
-    } else {
-      for (uint32_t i = 0; i < 8; i++)
-        if (b + i < len) v |= (uint64_t)src[b + i] << (8 * i);
-    }
-    return v;
-  };
+  auto load64 = [&](uint64_t b) -> uint64_t { return load_le_end<uint64_t>(src, len, b); };  // zeros behind the end
   uint64_t nb = p >> 3;  // next byte to load
   uint64_t lo = load64(nb), hi = load64(nb + 8);
   nb += 16;
@@ -338,99 +309,26 @@ __global__ __launch_bounds__(kFindThreads) void zh_seg_find_kernel(const uint8_t
   KPROF_FLUSH(56, 8);
 }
 
-// where code-length symbol s sits in a header (the inverse of c_clcl_order)
-__constant__ uint8_t c_clcl_place[19] = {3, 17, 15, 13, 11, 9, 7, 5, 4, 6, 8, 10, 12, 14, 16, 18, 0, 1, 2};
-
 // The code lengths of a candidate header, by a whole wave (the serial form above, seg_lengths_ok,
-// is what it has to agree with: ZH_SEG_CHECK=serial runs that one).  The code-length code goes into
-// a 128-entry table in LDS; then the 64 lanes decode the symbols that start at 64 consecutive bit
-// positions, a wave-uniform walk (one v_readlane a symbol) picks the ones really in the sequence,
-// and repeat counts, "previous length" and the two codes' Kraft sums are prefix sums and reductions.
-// The header (at most 17 + 57 + 316 * 14 bits) is staged in LDS first: one trip to memory a candidate.
+// is what it has to agree with: ZH_SEG_CHECK=serial runs that one): the tokens kernel's walk over the
+// header's staged dwords (code_lengths_walk, zh_inflate_header.h), with the two codes' Kraft sums,
+// the distance code's used lengths and "has an end of block" taken from every window instead of the
+// lengths being stored.  Its code-length code is complete (seg_precode_complete), so every position
+// has a code.  The header (at most 17 + 57 + 316 * 14 bits) is staged first: one trip to memory a candidate.
 constexpr uint32_t kHdrWords = 144;  // 4608 bits
 __device__ bool seg_lengths_ok_wave(const uint8_t* src, uint64_t len, uint64_t p, uint8_t* s_lut, uint32_t* s_hdr) {
   const unsigned lane = zh_lane();
   const uint64_t hb = p >> 3;  // first staged byte
   zh_wave_sync();              // (the candidate before is done with the staged bytes)
-  for (uint32_t i = lane; i < kHdrWords + 2u; i += 64u) {
-    const uint64_t b = hb + 4ull * i;
-    uint32_t v = 0;
-    if (b + 4 <= len) {
-      struct __attribute__((packed)) U32 { uint32_t v; };
-      v = reinterpret_cast<const U32*>(src + b)->v;
-    } else {
-      for (uint32_t k = 0; k < 4; k++)
-        if (b + k < len) v |= (uint32_t)src[b + k] << (8 * k);
-    }
-    s_hdr[i] = v;
-  }
+  for (uint32_t i = lane; i < kHdrWords + 2u; i += 64u) s_hdr[i] = load_le_end<uint32_t>(src, len, hb + 4ull * i);
   zh_wave_sync();
-  auto peek = [&](uint64_t at) -> uint32_t {  // the 32 bits at stream bit `at` (inside the staged header)
-    const uint32_t rel = (uint32_t)(at - hb * 8), i = rel >> 5;
-    return zh_alignbit(s_hdr[i + 1u], s_hdr[i], rel);
-  };
-  const uint32_t h = zh_bcast(peek(p));
+  const uint32_t p0 = (uint32_t)p & 7u;  // the header's first bit among the staged ones
+  const uint32_t h = zh_bcast(bits_at(s_hdr, p0));
   const uint32_t hlit = ((h >> 3) & 31u) + 257u, hdist = ((h >> 8) & 31u) + 1u, hclen = ((h >> 13) & 15u) + 4u;
-  // lane s < 19: the length of code-length symbol s (its place in the header: the inverse of c_clcl_order)
-  const uint32_t place = lane < 19u ? c_clcl_place[lane] : 99u;
-  const uint32_t l = place < hclen ? peek(p + 17u + 3u * place) & 7u : 0u;
-  // canonical codes (inflate.nim:29-65): symbols of one length in symbol order
-  uint32_t code = 0, next = 0;
-#pragma unroll
-  for (uint32_t k = 1; k <= 7; k++) {
-    const uint64_t m = __ballot(l == k);
-    if (l == k) code = next + (uint32_t)__popcll(m & zh_lanemask_lt());
-    next = (next + (uint32_t)__popcll(m)) << 1;
-  }
-  zh_wave_sync();  // (the table of the candidate before has been read)
-  if (l) {
-    const uint32_t rev = __brev(code) >> (32u - l);  // the stream carries codes first bit first
-    for (uint32_t e = rev; e < 128u; e += 1u << l) s_lut[e] = (uint8_t)(lane | (l << 5));
-  }
-  zh_wave_sync();
-  uint64_t q = p + 17u + 3u * hclen;
-  const uint32_t total = hlit + hdist;
-  uint32_t i = 0, prev = 0, lit_kraft = 0, dist_kraft = 0, dist_used = 0;
+  uint32_t lit_kraft = 0, dist_kraft = 0, dist_used = 0;
   bool eob = false;
-  while (i < total) {
-    // the symbol that starts at bit q + lane
-    const uint32_t w = peek(q + lane);
-    const uint32_t e = s_lut[w & 127u], sym = e & 31u, cl = e >> 5;
-    const uint32_t x = w >> cl;
-    uint32_t rep = 1, val = sym, nb = cl;
-    if (sym == 16u) {
-      rep = (x & 3u) + 3u;
-      nb += 2u;
-    } else if (sym == 17u) {
-      rep = (x & 7u) + 3u;
-      nb += 3u;
-      val = 0;
-    } else if (sym == 18u) {
-      rep = (x & 127u) + 11u;
-      nb += 7u;
-      val = 0;
-    }
-    if (__ballot(cl == 0u)) return false;  // (cannot happen with a complete code: keeps the walk below moving whatever the bits)
-    // the walk: which of the 64 positions start a symbol of the sequence
-    uint64_t on = 0;
-    uint32_t pos = 0;
-    while (pos < 64u) {
-      on |= 1ull << pos;
-      pos += (uint32_t)__builtin_amdgcn_readlane((int)nb, (int)pos);
-    }
-    bool mine = (on >> lane) & 1ull;
-    // entries before mine in this window; symbols past the end of the sequence do not count
-    const uint32_t incl = zh_wave_scan(mine ? rep : 0u);
-    const uint32_t at = i + incl - (mine ? rep : 0u);  // index of my first entry
-    if (mine && at >= total) mine = false;
-    const uint64_t ON = __ballot(mine);
-    if (__ballot(mine && at + rep > total)) return false;  // inflate.nim:161-162: runs past the end
-    // "previous length" for symbol 16: the nearest symbol before that is not a 16
-    const uint64_t plain = __ballot(mine && sym != 16u) & zh_lanemask_lt();
-    const uint32_t from = plain ? 63u - (uint32_t)__clzll((long long)plain) : 0u;
-    const uint32_t pv = (uint32_t)__shfl((int)val, (int)from, 64);
-    if (sym == 16u) val = plain ? pv : prev;
-    if (i == 0 && (ON & 1ull) && (uint32_t)__builtin_amdgcn_readlane((int)sym, 0) == 16u) return false;  // nothing to repeat
+  const uint32_t q = code_lengths_walk(s_hdr, p0 + 17u, hlit, hdist, hclen, (len - hb) * 8, s_lut,
+                                       [&](uint32_t at, uint32_t rep, uint32_t val, bool mine) -> bool {
     uint32_t lk = 0, dk = 0, du = 0;
     bool eb = false;
     if (mine && val) {
@@ -444,15 +342,9 @@ __device__ bool seg_lengths_ok_wave(const uint8_t* src, uint64_t len, uint64_t p
     dist_kraft += zh_wave_sum(dk);
     dist_used += zh_wave_sum(du);
     eob = eob || __ballot(eb) != 0;
-    if (lit_kraft > 32768u || dist_kraft > 32768u) return false;
-    // behind the last symbol taken
-    const uint32_t lastl = 63u - (uint32_t)__clzll((long long)ON);  // (ON has bit 0: at = i < total)
-    i = (uint32_t)__builtin_amdgcn_readlane((int)(at + rep), (int)lastl);
-    prev = (uint32_t)__builtin_amdgcn_readlane((int)val, (int)lastl);
-    q += lastl + (uint32_t)__builtin_amdgcn_readlane((int)nb, (int)lastl);
-  }
-  if (q > len * 8) return false;
-  if (!eob || lit_kraft != 32768u) return false;
+    return lit_kraft <= 32768u && dist_kraft <= 32768u;
+  });
+  if (!q || !eob || lit_kraft != 32768u) return false;
   return dist_kraft == 32768u || dist_used <= 1u;
 }
 
@@ -480,7 +372,7 @@ __device__ __forceinline__ void seg_note_start(const ZhSegArgs& g, uint32_t sid,
 }
 __global__ __launch_bounds__(64) void zh_seg_check_kernel(const uint8_t* __restrict__ d_src, ZhInflateArgs a,
                                                                   ZhSegArgs g, int serial) {
-  __shared__ uint8_t s_lut[128];
+  __shared__ alignas(4) uint8_t s_lut[128];  // (the walk clears it a dword a lane)
   __shared__ uint32_t s_hdr[kHdrWords + 2];
   const uint32_t w = blockIdx.x, lane = threadIdx.x;
   const uint32_t nc = g.cand_n[w] < kFindSlots ? g.cand_n[w] : kFindSlots;

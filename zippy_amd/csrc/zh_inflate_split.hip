@@ -62,7 +62,7 @@
 #define KPROF_HDR_MARK(i) ((void)0)
 #endif
 #include "zh_tables.h"
-#include "zh_inflate_tables.h"
+#include "zh_inflate_header.h"
 
 namespace {
 
@@ -180,12 +180,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
   const uint32_t mis = (uint32_t)((uintptr_t)src & 3u);
   const uint32_t* asrc = reinterpret_cast<const uint32_t*>(src - mis);
   const uint64_t end = mis + src_len;  // first byte offset (from asrc) past the stream
-  auto load_dword = [&](uint64_t off) -> uint32_t {  // bytes past the end read as zero
-    if (off >= end) return 0u;
-    uint32_t v = asrc[off >> 2];
-    if (off + 4 > end) v &= (1u << (8 * (uint32_t)(end - off))) - 1u;
-    return v;
-  };
+  auto load_dword = [&](uint64_t off) -> uint32_t { return load_dword_end(asrc, off, end); };
   // Batches take two forms of this kernel (zh_launch_inflate_tokens): a superchunk's worth of lanes is busy only while
   // the block lasts, and a stream of short blocks -- system zlib's are ~ 15 KiB of codes each -- ends most
   // superchunks of 256 subchunks early; 128 fill twice as well (zlib-6 members 12.7 -> 10.7 ms), at ~ 7 % more
@@ -208,6 +203,27 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
   int st = ZH_OK;
   bool final_block = false;
 
+  // the rare litlen entries (not "plain", zh_inflate_tables.h): a link to a second-level table, or an empty entry --
+  // inflate.nim:67-91 decodeSymbolSlow: longer than the tables reach, or unassigned.  What comes back is a plain
+  // entry, end of block, or an invalid symbol (kKindBad).
+  auto lit_rare = [&](uint32_t e, uint32_t v_lo) -> uint32_t {
+    if (e & 0x400u) e = s_lit[(e >> 16) + ((v_lo >> kLitBits) & ((1u << (e & 15u)) - 1u))];
+    if (e == 0) {
+      uint32_t nb;
+      const uint32_t sym = decode_symbol_slow<false>(v_lo, kLitBits, &s_tab_lit, s_val_lit, &nb);
+      e = litlen_entry(sym, nb);
+    }
+    return e;
+  };
+  auto dist_rare = [&](uint32_t de, uint32_t dv) -> uint32_t {
+    if (de & 0x400u) de = s_dst[(de >> 16) + ((dv >> kDistBits) & ((1u << (de & 15u)) - 1u))];
+    if (de == 0) {
+      uint32_t nb;
+      const uint32_t sym = decode_symbol_slow<false>(dv, kDistBits, &s_tab_dist, s_val_dist, &nb);
+      de = dist_entry(sym, nb);
+    }
+    return de;
+  };
   // ---- one token at superchunk-relative bit p, decoded by the calling lane alone ----
   // returns the token's bits (0: not a token, see *kind) and its record (the all-starts pass; the passes proper
   // live in run() below)
@@ -216,17 +232,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
     const uint32_t si = wi + 3u * (p / kSubBits);
     const uint32_t d0 = s_in[si], d1 = s_in[si + 1u], d2 = s_in[si + 2u];
     const uint32_t v_lo = zh_alignbit(d1, d0, sh), v_hi = zh_alignbit(d2, d1, sh);
-    uint32_t e = s_lit[v_lo & ((1u << kLitBits) - 1u)];
-    if (e & 0x400u) e = s_lit[(e >> 16) + ((v_lo >> kLitBits) & ((1u << (e & 15u)) - 1u))];
-    if (e == 0) {  // inflate.nim:67-91 decodeSymbolSlow: longer than the tables reach, or unassigned
-      const uint32_t k = __brev(v_lo) >> 16;
-      uint32_t cl = kLitBits + 1;
-      while (cl < 16 && k >= s_tab_lit.max_codes[cl]) cl++;
-      uint32_t sym = 0xffffu;
-      if (cl < 16)
-        sym = s_val_lit[((k >> (16 - cl)) - s_tab_lit.first_code[cl] + s_tab_lit.first_symbol[cl]) & 0xffffu];
-      e = litlen_entry(sym, cl < 16 ? cl : 0);
-    }
+    const uint32_t e = lit_rare(s_lit[v_lo & ((1u << kLitBits) - 1u)], v_lo);
     const uint32_t L = e & 15u;
     if (e & 0x8000u) {
       *kind = 0;
@@ -244,17 +250,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
     const uint32_t length = (e >> 16) + ((v_lo >> L) & ((1u << eb) - 1u));
     const uint32_t o2 = L + eb;  // <= 20
     const uint32_t dv = zh_alignbit(v_hi, v_lo, o2);
-    uint32_t de = s_dst[dv & ((1u << kDistBits) - 1u)];
-    if (de & 0x400u) de = s_dst[(de >> 16) + ((dv >> kDistBits) & ((1u << (de & 15u)) - 1u))];
-    if (de == 0) {
-      const uint32_t k = __brev(dv) >> 16;
-      uint32_t cl = kDistBits + 1;
-      while (cl < 16 && k >= s_tab_dist.max_codes[cl]) cl++;
-      uint32_t sym = 0xffffu;
-      if (cl < 16)
-        sym = s_val_dist[((k >> (16 - cl)) - s_tab_dist.first_code[cl] + s_tab_dist.first_symbol[cl]) & 0xffffu];
-      de = dist_entry(sym, cl < 16 ? cl : 0);
-    }
+    const uint32_t de = dist_rare(s_dst[dv & ((1u << kDistBits) - 1u)], dv);
     if (((de >> 8) & 3u) != kKindBase) {  // inflate.nim:211-213
       *kind = (uint32_t)ZH_ERR_INVALID_BUFFER;
       *rec = 0;
@@ -265,35 +261,6 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
     *kind = 0;
     *rec = length | (dist << 16);
     return o3 + deb;
-  };
-  // the rare litlen entries (not "plain", zh_inflate_tables.h): a link to a second-level table, or an empty entry --
-  // inflate.nim:67-91 decodeSymbolSlow: longer than the tables reach, or unassigned.  What comes back is a plain
-  // entry, end of block, or an invalid symbol (kKindBad).
-  auto lit_rare = [&](uint32_t e, uint32_t v_lo) -> uint32_t {
-    if (e & 0x400u) e = s_lit[(e >> 16) + ((v_lo >> kLitBits) & ((1u << (e & 15u)) - 1u))];
-    if (e == 0) {
-      const uint32_t k = __brev(v_lo) >> 16;
-      uint32_t cl = kLitBits + 1;
-      while (cl < 16 && k >= s_tab_lit.max_codes[cl]) cl++;
-      uint32_t sym = 0xffffu;
-      if (cl < 16)
-        sym = s_val_lit[((k >> (16 - cl)) - s_tab_lit.first_code[cl] + s_tab_lit.first_symbol[cl]) & 0xffffu];
-      e = litlen_entry(sym, cl < 16 ? cl : 0);
-    }
-    return e;
-  };
-  auto dist_rare = [&](uint32_t de, uint32_t dv) -> uint32_t {
-    if (de & 0x400u) de = s_dst[(de >> 16) + ((dv >> kDistBits) & ((1u << (de & 15u)) - 1u))];
-    if (de == 0) {
-      const uint32_t k = __brev(dv) >> 16;
-      uint32_t cl = kDistBits + 1;
-      while (cl < 16 && k >= s_tab_dist.max_codes[cl]) cl++;
-      uint32_t sym = 0xffffu;
-      if (cl < 16)
-        sym = s_val_dist[((k >> (16 - cl)) - s_tab_dist.first_code[cl] + s_tab_dist.first_symbol[cl]) & 0xffffu];
-      de = dist_entry(sym, cl < 16 ? cl : 0);
-    }
-    return de;
   };
   // tokens from p up to the first token start at or behind `limit`; `end_rel`: the input's end.
   // The loop every pass of the kernel lives in (run-up, turns, writing pass), so it is written for the instructions it
@@ -389,11 +356,10 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
     return r;
   };
 
-  // the block header at `pos`: staged, then read by wave 0 like the serial kernel does; leaves the
-  // tables in LDS and the s_c_* words
+  // the block header at `pos`: staged, then read by wave 0 with BlockHeaderReader (zh_inflate_header.h); leaves
+  // the tables in LDS and the s_c_* words
   uint32_t hdr_st = 0;  // the header's status (the same in every thread)
   auto parse_header = [&]() {
-    // ---- block header: staged, then read by wave 0 like the serial kernel does ----
     const uint64_t hbase = pos >> 5;  // dword of the header's first bit
     KPROF_MARK(4);
     __syncthreads();
@@ -402,138 +368,35 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
     KPROF_HDR_MARK(1);  // (-DZH_KPROF_HDR: the header's phases in slots 1 / 3 / 0 -- staged, lengths read, tables built)
     if (tid < 64) {
       uint64_t bp = pos & 31u;  // relative to hbase * 32
-      uint64_t hb = 0;
-      uint32_t hc = 0;
-      int hst = ZH_OK;
-      auto fetch = [&]() -> uint64_t {
-        const uint32_t wi = (uint32_t)(bp >> 5), sh = (uint32_t)bp & 31u;
+      auto fetch = [&](uint64_t at) -> uint64_t {
+        const uint32_t wi = (uint32_t)(at >> 5), sh = (uint32_t)at & 31u;
         const uint32_t d0 = zh_bcast(s_in[wi]), d1 = zh_bcast(s_in[wi + 1u]), d2 = zh_bcast(s_in[wi + 2u]);
         return (uint64_t)zh_alignbit(d1, d0, sh) | ((uint64_t)zh_alignbit(d2, d1, sh) << 32);
       };
-      auto need = [&]() {
-        if (hc < 32u) {
-          hb = fetch();
-          hc = 64;
-        }
-      };
-      auto take = [&](uint32_t nbits) -> uint32_t {
-        const uint32_t v = (uint32_t)hb & ((1u << nbits) - 1u);
-        hb >>= nbits;
-        hc -= nbits;
-        bp += nbits;
-        return v;
-      };
-      auto past_end = [&]() -> bool { return hbase * 32 + bp > end * 8; };
-      auto decode_slow = [&](uint32_t bits, uint32_t lut_bits, const HuffTab* tab, const uint16_t* values,
-                             uint32_t* nb) -> uint32_t {
-        const uint32_t k = __brev(bits) >> 16;
-        uint32_t cl = lut_bits + 1;
-        while (cl < 16 && k >= zh_bcast(tab->max_codes[cl])) cl++;
-        *nb = 0;
-        if (cl >= 16) return 0xffffu;
-        const uint32_t id = ((k >> (16 - cl)) - zh_bcast(tab->first_code[cl]) +
-                             zh_bcast(tab->first_symbol[cl])) & 0xffffu;
-        *nb = cl;
-        return zh_bcast(values[id]);
-      };
-      need();
-      const uint32_t bfinal = take(1), btype = take(2);
-      uint32_t stored_len = 0;
-      if (btype == 0) {  // inflate.nim:252-266 inflateNoCompression
-        bp = ((hbase * 32 + bp + 7u) & ~(uint64_t)7) - hbase * 32;
-        hc = 0;
-        need();
-        const uint32_t len = take(16), nlen = take(16);
-        if (len + nlen != 65535u) hst = ZH_ERR_INVALID_BUFFER;
-        else if (((hbase * 32 + bp) >> 3) + len > end) hst = ZH_ERR_END_OF_BUFFER;
-        stored_len = len;
-      } else if (btype == 3) {
-        hst = ZH_ERR_BLOCK_HEADER;
-      } else {
-        uint32_t hlit = 288, hdist = 30;
-        if (btype == 1) {  // fixed codes, inflate.nim:111-113
-          zh_wave_sync();
-          for (uint32_t s = lane; s < 288; s += 64) s_lens[s] = (uint8_t)(s <= 143 ? 8 : s <= 255 ? 9 : s <= 279 ? 7 : 8);
-          if (lane < 30) s_lens[288 + lane] = 5;
-        } else {  // dynamic header, inflate.nim:115-171
-          hlit = take(5) + 257;
-          hdist = take(5) + 1;
-          const uint32_t hclen = take(4) + 4;
-          if (hlit > 286 || hdist > 30) hst = ZH_ERR_INVALID_BUFFER;
-          // the code lengths by the whole wave (zh_inflate_tables.h); anything but a clean header comes back as 0
-          // and is read again by the serial reader below, which raises the reference's error for it
-          uint32_t fast_q = 0;
-          if (hst == ZH_OK && !kSerialHeader)
-            fast_q = code_lengths_wave(s_in, (uint32_t)bp, hlit, hdist, hclen, end * 8 > hbase * 32 ? end * 8 - hbase * 32 : 0,
-                                       s_lens, reinterpret_cast<uint8_t*>(s_dst));
+      BlockHeaderReader hdr(fetch, bp, hbase * 32, end);
+      int hst = hdr.fields();
+      // a dynamic header's code lengths by the whole wave (code_lengths_wave); anything but a clean header comes
+      // back as 0 and is read again by the serial reader, which raises the reference's error for it
+      uint32_t fast_q = 0;
+      if (hst == ZH_OK && hdr.btype == 2u) {
+        if (!kSerialHeader)
+          fast_q = code_lengths_wave(s_in, (uint32_t)bp, hdr.hlit, hdr.hdist, hdr.hclen, end * 8 > hbase * 32 ? end * 8 - hbase * 32 : 0,
+                                     s_lens, reinterpret_cast<uint8_t*>(s_dst));
 #ifdef ZH_EMU
-          if (lane == 0 && hst == ZH_OK && getenv("ZH_DBG_HDR")) fprintf(stderr, "dynamic header: %s\n", fast_q ? "wave" : "serial reader");
+        if (lane == 0 && getenv("ZH_DBG_HDR")) fprintf(stderr, "dynamic header: %s\n", fast_q ? "wave" : "serial reader");
 #endif
-          if (fast_q) {
-            bp = fast_q;
-            hc = 0;
-          }
-          if (hst == ZH_OK && !fast_q) {
-            zh_wave_sync();
-            if (lane < 20) s_lens[lane] = 0;
-            zh_wave_sync();
-            for (uint32_t i = 0; i < hclen; i++) {
-              need();
-              const uint32_t v = take(3);
-              if (lane == 0) s_lens[c_clcl_order[i]] = (uint8_t)v;
-            }
-            hst = build_table(s_lens, 19, s_dst, 7, 2, &s_tab_cl, s_val_cl, s_cnt);
-          }
-          if (hst == ZH_OK && !fast_q) {
-            uint32_t i = 0;
-            const uint32_t total = hlit + hdist;
-            uint32_t prev = 0;
-            while (i != total) {
-              need();
-              uint32_t sym;
-              const uint32_t e = zh_bcast(s_dst[(uint32_t)hb & 127u]);
-              if (e) {
-                take(e & 15u);
-                sym = e >> 16;
-              } else {
-                uint32_t nb;
-                sym = decode_slow((uint32_t)hb, 7, &s_tab_cl, s_val_cl, &nb);
-                take(nb);
-              }
-              if (past_end()) { hst = ZH_ERR_END_OF_BUFFER; break; }
-              if (sym <= 15) {
-                if (lane == 0) s_lens[i] = (uint8_t)sym;
-                prev = sym;
-                i++;
-              } else if (sym == 16) {
-                if (i == 0) { hst = ZH_ERR_INVALID_BUFFER; break; }
-                const uint32_t rep = take(2) + 3;
-                if (i + rep > 320) { hst = ZH_ERR_INVALID_BUFFER; break; }
-                if (lane < rep) s_lens[i + lane] = (uint8_t)prev;
-                i += rep;
-              } else if (sym == 17 || sym == 18) {
-                const uint32_t rep = sym == 17 ? take(3) + 3 : take(7) + 11;
-                for (uint32_t j = lane; j < rep && i + j < 320 + 16; j += 64) s_lens[i + j] = 0;
-                prev = 0;
-                i += rep;
-              } else {
-                hst = ZH_ERR_INVALID_SYMBOL;
-                break;
-              }
-              if (i > total) { hst = ZH_ERR_INVALID_BUFFER; break; }
-            }
-          }
-        }
-        if (lane == 0) {
-          s_c_hlit = hlit;
-          s_c_hdist = hdist;
-        }
+        if (fast_q) bp = fast_q;
+      }
+      if (hst == ZH_OK && hdr.btype != 0u && !fast_q) hst = hdr.code_lengths(s_lens, s_dst, &s_tab_cl, s_val_cl, s_cnt);
+      if (lane == 0 && (hdr.btype == 1u || hdr.btype == 2u)) {
+        s_c_hlit = hdr.hlit;
+        s_c_hdist = hdr.hdist;
       }
       if (lane == 0) {
-        s_c_btype = btype;
-        s_c_final = bfinal;
+        s_c_btype = hdr.btype;
+        s_c_final = hdr.bfinal;
         s_c_st = (uint32_t)hst;
-        s_c_stored_len = stored_len;
+        s_c_stored_len = hdr.stored_len;
         s_c_pos = hbase * 32 + bp;  // behind the header (stored: the first raw byte)
       }
     }

@@ -386,95 +386,5 @@ __device__ __noinline__ int build_tables_wg(const uint8_t* lit_lens, uint32_t hl
   return ZH_OK;
 }
 
-// The code lengths of a dynamic header (inflate.nim:115-171) by ONE WAVE instead of one lane's scalar chain:
-// the 64 lanes decode the code-length symbols that start at 64 consecutive bit positions, a wave-uniform walk
-// (one v_readlane a symbol) picks the ones really in the sequence, repeat counts become places by a prefix sum.
-// `hdr`: the header staged in LDS (dwords), bit 0 of hdr[0] = bit 0 of the staged range; `q`: the first bit
-// behind HCLEN; `end_bits`: the input's end in the same bit coordinates.  Fills lens[0 .. hlit + hdist) and
-// returns the bit behind the last symbol -- or 0 where the header is anything but clean (a code-length code
-// that is over-subscribed or does not cover what it is asked, a repeat with nothing before it or past the
-// end, input that ends inside): the caller then runs the serial reader, which knows the reference's status
-// for every such case.  `lut8`: 128 bytes of LDS.
-__device__ __noinline__ uint32_t code_lengths_wave(const uint32_t* hdr, uint32_t q, uint32_t hlit, uint32_t hdist, uint32_t hclen,
-                                      uint64_t end_bits, uint8_t* lens, uint8_t* lut8) {
-  const unsigned lane = zh_lane();
-  auto peek = [&](uint32_t at) -> uint32_t { return zh_alignbit(hdr[(at >> 5) + 1u], hdr[at >> 5], at); };
-  // lane s < 19: the length of code-length symbol s; its place in the header is the inverse of c_clcl_order
-  // {3, 17, 15, 13, 11, 9, 7, 5, 4, 6, 8, 10, 12, 14, 16, 18, 0, 1, 2}, five bits a symbol in two constants
-  constexpr uint64_t kPlaceLo = 3ull | 17ull << 5 | 15ull << 10 | 13ull << 15 | 11ull << 20 | 9ull << 25 | 7ull << 30 |
-                                5ull << 35 | 4ull << 40 | 6ull << 45 | 8ull << 50 | 10ull << 55;
-  constexpr uint64_t kPlaceHi = 12ull | 14ull << 5 | 16ull << 10 | 18ull << 15 | 0ull << 20 | 1ull << 25 | 2ull << 30;
-  const uint32_t place = lane < 12u ? (uint32_t)(kPlaceLo >> (5u * lane)) & 31u
-                                    : lane < 19u ? (uint32_t)(kPlaceHi >> (5u * (lane - 12u))) & 31u : 99u;
-  const uint32_t l = place < hclen ? peek(q + 3u * place) & 7u : 0u;
-  q += 3u * hclen;
-  // canonical codes (inflate.nim:29-65): symbols of one length in symbol order; Kraft sum in 1/128ths
-  uint32_t code = 0, next = 0;
-#pragma unroll
-  for (uint32_t k = 1; k <= 7; k++) {
-    const uint64_t m = __ballot(l == k);
-    if (l == k) code = next + (uint32_t)__popcll(m & zh_lanemask_lt());
-    next = (next + (uint32_t)__popcll(m)) << 1;
-  }
-  if (zh_wave_sum(l ? 128u >> l : 0u) > 128u) return 0;  // over-subscribed
-  zh_wave_sync();
-  if (lane < 32u) reinterpret_cast<uint32_t*>(lut8)[lane] = 0;
-  for (uint32_t i = lane; i < (320u + 16u) / 4u; i += 64u) reinterpret_cast<uint32_t*>(lens)[i] = 0;
-  zh_wave_sync();
-  if (l) {
-    const uint32_t rev = __brev(code) >> (32u - l);
-    for (uint32_t e = rev; e < 128u; e += 1u << l) lut8[e] = (uint8_t)(lane | (l << 5));
-  }
-  zh_wave_sync();
-  const uint32_t total = hlit + hdist;
-  uint32_t i = 0, prev = 0;
-  while (i < total) {
-    const uint32_t w = peek(q + lane);  // the symbol that starts at bit q + lane
-    const uint32_t e = lut8[w & 127u], sym = e & 31u, cl = e >> 5;
-    const uint32_t x = w >> cl;
-    uint32_t rep = 1, val = sym, nb = cl;
-    if (sym == 16u) {
-      rep = (x & 3u) + 3u;
-      nb += 2u;
-    } else if (sym == 17u) {
-      rep = (x & 7u) + 3u;
-      nb += 3u;
-      val = 0;
-    } else if (sym == 18u) {
-      rep = (x & 127u) + 11u;
-      nb += 7u;
-      val = 0;
-    }
-    if (cl == 0u) nb = 64u;  // no code here: a walk that comes by ends the fast path
-    uint64_t on = 0;
-    uint32_t pos = 0;
-    while (pos < 64u) {
-      on |= 1ull << pos;
-      pos += (uint32_t)__builtin_amdgcn_readlane((int)nb, (int)pos);
-    }
-    bool mine = (on >> lane) & 1ull;
-    const uint32_t incl = zh_wave_scan(mine ? rep : 0u);
-    const uint32_t at = i + incl - (mine ? rep : 0u);  // index of my first entry
-    if (mine && at >= total) mine = false;             // behind the last length: not part of the header
-    const uint64_t ON = __ballot(mine);                // (bit 0 is set: at = i < total)
-    if (__ballot(mine && (cl == 0u || at + rep > total))) return 0;
-    if (i == 0 && (uint32_t)__builtin_amdgcn_readlane((int)sym, 0) == 16u) return 0;  // nothing to repeat
-    // "previous length" for symbol 16: the nearest symbol before that is not a 16 (17 / 18 leave zero)
-    const uint64_t plain = __ballot(mine && sym != 16u) & zh_lanemask_lt();
-    const uint32_t from = plain ? 63u - (uint32_t)__clzll((long long)plain) : 0u;
-    const uint32_t pv = (uint32_t)__shfl((int)val, (int)from, 64);
-    if (sym == 16u) val = plain ? pv : prev;
-    if (mine && val)  // (zeros are there already; what is left repeats six times at most)
-      for (uint32_t j = 0; j < rep; j++) lens[at + j] = (uint8_t)val;
-    const uint32_t lastl = 63u - (uint32_t)__clzll((long long)ON);
-    i = (uint32_t)__builtin_amdgcn_readlane((int)(at + rep), (int)lastl);
-    prev = (uint32_t)__builtin_amdgcn_readlane((int)val, (int)lastl);
-    q += lastl + (uint32_t)__builtin_amdgcn_readlane((int)nb, (int)lastl);
-  }
-  zh_wave_sync();
-  if ((uint64_t)q > end_bits) return 0;
-  return q;
-}
-
 }  // namespace
 

@@ -9,8 +9,9 @@
 // (tests compare them token for token through zh_debug_tokens).
 //
 // Each wave keeps its u16 hash table (32 KiB, snappy.nim:7) in a pooled, L2/MALL-resident slot
-// of HBM scratch and only 7.4 KiB in LDS (per-step slot counters, reused as the coverage bitmap
-// afterwards; the slot-written bitmap; the symbol histograms): 20 waves per CU.  A lone wave runs
+// of HBM scratch and only 4.7 KiB in LDS (one 4 KiB region: the slot-written bitmap and the step's
+// two slot-flag maps while parsing, the coverage bitmap afterwards; the symbol histograms, two
+// counts a word): LDS alone would allow 32 waves per CU, the launch runs 16.  A lone wave runs
 // at well under a tenth of its SIMD's issue rate (every step is a chain of dependent round
 // trips), so waves per CU, not latency per access, is what buys throughput.  The fragment's own
 // bytes and the candidates' are read through L1/L2 with unaligned 128-bit loads.
@@ -26,9 +27,15 @@
 
 namespace {
 constexpr uint32_t kHashMul = 0x1e35a7bdu;  // snappy.nim:70-71
-// byte-wide per-step slot counters, four to a dword, keyed by the low hash bits (also the size
-// of the coverage bitmap that reuses the array: 1024 words = 32768 bits)
+// the coverage bitmap: 1024 words = 32768 bits, a bit a position of the fragment.  The parse's LDS lies in the same
+// 4 KiB (kBitsWords words of slot-written bits, then two step-flag maps of kFlagWords words each, keyed by the low
+// kFlagBits hash bits); the last 256 words are the bitmap's alone
 constexpr uint32_t kCntWords = 1024;
+constexpr uint32_t kBitsWords = 512, kFlagBits = 12, kFlagWords = (1u << kFlagBits) / 32u;
+static_assert(kBitsWords + 2u * kFlagWords <= kCntWords, "the parse's maps lie inside the coverage bitmap's words");
+// the symbol histograms in LDS: two 16-bit counts a word (symbol i: word i >> 1, half i & 1)
+constexpr uint32_t kHistWords = ZH_HIST_STRIDE / 2;
+static_assert(ZH_HIST_STRIDE % 2 == 0, "packed pairs");
 // 16 bytes at any byte address (gfx950 global loads need no alignment)
 struct __attribute__((packed)) Bytes16 {
   uint32_t x, y, z, w;
@@ -47,15 +54,26 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
                                                          uint32_t* __restrict__ next_frag,
                                                          const uint32_t* __restrict__ order,
                                                          uint32_t* __restrict__ cost, uint32_t ticket_base) {
-  __shared__ uint32_t s_hist[ZH_HIST_STRIDE];
-  // parse: 4096 byte-wide counters (4 per dword) of the probes per table slot in one step,
-  // all zero between steps; afterwards the first 4 KiB are the coverage bitmap (bit p set:
-  // byte p lies inside a match, behind its first byte)
+  // LDS a wave, as declared: 640 + 4096 + 4 = 4740 B pooled, + 32 768 = 37 508 B with the table (what the compiler
+  // reports, -Rpass-analysis=kernel-resource-usage: 4740 and 37 508 bytes/workgroup).  The hardware hands LDS out in
+  // blocks: with 512 B a block that is 5120 and 37 888, with 1280 B 5120 and 38 400 -- and 16 x 5120 + 2 x 38 400 =
+  // 158 720 of a CU's 163 840 B either way: sixteen pooled waves and two LDS-table waves a CU.
+  //
+  // The histograms, two counts a word.  No half can carry into the other: a fragment is 32 768 bytes at most, so a
+  // literal's count is at most 32 768 = 0x8000, and a match is four bytes at least, so a length or distance symbol's
+  // is at most 8192 -- both below 65 536 (and hist_out is uint16_t for the same reason).
+  __shared__ uint32_t s_hist[kHistWords];
+  // One 4 KiB region for both phases, never live together:
+  //   parse: s_bits (words 0 .. 511), one bit per table slot: written while parsing this fragment.  A slot that was
+  //     not holds the reference's initial zero, which needs no load -- and the pooled table needs no clearing;
+  //     s_seen / s_dup (128 words each behind it): one bit per value of the low 12 hash bits, "a valid lane of this
+  //     step has it" / "a second one has", all zero between steps;
+  //   afterwards: all of it is the coverage bitmap (bit p set: byte p lies inside a match, behind its first byte)
   __shared__ uint32_t s_scr[kCntWords];
-  // one bit per table slot: written while parsing this fragment.  A slot that was not holds the
-  // reference's initial zero, which needs no load -- and the pooled table needs no clearing.
-  __shared__ uint32_t s_bits[512];
   __shared__ uint32_t s_nmatch;
+  uint32_t* const s_bits = s_scr;
+  uint32_t* const s_seen = s_scr + kBitsWords;
+  uint32_t* const s_dup = s_seen + kFlagWords;
   uint32_t* const s_cover = s_scr;
 
   const unsigned lane = zh_lane();
@@ -91,9 +109,6 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
     const uint32_t q = p + mis, i = q >> 2;
     return __builtin_amdgcn_alignbyte(dw(i + 1), dw(i), q);
   };
-  for (uint32_t i = lane; i < ZH_HIST_STRIDE; i += 64) s_hist[i] = 0;
-  for (uint32_t i = lane; i < kCntWords; i += 64) s_scr[i] = 0;
-
   uint32_t table_size = 256, shift = 24;  // snappy.nim:24-29
   while (table_size < 16384u && table_size < n) {
     table_size <<= 1;
@@ -117,7 +132,8 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
   // candidate's bytes (half of the non-matching gathers, which are what this kernel's memory
   // traffic is made of).  "Empty" is the reference's zero = position 0, with position 0's tag (e0).
   const uint32_t e0 = (!huffman_only && n >= 4) ? (((ld32(0) * kHashMul) >> 17) & 1u) << 15 : 0u;
-  for (uint32_t i = lane; i < 512; i += 64) s_bits[i] = 0;
+  // (what the parse reads: the slot bits and the flag maps; the words behind them hold the last fragment's bitmap)
+  for (uint32_t i = lane; i < kBitsWords + 2u * kFlagWords; i += 64) s_scr[i] = 0;
   zh_wave_sync();
   KPROF_MARK(0);
 
@@ -177,24 +193,27 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
         const uint32_t a0 = av.x, a1 = av.y, a2 = av.z, a3 = av.w;
         const uint32_t hp = a0 * kHashMul;
         const uint32_t h = hp >> shift, tag = (hp >> 17) & 1u;
-        // round trip 2: the table slot; every lane also ticks a counter of its (folded) hash,
-        // read back together with the candidate bytes
+        // round trip 2: the table slot; every lane also flags its (folded) hash in `seen`, and behind the candidates'
+        // gather in `dup` if another lane had flagged it: of k >= 2 lanes with one folded hash exactly one finds the
+        // bit clear, in whatever order the LDS serves them, so `dup` holds the bit iff k >= 2.  It is read back while
+        // the candidate bytes are on their way
         uint32_t oldw = e0;
         if (valid && ((s_bits[h >> 5] >> (h & 31u)) & 1u))
           oldw = kLdsTable ? (uint32_t)s_table[h]
                            : (uint32_t)__hip_atomic_load(s_table + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t old = oldw & 0x7fffu;
         const bool fetch = valid && (oldw >> 15) == tag;  // equal bytes have equal tags
-        const uint32_t ck = (h & (kCntWords * 4u - 1u)) >> 2, cs = (h & 3u) * 8u;
-        if (valid) atomicAdd(&s_scr[ck], 1u << cs);
-        zh_wave_sync();  // (orders the counter traffic between lanes; emits nothing)
+        const uint32_t ck = (h & ((1u << kFlagBits) - 1u)) >> 5, cb = 1u << (h & 31u);
+        const uint32_t seen_before = valid ? atomicOr(&s_seen[ck], cb) : 0u;
         // round trip 3: 16 bytes at the candidate the table held when the step began -- one
         // scattered 128-bit load per lane (one L1 tag lookup instead of five)
         Bytes16 qv = {0, 0, 0, 0};
         if (fetch) qv = *reinterpret_cast<const Bytes16*>(src + old);
-        const uint32_t cnt = valid ? (s_scr[ck] >> cs) & 255u : 0u;
+        if (seen_before & cb) atomicOr(&s_dup[ck], cb);
+        zh_wave_sync();  // (orders the flag traffic between lanes; emits nothing)
+        const bool flagged = valid && (s_dup[ck] & cb);
         zh_wave_sync();
-        if (valid) s_scr[ck] = 0;
+        if (valid) s_seen[ck] = s_dup[ck] = 0;
         const uint32_t x0 = fetch ? a0 ^ qv.x : 1u;
         const uint32_t x1 = a1 ^ qv.y;
         const uint32_t x2 = a2 ^ qv.z;
@@ -211,8 +230,8 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
         const uint64_t V = __ballot(valid);  // a prefix of the lanes (pos + step is monotone)
         const uint64_t H = __ballot(valid && x0 == 0);
         // lanes that may share their table slot with another lane of this step (a superset:
-        // the counters see 12 of the 14 hash bits); the general walk below sorts them out exactly
-        const uint64_t C = __ballot(cnt > 1u);
+        // the flags see 12 of the 14 hash bits); the general walk below sorts them out exactly
+        const uint64_t C = __ballot(flagged);
         // Cw: the flagged lanes that really have an earlier lane with their hash in this step --
         // only those can have a candidate other than `old` (the first lane of a group, and lanes
         // flagged by the folded counter alone, walk like any other lane)
@@ -517,6 +536,10 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
   zh_wave_sync();
   KPROF_MARK(3);
   const uint32_t nmatch = s_nmatch;
+  // the parse is over: its region becomes the (empty) coverage bitmap, and the histograms start at zero
+  for (uint32_t i = lane; i < kCntWords; i += 64) s_scr[i] = 0;
+  for (uint32_t i = lane; i < kHistWords; i += 64) s_hist[i] = 0;
+  zh_wave_sync();
 
   // ---- match histograms, and the coverage bitmap as the places where "inside a match, behind its first byte" flips:
   // the match's second byte and the byte behind its last (a match is four bytes at least: no two flips share a bit).
@@ -524,6 +547,7 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
   // (zh_emit_kernel: it gets the bitmap, a.f_cover, instead of filing the match list a second time).
   // The next 64 matches' fields are asked for before these are filed (clamped, unconditional loads) ----
   uint32_t extra_bits = 0, covered = 0;
+  auto hist_add = [&](uint32_t sym) { atomicAdd(&s_hist[sym >> 1], 1u << (16u * (sym & 1u))); };
   {
     const uint32_t mlast = nmatch ? nmatch - 1u : 0u;
     auto at = [&](uint32_t m) { return m < nmatch ? m : mlast; };
@@ -535,8 +559,8 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
       oq = m_off[at(m + 64u)];
       if (m < nmatch) {
         const uint32_t li = zh_len_code(l), di = zh_dist_code(o);
-        atomicAdd(&s_hist[257 + li], 1u);
-        atomicAdd(&s_hist[ZH_NUM_LITLEN + di], 1u);
+        hist_add(257u + li);
+        hist_add(ZH_NUM_LITLEN + di);
         extra_bits += zh_len_extra_bits(li) + zh_dist_extra_bits(di);
         covered += l;
         atomicXor(&s_cover[(p + 1u) >> 5], 1u << ((p + 1u) & 31u));
@@ -585,7 +609,7 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
         const uint32_t notlit = cov | (cov >> 1);
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++)
-          if (p + k < n && !((notlit >> k) & 1u)) atomicAdd(&s_hist[(wq[u] >> (8u * k)) & 255u], 1u);
+          if (p + k < n && !((notlit >> k) & 1u)) hist_add((wq[u] >> (8u * k)) & 255u);
       }
     }
   }
@@ -594,7 +618,7 @@ __global__ __launch_bounds__(64) void zh_l1_match_kernel(const uint8_t* __restri
   zh_wave_sync();
 
   uint16_t* hist_out = a.f_hist + (size_t)f * ZH_HIST_STRIDE;
-  for (uint32_t i = lane; i < ZH_HIST_STRIDE; i += 64) hist_out[i] = (uint16_t)s_hist[i];
+  for (uint32_t i = lane; i < ZH_HIST_STRIDE; i += 64) hist_out[i] = (uint16_t)(s_hist[i >> 1] >> (16u * (i & 1u)));
   if (lane == 0) {
     a.f_nmatch[f] = nmatch;
     a.f_spill[f] = 0;
@@ -730,13 +754,14 @@ uint32_t l1_lds_waves() {
   static const uint32_t waves = [] {
     const char* e = getenv("ZH_L1_LDS_WAVES");
     const long v = e ? atol(e) : -1;
-    return v >= 0 && v <= 1024 ? (uint32_t)v : 256u;
+    return v >= 0 && v <= 1024 ? (uint32_t)v : 512u;
   }();
   return waves;
 }
 }  // namespace
 
-// waves that share the table pool: 19 per CU on 256 CUs, LDS 7.4 KiB each (ZH_L1_SLOTS: tuning override).  The kernel's
+// waves that share the table pool when the launch is the pooled kernel alone: 19 per CU on 256 CUs, LDS 4.7 KiB each
+// (which would allow 32; ZH_L1_SLOTS: tuning override).  The kernel's
 // throughput is the fabric's, not its waves': 4096 .. 5376 of them are within 2 %; three rounds on one box,
 // ms for 4096 x 1 MiB: 4608 waves 63.7, 4864 63.5, 5120 (rounds 2-5) 64.4; one GPU's share (16 384 fragments) the same
 extern "C" uint32_t zh_l1_table_slots(void) { return l1_slots_env() ? (uint32_t)l1_slots_env() : 4864u; }
@@ -751,9 +776,9 @@ __global__ void zh_l1_head_start_kernel() {}
 
 // What a run's launch looks like, and everything in front of it on `stream`: the order and the counter.
 // The mixed launch (`side_ok`: the caller has a second stream for it; batches of at least a fragment a wave): 16 pooled
-// waves a CU instead of 19 -- past 16 the memory system is the limit, DESIGN.md 4.1 -- and in the LDS the other three
-// leave (3 x 7.4 KiB beside 17.5 KiB nobody had) one wave a CU with its table there, 40 KiB, which asks a tenth of
-// the fabric.  A wave's first ticket is its own index, the pooled ones' 0 .. P-1, the others' P .. P+L-1; the counter
+// waves a CU instead of 19 -- past 16 the memory system is the limit, DESIGN.md 4.1 -- and in the LDS they leave
+// (16 x 5 KiB of 160) two waves a CU with their tables there, 37.5 KiB each, which ask a tenth of the fabric.
+// A wave's first ticket is its own index, the pooled ones' 0 .. P-1, the others' P .. P+L-1; the counter
 // starts behind them and every later ticket is drawn from it by both kernels, first come, first served: neither
 // waits for the other, and an LDS-table wave that finds no room while pooled waves hold the CU only comes later.
 // `cost` / `order` / `hist` (each may be null): this run's cycles a fragment; the order made of LAST run's (built here
@@ -768,7 +793,7 @@ extern "C" ZhL1Launch zh_l1_match_prepare(hipStream_t stream, uint32_t nfrags, u
     return e && strcmp(e, "lds") == 0;
   }();
   if (lds) {
-    l.lds = nfrags < 1024u ? nfrags : 1024u;  // (39.4 KiB of LDS: four waves per CU)
+    l.lds = nfrags < 1024u ? nfrags : 1024u;  // (36.6 KiB of LDS: four waves per CU)
     hipLaunchKernelGGL(zh_l1_set_counter_kernel, dim3(1), dim3(1), 0, stream, next_frag, l.lds);
     return l;
   }
@@ -827,7 +852,9 @@ extern "C" void zh_launch_l1_match(hipStream_t stream, const uint8_t* d_src, ZhC
     // the LDS-table waves start when those retire -- at worst for their first tickets only.  Nothing waits for anything:
     // a few empty launches in front of the pooled kernel merely let the other stream's 256 workgroups go first.
     // Fragments of 131 072 the LDS-table waves took, eight runs each: no such launch 256 (seven times) and 8859; one:
-    // 256 .. 379 six times, 8866, 8883; three: 8890 .. 8968 every time; eight: 8853 .. 8930.  DESIGN.md 4.1)
+    // 256 .. 379 six times, 8866, 8883; three: 8890 .. 8968 every time; eight: 8853 .. 8930.  With 512 such waves:
+    // none 12 386, 512 and six times 16 848 .. 16 945; one: 512 once and 16 859 .. 16 942; three: 16 863 .. 16 955
+    // every time; eight: 16 846 .. 16 957.  DESIGN.md 4.1)
     static const uint32_t head_start = [] {  // (ZH_L1_HEAD_START: measurement)
       const char* e = getenv("ZH_L1_HEAD_START");
       const long v = e ? atol(e) : -1;

@@ -400,6 +400,10 @@ def check_range_shapes(eng):
     assert eng.debug_range_stats()[1:] == (2, 0)
     check_ranges(eng, srcs, images, indexes, [(0, 10, 20), (0, 15, 30)])  # the same member twice: sent once, decoded twice
     assert eng.debug_range_stats()[1:] == (0, 2)
+    # the upload's accounting (check_ranges' bound) where spans merge: neighbours that touch exactly, and the same
+    # offsets asked of two images in alternating order
+    check_ranges(eng, srcs, images, indexes, [(0, 0, RB), (0, RB, RB)], want=[0, 0])
+    check_ranges(eng, srcs, images, indexes, [(1, 100, 50), (0, 100, 50), (1, RB, 10), (0, RB, 10)], want=[0] * 4)
     assert eng.bgzf_read_ranges(images, indexes, []) == ([], [])
 
 

@@ -482,12 +482,7 @@ def check_upload_accounting(eng, make):
     span, and never more spans than ranges."""
     srcs, streams, indexes = format_streams(make)
     lens = [len(x) for x in streams]
-    rng = random.Random(5)
-    for ranges in ([(0, 100, 10)],
-                   [(0, 100, 10), (0, 200, 10)],                      # the same block twice: sent once
-                   [(0, 0, BB), (0, BB, BB)],                         # neighbours: they touch
-                   [(s, rng.randrange(len(srcs[s])), rng.randrange(1, 40000)) for s in (3, 0, 2, 1, 0, 3, 2, 1, 5)],
-                   [(0, 0, 70000), (1, 69999, 1), (4, 0, 1)]):
+    for ranges in accounting_sets(srcs):
         check_call(eng, srcs, streams, indexes, ranges)
         up = eng.debug_range_stats()[0]
         S, U = spans_of(indexes, lens, ranges)
@@ -500,6 +495,81 @@ def check_upload_accounting(eng, make):
     assert S + 64 < len(blob) // 4  # (from the index: a 4 KiB range needs one block of eight, or two)
     check_call(eng, [src], [blob], [idx], ranges)
     assert U <= eng.debug_range_stats()[0] <= S + 64 < len(blob) // 4
+
+
+# ---- the cases as files, for tests/ranges_sanitize_main.cpp ----
+def accounting_sets(srcs):
+    """the five sets of ranges of check_upload_accounting over format_streams()"""
+    rng = random.Random(5)
+    return [[(0, 100, 10)],
+            [(0, 100, 10), (0, 200, 10)],                      # the same block twice: sent once
+            [(0, 0, BB), (0, BB, BB)],                         # neighbours: they touch
+            [(s, rng.randrange(len(srcs[s])), rng.randrange(1, 40000)) for s in (3, 0, 2, 1, 0, 3, 2, 1, 5)],
+            [(0, 0, 70000), (1, 69999, 1), (4, 0, 1)]]
+
+
+def dump(path):
+    """shape_ranges(), the damaged block, the unsound indexes of one stream among three and the five sets of the
+    upload's accounting, streams and indexes from the oracle.  cases.txt: "NAME STREAMS U" a line (U: the union of the
+    spans the call must send, -1: not held against the counter); NAME_<s>.bin / .idx ("BIT_OFF OUT_OFF" a line) / .src
+    per stream; NAME.ranges: "STREAM OFF LEN STATUS" a line -- 0: the slice of .src; -1: a status of the decoder's;
+    else that status.  -> the number of (cases, ranges)"""
+    import os
+    os.makedirs(path)
+
+    def put(name, data):
+        with open(os.path.join(path, name), "wb") as f:
+            f.write(data)
+
+    cases = []  # (name, srcs, streams, indexes, [(stream, off, len, status)], U)
+
+    def add(name, srcs, streams, indexes, ranges, bad=(), bad_status=INVALID_BUFFER, account=False):
+        U = spans_of(indexes, [len(x) for x in streams], ranges)[1] if account else -1
+        cases.append((name, srcs, streams, indexes,
+                      [x + (bad_status if r in bad else OK,) for r, x in enumerate(ranges)], U))
+
+    src = mix(SHAPE_SIZE)
+    blob, idx = make_oracle(src, 1, oracle.dfGzip, BB)
+    add("shapes", [src], [blob], [idx], shape_ranges(), account=True)
+
+    src, blob, idx = seven_blocks(make_oracle)
+    at = (idx[3][0] // 8 + idx[4][0] // 8) // 2
+    damaged = bytearray(blob)
+    damaged[at] ^= 0xff
+    damaged[at + 1] ^= 0xff
+    try:
+        oracle.uncompress(bytes(damaged), oracle.dfGzip)
+        raise AssertionError("the oracle decodes the damaged stream")
+    except oracle.ZippyError:
+        pass
+    ranges = block_ranges(7, len(src))
+    bad = {r for r, x in enumerate(ranges) if touches(x, 3 * BB, 4 * BB, len(src))}
+    assert 3 <= len(bad) < len(ranges)
+    add("damaged", [src], [bytes(damaged)], [idx], ranges, bad, -1)
+
+    srcs = [mix(70000, 1), mix(70000, 2), mix(70000, 3)]
+    made = [make_oracle(x, 1, oracle.dfGzip, BB) for x in srcs]
+    streams = [m[0] for m in made]
+    ranges = [(s, off, n) for off, n in ((0, 70000), (100, 10), (40000, 30000), (70000, 1), (5, 0)) for s in range(3)]
+    good = made[1][1]
+    for k, bad_idx in enumerate(([good[0], good[2], good[1], good[3]], good[:1], [], [(good[0][0], 1)] + good[1:],
+                                 good[:2] + [(8 * len(streams[1]), good[2][1])] + good[3:],
+                                 good[:2] + [(good[2][0], 10 ** 9), (good[3][0], 10 ** 9 + 10)])):
+        add("badindex%d" % k, srcs, streams, [made[0][1], bad_idx, made[2][1]], ranges,
+            {r for r, x in enumerate(ranges) if x[0] == 1})
+
+    srcs, streams, indexes = format_streams(make_oracle)
+    for k, ranges in enumerate(accounting_sets(srcs)):
+        add("accounting%d" % k, srcs, streams, indexes, ranges, account=True)
+
+    for name, srcs, streams, indexes, ranges, U in cases:
+        for s in range(len(streams)):
+            put("%s_%d.bin" % (name, s), streams[s])
+            put("%s_%d.src" % (name, s), srcs[s])
+            put("%s_%d.idx" % (name, s), "".join("%d %d\n" % e for e in indexes[s]).encode())
+        put(name + ".ranges", "".join("%d %d %d %d\n" % x for x in ranges).encode())
+    put("cases.txt", "".join("%s %d %d\n" % (c[0], len(c[2]), c[5]) for c in cases).encode())
+    return len(cases), sum(len(c[4]) for c in cases)
 
 
 # ---- scratch groups ----

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-w"]
 # the files of the batch readers: the calls' own, and the headers that hold what they share
-READER_CODE = ("zh_zip", "zh_tar", "zh_walk", "zh_gather", "zh_host")
+READER_CODE = ("zh_zip", "zh_tar", "zh_walk", "zh_scan", "zh_gather", "zh_host")
 
 
 def _compile(jobs):

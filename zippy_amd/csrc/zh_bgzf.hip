@@ -22,7 +22,13 @@
 // Range reads (zh_bgzf_read_ranges): only the members a range touches go over the link; their headers are parsed
 // again (zh_bgzf_parse_at_kernel), members wholly inside a range decode into its slot, the one or two at its ends
 // into scratch and through zh_launch_range_clip.
+// Shared host code: the upload of the images, the two passes of the scan and the walk's scratch are zh_scan.h's
+// (scan_upload, scan_hits, scan_walk_alloc; zh_zip_read_batch.hip drives the same); pread's arithmetic, the merged
+// spans of a range read's upload, the cut of a clip and the tail that hands results out are zh_range_host.h's
+// (zh_ranges.hip uses the same).  What is BGZF's own stays here: member_at and the kernels built on it, the index's
+// soundness, the members' slots.
 // The host parses no header byte, compares no checksum and writes no byte of an image.
+#include "zh_range_host.h"
 #include "zh_scan.h"
 #include "zh_zip_dev.h"
 
@@ -211,17 +217,6 @@ __global__ __launch_bounds__(256) void zh_bgzf_parse_at_kernel(const uint8_t* __
   recs[m] = rec;
 }
 
-// The images' ranges of records: hits are in image order, so image t's records are those between the ordinals of
-// its first hit and of the next image's (ord[n_hits] = all records)
-__global__ __launch_bounds__(256) void zh_bgzf_rec_ranges_kernel(const uint32_t* __restrict__ ranges, uint32_t n_img,
-                                                                 const uint32_t* __restrict__ ord,
-                                                                 uint32_t* __restrict__ rec_ranges) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_img) return;
-  rec_ranges[2 * t] = ord[ranges[2 * t]];
-  rec_ranges[2 * t + 1] = ord[ranges[2 * t + 1]];
-}
-
 // out[i] = v[0] + .. + v[i - 1] for i in [0, n]: one workgroup, 256 values a step (the values are sizes of members:
 // a step's sum fits 32 bits)
 __global__ __launch_bounds__(256) void zh_bgzf_scan64_kernel(const uint32_t* __restrict__ v, uint32_t n,
@@ -394,8 +389,8 @@ int fetch(zh_ctx* ctx, std::vector<uint8_t>& h, const Arena& ar, size_t from, si
 
 // What the walk over a call's images leaves: the upload, and per image its records in file order.
 struct BgzfWalk {
-  DevBuf d_in, d_imgs, d_rec;
-  std::vector<uint64_t> up_off;
+  ScanUpload S;  // (zh_scan.h)
+  DevBuf d_rec;
   ZhBgzfRec* d_recs = nullptr;
   uint32_t* d_rec_ranges = nullptr;  // [2 * n_img]
   uint32_t n_rec = 0;
@@ -418,62 +413,22 @@ struct BgzfWalk {
   }
 };
 
-// One upload (every image at an 8-byte aligned offset of one allocation with 512 spare bytes), the scan, the walk,
-// the records.  n > 0.
+// The upload and the scan (zh_scan.h), the walk, the records.  n > 0.
 int bgzf_walk(zh_ctx* ctx, Trace& tr, const void* const* images, const size_t* lens, size_t n, BgzfWalk& W) {
-  std::vector<ZhZrImg> imgs(n);
-  std::vector<uint64_t> up_len(n);
-  W.up_off.assign(n, 0);
-  uint64_t up_total = 0, most_nodes = 0, max_chain = 0;
-  for (size_t t = 0; t < n; t++) {
-    imgs[t] = ZhZrImg{up_total, (uint64_t)lens[t]};
-    W.up_off[t] = up_total;
-    up_len[t] = lens[t];
-    up_total += round_up8(lens[t]);
-    most_nodes += lens[t] / 4 + 1;
-    max_chain = std::max<uint64_t>(max_chain, lens[t] / 26 + 1);  // (no member is shorter than 26 bytes)
-  }
-  if (most_nodes >= 0xffffffffull || n >= 0x7fffffffull) return ZH_ERR_ARGUMENT;
-  ZH_HIP(ctx, hipSetDevice(ctx->device));
   int st;
+  ScanUpload& S = W.S;
+  ScanHits H;
+  if ((st = scan_upload(ctx, tr, "bgzf", images, lens, n, 26, S))) return st;  // (no member is shorter than 26 bytes)
+  if ((st = scan_hits<BgzfSignature>(ctx, tr, "bgzf", S, H))) return st;
   hipStream_t s = ctx->stream;
   const dim3 wg(256);
-  const uint32_t n_img = (uint32_t)n;
-  if (dev_alloc(ctx, W.d_in, up_total + 512) != hipSuccess) return ZH_ERR_NOMEM;
-  if (up_total && (st = zhh_upload_slices(ctx, images, W.up_off, up_len, up_total, W.d_in.p))) return st;
-  std::vector<uint64_t> ioff;
-  if ((st = zhh_upload_spans(ctx, {{imgs.data(), n * sizeof(ZhZrImg)}}, W.d_imgs, ioff))) return st;
-  const ZhZrImg* const dimgs = reinterpret_cast<const ZhZrImg*>(W.d_imgs.p);
-  const uint8_t* const in = W.d_in.p;  // (plain pointers: a launch must not take the guard of a buffer along)
-  tr.mark(ctx, "bgzf: upload");
-
-  // the scan
-  const uint64_t scan_bytes = (up_total + 15) & ~(uint64_t)15;
-  const uint64_t n_groups64 = std::max<uint64_t>(1, (scan_bytes + kScanGroupBytes - 1) / kScanGroupBytes);
-  if (n_groups64 >= 0x7fffffffull) return ZH_ERR_ARGUMENT;
-  const uint32_t n_groups = (uint32_t)n_groups64;
-  DevBuf d_sums, d_hits;
-  if (dev_alloc(ctx, d_sums, ((size_t)n_groups + 1) * 4) != hipSuccess) return ZH_ERR_NOMEM;
-  uint32_t* const gsums = reinterpret_cast<uint32_t*>(d_sums.p);
-  hipLaunchKernelGGL((zh_sig_scan_kernel<false, BgzfSignature>), dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs,
-                     n_img, gsums, (uint64_t*)nullptr);
-  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, gsums, n_groups);
-  ZH_HIP(ctx, hipGetLastError());
-  uint32_t n_hits = 0;  // everything behind the scan is sized by the hits there are
-  ZH_HIP(ctx, hipMemcpyAsync(&n_hits, gsums + n_groups, 4, hipMemcpyDeviceToHost, s));
-  ZH_HIP(ctx, hipStreamSynchronize(s));
-  if (dev_alloc(ctx, d_hits, (size_t)n_hits * 8 + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  uint64_t* const hits = reinterpret_cast<uint64_t*>(d_hits.p);
-  if (n_hits)
-    hipLaunchKernelGGL((zh_sig_scan_kernel<true, BgzfSignature>), dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs,
-                       n_img, gsums, hits);
-  tr.mark(ctx, "bgzf: scan");
+  const uint32_t n_img = S.n_img, n_hits = H.n_hits;
+  const uint8_t* const in = S.d_in.p;
+  const ZhZrImg* const dimgs = S.imgs();
+  const uint64_t* const hits = H.hits();
 
   // the walk
-  max_chain = std::min<uint64_t>(max_chain, n_hits);
-  uint32_t rounds = 0;
-  while ((1ull << rounds) < max_chain + 1) rounds++;
-  const uint32_t N = n_hits + n_img;
+  const uint32_t rounds = H.rounds, N = n_hits + n_img;
   int32_t *succ, *start;
   uint32_t* hit_ranges;
   Arena ex;
@@ -481,15 +436,13 @@ int bgzf_walk(zh_ctx* ctx, Trace& tr, const void* const* images, const size_t* l
   ex.add(hit_ranges, (size_t)n_img * 2);
   ex.add(start, n_img);
   Walk w;
-  if ((st = walk_alloc(ctx, w, N, ex.size + 256))) return st;
-  ex.base = w.extra;
-  ex.bind();
+  if ((st = scan_walk_alloc(ctx, S, H, ex, w))) return st;
   uint32_t *const j0 = w.j0, *const mark = w.mark;
   const uint32_t *const ord = w.ord, *const list = w.list;
   const dim3 node_grid((N + 255) / 256), img_grid((n_img + 255) / 256);
-  hipLaunchKernelGGL(zh_bgzf_ranges_kernel, img_grid, wg, 0, s, in, dimgs, n_img, (const uint64_t*)hits, n_hits,
+  hipLaunchKernelGGL(zh_bgzf_ranges_kernel, img_grid, wg, 0, s, in, dimgs, n_img, hits, n_hits,
                      hit_ranges, start);
-  hipLaunchKernelGGL(zh_bgzf_next_kernel, node_grid, wg, 0, s, in, dimgs, n_img, (const uint64_t*)hits, n_hits,
+  hipLaunchKernelGGL(zh_bgzf_next_kernel, node_grid, wg, 0, s, in, dimgs, n_img, hits, n_hits,
                      (const uint32_t*)hit_ranges, N, j0, mark, succ);
   walk_double(w, rounds, s);
   walk_scan(w, s);
@@ -515,9 +468,9 @@ int bgzf_walk(zh_ctx* ctx, Trace& tr, const void* const* images, const size_t* l
   uint32_t* const d_rr = W.d_rec_ranges;
   const dim3 rec_grid((n_rec + 255) / 256);
   if (n_rec)
-    hipLaunchKernelGGL(zh_bgzf_parse_kernel, rec_grid, wg, 0, s, in, dimgs, n_img, (const uint64_t*)hits, list,
+    hipLaunchKernelGGL(zh_bgzf_parse_kernel, rec_grid, wg, 0, s, in, dimgs, n_img, hits, list,
                        (const int32_t*)succ, n_rec, d_recs, d_isz);
-  hipLaunchKernelGGL(zh_bgzf_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord, d_rr);
+  hipLaunchKernelGGL(zh_walk_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord, d_rr);
   hipLaunchKernelGGL(zh_bgzf_scan64_kernel, dim3(1), wg, 0, s, (const uint32_t*)d_isz, n_rec, d_usum);
   if (n_rec)
     hipLaunchKernelGGL(zh_bgzf_uoff_kernel, rec_grid, wg, 0, s, dimgs, n_img, (const uint32_t*)d_rr,
@@ -784,7 +737,7 @@ extern "C" int zh_bgzf_read_batch(zh_ctx* ctx, const void* const* images, const 
       const ZhBgzfRec& m = W.recs[r];
       if (m.status != ZH_OK) continue;
       pidx[r] = (uint32_t)p_soff.size();
-      p_soff.push_back(W.up_off[t] + m.cdata_off);
+      p_soff.push_back(W.S.up_off[t] + m.cdata_off);
       p_slen.push_back(m.cdata_len);
       p_doff.push_back(aoff[t] + m.uoff);
       p_dcap.push_back(m.isize);
@@ -809,7 +762,7 @@ extern "C" int zh_bgzf_read_batch(zh_ctx* ctx, const void* const* images, const 
   ZH_HIP(ctx, ar.upload(s));
   ZH_HIP(ctx, hipStreamSynchronize(s));  // (pidx is the scope's)
   PlanGuard pg;
-  if ((st = decode_and_verify(ctx, W.d_in.p, d_out.p, p_soff, p_slen, p_doff, p_dcap, W.d_recs, d_pidx, n_rec, d_est, pg)))
+  if ((st = decode_and_verify(ctx, W.S.d_in.p, d_out.p, p_soff, p_slen, p_doff, p_dcap, W.d_recs, d_pidx, n_rec, d_est, pg)))
     return st;
   const uint32_t* const d_rr = W.d_rec_ranges;  // (a plain pointer: a launch must not take the walk's buffers along)
   hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), dim3(256), 0, s, d_rr, (const int32_t*)d_est, (const uint8_t*)nullptr, d_bad, d_any);
@@ -821,20 +774,10 @@ extern "C" int zh_bgzf_read_batch(zh_ctx* ctx, const void* const* images, const 
   tr.mark(ctx, "bgzf read: decode + verify");
 
   std::vector<int32_t> ist(n);
-  std::vector<char> take(n);
-  for (size_t t = 0; t < n; t++) {
+  for (size_t t = 0; t < n; t++)
     ist[t] = W.start[t] != ZH_OK ? W.start[t] : bad[t] != kNone ? est[bad[t]] : (int32_t)ZH_OK;
-    take[t] = ist[t] == ZH_OK;
-  }
-  if ((st = zhh_download(ctx, d_out.p, n, aoff, alen, take, dsts, dst_lens, ist.data()))) {
-    for (size_t t = 0; t < n; t++) free(dsts[t]);
-    clear_outputs(dsts, dst_lens, statuses, n);
-    return st;
-  }
-  for (size_t t = 0; t < n; t++) {
-    statuses[t] = ist[t];
-    if (has_eof) has_eof[t] = W.has_eof(t);
-  }
+  if ((st = hand_out(ctx, d_out.p, aoff, alen, ist, dsts, dst_lens, statuses))) return st;
+  for (size_t t = 0; has_eof && t < n; t++) has_eof[t] = W.has_eof(t);
   tr.mark(ctx, "bgzf read: download");
   return ZH_OK;
 }
@@ -843,12 +786,6 @@ extern "C" int zh_bgzf_read_batch(zh_ctx* ctx, const void* const* images, const 
 // range reads
 // ---------------------------------------------------------------------------
 namespace {
-
-struct BgzfGeo {
-  int32_t fixed = ZH_OK;
-  uint64_t off = 0, end = 0;  // clipped
-  size_t k0 = 1, k1 = 0;      // members of the image's own list (none: k0 > k1)
-};
 
 // What can be said of an index without looking at the image: at least the closing entry, entry 0 at byte 0, neither
 // offset ever falling, no member of more than 65536 bytes, nothing beyond the image
@@ -871,79 +808,35 @@ extern "C" int zh_bgzf_read_ranges(zh_ctx* ctx, const void* const* images, const
   if (!ctx || (n_images && (!images || !lens)) || (n_ranges && (!dsts || !dst_lens || !statuses))) return ZH_ERR_ARGUMENT;
   clear_outputs(dsts, dst_lens, statuses, n_ranges);
   if (const int e = images_there(images, lens, n_images)) return e;
-  if (n_ranges && (!range_image || !range_off || !range_len)) return ZH_ERR_ARGUMENT;
-  if (n_images && !first) return ZH_ERR_ARGUMENT;
-  for (size_t t = 0; t < n_images; t++)
-    if (first[t + 1] < first[t]) return ZH_ERR_ARGUMENT;
-  if (n_images && first[n_images] > first[0] && !index) return ZH_ERR_ARGUMENT;
-  for (size_t r = 0; r < n_ranges; r++)
-    if (range_image[r] >= n_images) return ZH_ERR_ARGUMENT;
-  if (!n_ranges) return ZH_OK;
   if (n_ranges > 0x7fffffffull) return ZH_ERR_ARGUMENT;
 
-  // ---- 1. pread's arithmetic and the binary search ----
-  std::vector<signed char> ok(n_images, -1);  // (checked when a range first asks)
-  std::vector<BgzfGeo> geo(n_ranges);
-  for (size_t r = 0; r < n_ranges; r++) {
-    const size_t t = (size_t)range_image[r];
-    const zh_bgzf_entry* e = index + first[t];
-    const size_t ne = first[t + 1] - first[t];
-    if (ok[t] < 0) ok[t] = bgzf_index_sound(e, ne, lens[t]) ? 1 : 0;
-    BgzfGeo& g = geo[r];
-    if (!ok[t]) {
-      g.fixed = ZH_ERR_INVALID_BUFFER;
-      continue;
-    }
-    const uint64_t total = e[ne - 1].uoff;
-    if (range_off[r] >= total || !range_len[r]) continue;
-    g.off = range_off[r];
-    g.end = range_len[r] > total - range_off[r] ? total : range_off[r] + range_len[r];  // (off + len may not fit 64 bits)
-    auto holds = [&](uint64_t byte) {  // the member k with uoff[k] <= byte < uoff[k + 1]
-      return (size_t)(std::upper_bound(e, e + ne, byte, [](uint64_t v, const zh_bgzf_entry& x) { return v < x.uoff; }) - e) - 1;
-    };
-    g.k0 = holds(g.off);
-    g.k1 = holds(g.end - 1);
-  }
+  // ---- 1. pread's arithmetic and the binary search (zh_range_host.h) ----
+  std::vector<RangeGeo> geo;
+  if (const int e = range_geometry(
+          n_images, index, first, n_ranges, range_image, range_off, range_len,
+          [&](size_t t, const zh_bgzf_entry* e, size_t ne) { return bgzf_index_sound(e, ne, lens[t]); },
+          [](const zh_bgzf_entry& x) { return x.uoff; }, geo))
+    return e;
+  if (!n_ranges) return ZH_OK;
   Trace tr;
 
   // ---- 2. the spans [coff[k0], coff[k1 + 1]), merged image by image; one upload ----
-  struct Span {
-    uint64_t image, lo, hi, dev;
-  };
-  std::vector<Span> spans;
+  RangeSpans up;
   for (size_t r = 0; r < n_ranges; r++) {
-    const BgzfGeo& q = geo[r];
+    const RangeGeo& q = geo[r];
     if (q.fixed != ZH_OK || q.k0 > q.k1) continue;
     const zh_bgzf_entry* e = index + first[range_image[r]];
-    spans.push_back(Span{range_image[r], e[q.k0].coff, e[q.k1 + 1].coff, 0});
+    up.add(range_image[r], e[q.k0].coff, e[q.k1 + 1].coff);
   }
-  std::sort(spans.begin(), spans.end(),
-            [](const Span& a, const Span& b) { return a.image != b.image ? a.image < b.image : a.lo < b.lo; });
-  size_t ns = 0;
-  for (size_t i = 0; i < spans.size(); i++) {
-    if (ns && spans[ns - 1].image == spans[i].image && spans[i].lo <= spans[ns - 1].hi)
-      spans[ns - 1].hi = std::max(spans[ns - 1].hi, spans[i].hi);
-    else
-      spans[ns++] = spans[i];
-  }
-  spans.resize(ns);
-  std::vector<const void*> sp(ns);
-  std::vector<uint64_t> soff(ns), slen(ns);
-  uint64_t up_total = 0;
-  for (size_t i = 0; i < ns; i++) {
-    up_total = (up_total + 15) & ~(uint64_t)15;
-    spans[i].dev = soff[i] = up_total;
-    slen[i] = spans[i].hi - spans[i].lo;
-    sp[i] = (const uint8_t*)images[spans[i].image] + spans[i].lo;
-    up_total += slen[i];
-  }
+  up.place(images);
+  const uint64_t up_total = up.up_total;
   ZH_HIP(ctx, hipSetDevice(ctx->device));
   int st;
   hipStream_t s = ctx->stream;
   const dim3 wg(256);
   DevBuf d_src;
   if (dev_alloc(ctx, d_src, up_total + 512) != hipSuccess) return ZH_ERR_NOMEM;
-  if ((st = zhh_upload_slices(ctx, sp.data(), soff, slen, up_total, d_src.p))) return st;
+  if ((st = zhh_upload_slices(ctx, up.sp.data(), up.soff, up.slen, up_total, d_src.p))) return st;
   tr.mark(ctx, "bgzf ranges: upload");
 
   // ---- 3. the touched members: where they are in the upload, what the index promises; slots, scratch, clips ----
@@ -959,16 +852,12 @@ extern "C" int zh_bgzf_read_ranges(zh_ctx* ctx, const void* const* images, const
   }
   const uint64_t scratch_base = dst_total;
   for (size_t r = 0; r < n_ranges; r++) {
-    const BgzfGeo& q = geo[r];
+    const RangeGeo& q = geo[r];
     m_ranges[2 * r] = m_ranges[2 * r + 1] = (uint32_t)m_at.size();
     if (q.fixed != ZH_OK || q.k0 > q.k1) continue;
     const uint64_t t = range_image[r];
     const zh_bgzf_entry* e = index + first[t];
-    // the range's span lies in one merged span: the last one of its image that starts at or before it
-    const auto it = std::upper_bound(spans.begin(), spans.end(), e[q.k0].coff, [t](uint64_t v, const Span& x) {
-      return x.image != t ? t < x.image : v < x.lo;
-    });
-    const Span& x = *(it - 1);
+    const RangeSpans::Span& x = up.holding(t, e[q.k0].coff);
     if (m_at.size() + (q.k1 - q.k0 + 1) > 0x7fffffffull) return ZH_ERR_ARGUMENT;
     for (size_t k = q.k0; k <= q.k1; k++) {
       const uint64_t bs = e[k].uoff, be = e[k + 1].uoff;
@@ -984,14 +873,7 @@ extern "C" int zh_bgzf_read_ranges(zh_ctx* ctx, const void* const* images, const
       m_edge.push_back(1);
       m_doff.push_back(scratch_base + scratch);
       const uint64_t lo = std::max(q.off, bs), hi = std::min(q.end, be);
-      // pieces that end where the slot's offset is a multiple of 16, as in zh_ranges.hip: one workgroup never moves a whole member
-      for (uint64_t a = lo; a < hi;) {
-        const uint64_t d = doff[r] + (a - q.off);
-        uint64_t n = std::min<uint64_t>(hi - a, kClipChunk);
-        if (n == kClipChunk && ((d + n) & 15u)) n -= (d + n) & 15u;
-        clips.push_back(ZhClipDesc{scratch + (a - bs), d, (uint32_t)n, 0});
-        a += n;
-      }
+      append_clips(clips, scratch + (lo - bs), doff[r] + (lo - q.off), hi - lo);
       scratch += (be - bs + kGatherSlack + 255) & ~(uint64_t)255;
     }
     m_ranges[2 * r + 1] = (uint32_t)m_at.size();
@@ -1067,17 +949,9 @@ extern "C" int zh_bgzf_read_ranges(zh_ctx* ctx, const void* const* images, const
   tr.mark(ctx, "bgzf ranges: decode");
 
   std::vector<int32_t> rst(n_ranges);
-  std::vector<char> take(n_ranges);
-  for (size_t r = 0; r < n_ranges; r++) {
+  for (size_t r = 0; r < n_ranges; r++)
     rst[r] = geo[r].fixed != ZH_OK ? geo[r].fixed : bad[r] != kNone ? est[bad[r]] : (int32_t)ZH_OK;
-    take[r] = rst[r] == ZH_OK;
-  }
-  if ((st = zhh_download(ctx, d_dst.p, n_ranges, doff, dcap, take, dsts, dst_lens, rst.data()))) {
-    for (size_t r = 0; r < n_ranges; r++) free(dsts[r]);
-    clear_outputs(dsts, dst_lens, statuses, n_ranges);
-    return st;
-  }
-  for (size_t r = 0; r < n_ranges; r++) statuses[r] = rst[r];
+  if ((st = hand_out(ctx, d_dst.p, doff, dcap, rst, dsts, dst_lens, statuses))) return st;
   tr.mark(ctx, "bgzf ranges: download");
   return ZH_OK;
 }

@@ -8,9 +8,10 @@
 // reads from block-indexed streams: geometry, host call and its two kernels), the batch writers
 // zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
 // zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
-// all four share, zh_scan.h the signature scan of zh_zip_read_batch.hip and zh_bgzf.hip, zh_tar_dev.h and zh_zip_dev.h
-// what the two of a format share, zh_gather.h the unaligned copy), and zh_bgzf.hip (BGZF written, read, indexed and
-// read by range).
+// all four share, zh_scan.h the signature scan of zh_zip_read_batch.hip and zh_bgzf.hip with its host driver,
+// zh_tar_dev.h and zh_zip_dev.h what the two of a format share, zh_gather.h the unaligned copy), and zh_bgzf.hip (BGZF
+// written, read, indexed and read by range; zh_range_host.h holds the host arithmetic its range read shares with
+// zh_ranges.hip).
 // No compute happens on the host.  This header also holds what those files build their device memory with: DevMem /
 // DevBuf (owners that free through the context's cache) and Arena (the device arrays of a plan or call, each declared once).
 #pragma once

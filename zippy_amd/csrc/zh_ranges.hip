@@ -2,10 +2,12 @@
 // is for.  A range of the uncompressed data touches a run of deflate blocks; the blocks that lie wholly inside it are
 // decoded straight into the range's slot, the one or two that its ends cut into go through plan-owned scratch and
 // are clipped into place.  The decoder is zh_inflate_kernel (zh_inflate.hip), one wave pair a block, as in
-// zh_plan_uncompress_indexed; this file holds the geometry, the clip and reduce kernels, and the host call that sends
-// only the compressed bytes the ranges need over the link.
+// zh_plan_uncompress_indexed; this file holds the clip and reduce kernels, the plan over the ranges, and the host call
+// that sends only the compressed bytes the ranges need over the link.  The arithmetic it has in common with
+// zh_bgzf_read_ranges -- the geometry, the merged spans of the upload, the cut of a clip into pieces, the tail that
+// hands the results out -- is zh_range_host.h's; what a block index adds (bit offsets, stream_index_ok) stays here.
 #include "zh_gather.h"
-#include "zh_host.h"
+#include "zh_range_host.h"
 
 // One workgroup per piece of a clip: scratch[src, src + len) -> d_dst[dst, dst + len).  Stores of 16 bytes to aligned
 // addresses, the source gathered at whatever alignment it has (src & 15 is one value for the whole piece); byte
@@ -74,13 +76,6 @@ extern "C" void zh_launch_ranges_reduce(hipStream_t stream, ZhRangesArgs a) {
 // ---------------------------------------------------------------------------
 namespace {
 
-// What a range comes to before anything is decoded: its status if that is settled already, its clipped length, and
-// the blocks k0 .. k1 of its stream that hold its first and last byte (none: k0 > k1).
-struct RangeGeo {
-  int32_t fixed = ZH_OK;
-  uint64_t off = 0, end = 0;  // clipped
-  size_t k0 = 1, k1 = 0;      // entries of the stream's own list
-};
 // Where a range's compressed bytes are: the block that starts at bit b of its stream is decoded from bit b - 8 * skip
 // of d_src[off .. off + len).
 struct RangeSrc {
@@ -102,41 +97,15 @@ bool stream_index_ok(const zh_block_entry* e, size_t n, uint64_t src_len) {
   return true;
 }
 
-// pread's arithmetic and the binary search; ZH_ERR_ARGUMENT for a caller's bug
+// range_geometry (zh_range_host.h) over a block index: the entry's place is out_off, the verdict stream_index_ok's
 int ranges_geometry(size_t n_streams, const uint64_t* src_len, const zh_block_entry* index, const size_t* first,
                     size_t n_ranges, const uint64_t* rs, const uint64_t* ro, const uint64_t* rl,
                     std::vector<RangeGeo>& geo) {
-  if (n_ranges && (!rs || !ro || !rl)) return ZH_ERR_ARGUMENT;
-  if (n_streams && (!src_len || !first)) return ZH_ERR_ARGUMENT;
-  for (size_t s = 0; s < n_streams; s++)
-    if (first[s + 1] < first[s]) return ZH_ERR_ARGUMENT;
-  if (n_streams && first[n_streams] > first[0] && !index) return ZH_ERR_ARGUMENT;
-  for (size_t r = 0; r < n_ranges; r++)
-    if (rs[r] >= n_streams) return ZH_ERR_ARGUMENT;
-  std::vector<signed char> ok(n_streams, -1);  // (checked when a range first asks)
-  geo.assign(n_ranges, RangeGeo{});
-  for (size_t r = 0; r < n_ranges; r++) {
-    const size_t s = (size_t)rs[r];
-    const zh_block_entry* e = index + first[s];
-    const size_t ne = first[s + 1] - first[s];
-    if (ok[s] < 0) ok[s] = stream_index_ok(e, ne, src_len[s]) ? 1 : 0;
-    RangeGeo& g = geo[r];
-    if (!ok[s]) {
-      g.fixed = ZH_ERR_INVALID_BUFFER;
-      continue;
-    }
-    const uint64_t total = e[ne - 1].out_off;
-    if (ro[r] >= total || !rl[r]) continue;
-    g.off = ro[r];
-    g.end = rl[r] > total - ro[r] ? total : ro[r] + rl[r];  // (off + len may not fit 64 bits)
-    auto holds = [&](uint64_t byte) {  // the block k with out_off[k] <= byte < out_off[k + 1]
-      return (size_t)(std::upper_bound(e, e + ne, byte,
-                                       [](uint64_t v, const zh_block_entry& x) { return v < x.out_off; }) - e) - 1;
-    };
-    g.k0 = holds(g.off);
-    g.k1 = holds(g.end - 1);
-  }
-  return ZH_OK;
+  if (n_streams && !src_len) return ZH_ERR_ARGUMENT;
+  return range_geometry(
+      n_streams, index, first, n_ranges, rs, ro, rl,
+      [&](size_t s, const zh_block_entry* e, size_t ne) { return stream_index_ok(e, ne, src_len[s]); },
+      [](const zh_block_entry& x) { return x.out_off; }, geo);
 }
 
 // The plan over ranges whose geometry and compressed bytes are known.  dst_cap: null where every slot is as long as
@@ -193,14 +162,7 @@ int ranges_build(zh_ctx* ctx, const zh_block_entry* index, const size_t* first, 
       sc.push_back(block_decoder_desc(src[r].off, src[r].len, gbytes, be - bs));
       sc_bit.push_back(bit);
       const uint64_t lo = std::max(q.off, bs), hi = std::min(q.end, be);
-      // pieces that end where the slot's offset is a multiple of 16: with d_dst aligned, bytes go singly at a clip's two ends only
-      for (uint64_t a = lo; a < hi;) {
-        const uint64_t d = dst_off[r] + (a - q.off);
-        uint64_t n = std::min<uint64_t>(hi - a, kClipChunk);
-        if (n == kClipChunk && ((d + n) & 15u)) n -= (d + n) & 15u;
-        clips.push_back(ZhClipDesc{gbytes + (a - bs), d, (uint32_t)n, 0});
-        a += n;
-      }
+      append_clips(clips, gbytes + (lo - bs), dst_off[r] + (lo - q.off), hi - lo);
       gbytes += (be - bs + kGatherSlack + 255) & ~(uint64_t)255;
     }
     if (clips.size() > 0x7fffffffull) return ZH_ERR_ARGUMENT;
@@ -305,41 +267,20 @@ extern "C" int zh_uncompress_ranges(zh_ctx* ctx, const void* const* srcs, const 
   if (!n_ranges) return ZH_OK;
   Trace tr;
   // the spans, merged stream by stream
-  struct Span {
-    uint64_t stream, lo, hi, dev;
-  };
-  std::vector<Span> spans;
+  RangeSpans up;
   for (size_t r = 0; r < n_ranges; r++) {
     const RangeGeo& q = geo[r];
     if (q.fixed != ZH_OK || q.k0 > q.k1) continue;
     const size_t s = (size_t)range_stream[r];
     const zh_block_entry* e = index + first[s];
-    spans.push_back(Span{s, e[q.k0].bit_off / 8, std::min<uint64_t>(bytes_up_to(e[q.k1 + 1].bit_off), lens[s]), 0});
+    up.add(s, e[q.k0].bit_off / 8, std::min<uint64_t>(bytes_up_to(e[q.k1 + 1].bit_off), lens[s]));
   }
-  std::sort(spans.begin(), spans.end(),
-            [](const Span& a, const Span& b) { return a.stream != b.stream ? a.stream < b.stream : a.lo < b.lo; });
-  size_t m = 0;
-  for (size_t i = 0; i < spans.size(); i++) {
-    if (m && spans[m - 1].stream == spans[i].stream && spans[i].lo <= spans[m - 1].hi)
-      spans[m - 1].hi = std::max(spans[m - 1].hi, spans[i].hi);
-    else
-      spans[m++] = spans[i];
-  }
-  spans.resize(m);
-  std::vector<const void*> sp(m);
-  std::vector<uint64_t> soff(m), slen(m);
-  uint64_t up_total = 0;
-  for (size_t i = 0; i < m; i++) {
-    up_total = (up_total + 15) & ~(uint64_t)15;
-    spans[i].dev = soff[i] = up_total;
-    slen[i] = spans[i].hi - spans[i].lo;
-    sp[i] = (const uint8_t*)srcs[spans[i].stream] + spans[i].lo;
-    up_total += slen[i];
-  }
+  up.place(srcs);
+  const uint64_t up_total = up.up_total;
   ZH_HIP(ctx, hipSetDevice(ctx->device));
   DevBuf d_src;
   if (dev_alloc(ctx, d_src, up_total + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  if (const int st = zhh_upload_slices(ctx, sp.data(), soff, slen, up_total, d_src.p)) return st;
+  if (const int st = zhh_upload_slices(ctx, up.sp.data(), up.soff, up.slen, up_total, d_src.p)) return st;
   tr.mark(ctx, "ranges: upload");
   // every range's span lies in one merged span: the last one of its stream that starts at or before it
   std::vector<RangeSrc> src(n_ranges, RangeSrc{0, 0, 0});
@@ -351,11 +292,8 @@ extern "C" int zh_uncompress_ranges(zh_ctx* ctx, const void* const* srcs, const 
     dcap[r] = q.end - q.off;
     dst_total += (dcap[r] + 255) & ~(uint64_t)255;
     if (q.fixed != ZH_OK || q.k0 > q.k1) continue;
-    const uint64_t s = range_stream[r], lo = index[first[s] + q.k0].bit_off / 8;
-    const auto it = std::upper_bound(spans.begin(), spans.end(), lo, [s](uint64_t v, const Span& x) {
-      return x.stream != s ? s < x.stream : v < x.lo;
-    });
-    const Span& x = *(it - 1);
+    const uint64_t s = range_stream[r];
+    const RangeSpans::Span& x = up.holding(s, index[first[s] + q.k0].bit_off / 8);
     src[r] = RangeSrc{x.dev, x.hi - x.lo, x.lo};
   }
   DevBuf d_dst;
@@ -369,20 +307,7 @@ extern "C" int zh_uncompress_ranges(zh_ctx* ctx, const void* const* srcs, const 
   if ((st = zh_plan_results(pg.p, olen.data(), ost.data()))) return st;
   ctx->rg_uploaded = up_total;
   tr.mark(ctx, "ranges: decode");
-  std::vector<char> take(n_ranges);
-  for (size_t r = 0; r < n_ranges; r++) {
-    take[r] = ost[r] == ZH_OK;
-    statuses[r] = ost[r];
-  }
-  st = zhh_download(ctx, d_dst.p, n_ranges, doff, olen, take, dsts, dst_lens, statuses);
-  if (st) {
-    for (size_t r = 0; r < n_ranges; r++) {
-      free(dsts[r]);
-      dsts[r] = nullptr;
-      dst_lens[r] = 0;
-    }
-    return st;
-  }
+  if ((st = hand_out(ctx, d_dst.p, doff, olen, ost, dsts, dst_lens, statuses))) return st;
   tr.mark(ctx, "ranges: download");
   return ZH_OK;
 }

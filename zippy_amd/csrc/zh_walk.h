@@ -4,6 +4,7 @@
 // start ARE the records:
 //   zh_walk_double_kernel  pointer doubling with marks
 //   zh_walk_scan_*         a prefix sum over the marks: every record's ordinal in walk order, the list of records
+//   zh_walk_rec_ranges_kernel  every image's range of that list, for the walks over scanned candidates (zh_scan.h)
 // and the host half that launches them (Walk).  What a node is, and next[b], is the caller's.
 // The kernels have internal linkage: each file that includes this header launches its own copy.
 #pragma once
@@ -88,6 +89,18 @@ __global__ __launch_bounds__(256) void zh_walk_scan_write_kernel(const uint32_t*
     }
     carry += total;
   }
+}
+
+// Where the nodes are found candidates in image order (zh_scan.h), ranges[2t .. 2t + 1] being image t's: image t's
+// records are those between the ordinals of its first candidate and of the next image's (ord[all candidates] = all
+// records)
+__global__ __launch_bounds__(256) void zh_walk_rec_ranges_kernel(const uint32_t* __restrict__ ranges, uint32_t n_img,
+                                                                 const uint32_t* __restrict__ ord,
+                                                                 uint32_t* __restrict__ rec_ranges) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_img) return;
+  rec_ranges[2 * t] = ord[ranges[2 * t]];
+  rec_ranges[2 * t + 1] = ord[ranges[2 * t + 1]];
 }
 
 // The walk's scratch: two jump arrays, the marks, the ordinals -- 4 bytes a node each --, the scan's workgroup sums,

@@ -25,6 +25,10 @@
 // aligned words around a source, the stored copy and the scan aligned 16-byte chunks).  The bytes between two images
 // and behind the last are stale: a signature there, or one that begins in an image's tail and ends in the padding or
 // the next image, is no hit.
+//
+// That layout and upload, the two passes of the scan with their ZH_TRACE lines, the rounds of doubling and the walk's
+// scratch are host code of zh_scan.h (scan_upload, scan_hits, scan_walk_alloc), shared with zh_bgzf.hip;
+// zh_walk_rec_ranges_kernel is zh_walk.h's.  This file holds what is zip's: the three kernels on read_head, the tables.
 #include <unordered_map>
 
 #include "zh_scan.h"
@@ -211,17 +215,6 @@ __global__ __launch_bounds__(256) void zh_zipr_parse_kernel(const uint8_t* __res
   }
 }
 
-// The images' ranges of records for the reduction: hits are in image order, so image t's records are those between
-// the ordinals of its first hit and of the next image's (ord[n_hits] = all records)
-__global__ __launch_bounds__(256) void zh_zipr_rec_ranges_kernel(const uint32_t* __restrict__ ranges, uint32_t n_img,
-                                                                 const uint32_t* __restrict__ ord,
-                                                                 uint32_t* __restrict__ rec_ranges) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_img) return;
-  rec_ranges[2 * t] = ord[ranges[2 * t]];
-  rec_ranges[2 * t + 1] = ord[ranges[2 * t + 1]];
-}
-
 namespace {
 
 // ZipArchive.contents as it grows (an OrderedTable[string, ArchiveEntry]): keys in first-insertion order
@@ -243,88 +236,30 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   if (const int e = reader_checks(ctx, images, lens, n_zip, readers, statuses)) return e;
   if (!n_zip) return ZH_OK;
 
-  // ---- 1. the layout of the upload; the most nodes there can be (two signatures do not overlap) ----
-  std::vector<ZhZrImg> imgs(n_zip);
-  std::vector<uint64_t> up_off(n_zip), up_len(n_zip);
-  uint64_t up_total = 0, most_nodes = 0, max_chain = 0;
-  for (size_t t = 0; t < n_zip; t++) {
-    imgs[t] = ZhZrImg{up_total, (uint64_t)lens[t]};
-    up_off[t] = up_total;
-    up_len[t] = lens[t];
-    up_total += round_up8(lens[t]);
-    most_nodes += lens[t] / 4 + 1;
-    max_chain = std::max<uint64_t>(max_chain, lens[t] / 22 + 1);  // (no record is shorter than the end record)
-  }
-  if (most_nodes >= 0xffffffffull || n_zip >= 0x7fffffffull) return ZH_ERR_ARGUMENT;
-  ZH_HIP(ctx, hipSetDevice(ctx->device));
+  // ---- 1. the layout of the upload; 2. one upload; 3. the signature scan (zh_scan.h) ----
   Trace tr;
   int st;
+  ScanUpload S;
+  ScanHits H;
+  if ((st = scan_upload(ctx, tr, "zip read", images, lens, n_zip, 22, S))) return st;  // (no record is shorter than the end record)
+  if ((st = scan_hits<ZipSignature>(ctx, tr, "zip read", S, H))) return st;
   hipStream_t s = ctx->stream;
   const dim3 wg(256);
-  const uint32_t n_img = (uint32_t)n_zip;
-
-  // ---- 2. one upload ----
-  DevBuf d_in, d_imgs;
-  if (dev_alloc(ctx, d_in, up_total + 512) != hipSuccess) return ZH_ERR_NOMEM;
-  if (up_total && (st = zhh_upload_slices(ctx, images, up_off, up_len, up_total, d_in.p))) return st;
-  std::vector<uint64_t> ioff;
-  if ((st = zhh_upload_spans(ctx, {{imgs.data(), n_zip * sizeof(ZhZrImg)}}, d_imgs, ioff))) return st;
-  const ZhZrImg* const dimgs = reinterpret_cast<const ZhZrImg*>(d_imgs.p);
-  const uint8_t* const in = d_in.p;  // (plain pointers: a launch must not take the guard of a buffer along)
-  tr.mark(ctx, "zip read: upload");
-
-  // ---- 3. the signature scan ----
-  const uint64_t scan_bytes = (up_total + 15) & ~(uint64_t)15;
-  const uint64_t n_groups64 = std::max<uint64_t>(1, (scan_bytes + kScanGroupBytes - 1) / kScanGroupBytes);
-  if (n_groups64 >= 0x7fffffffull) return ZH_ERR_ARGUMENT;
-  const uint32_t n_groups = (uint32_t)n_groups64;
-  DevBuf d_sums, d_hits;
-  if (dev_alloc(ctx, d_sums, ((size_t)n_groups + 1) * 4) != hipSuccess) return ZH_ERR_NOMEM;
-  uint32_t* const gsums = reinterpret_cast<uint32_t*>(d_sums.p);
-  Events evs;
-  if (tr.on) evs.create();
-  if (evs.ok) (void)hipEventRecord(evs.e[0], s);
-  hipLaunchKernelGGL((zh_sig_scan_kernel<false, ZipSignature>), dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums,
-                     (uint64_t*)nullptr);
-  if (evs.ok) (void)hipEventRecord(evs.e[1], s);
-  hipLaunchKernelGGL(zh_walk_scan_offsets_kernel, dim3(1), wg, 0, s, gsums, n_groups);
-  ZH_HIP(ctx, hipGetLastError());
-  uint32_t n_hits = 0;  // everything behind the scan is sized by the hits there are
-  ZH_HIP(ctx, hipMemcpyAsync(&n_hits, gsums + n_groups, 4, hipMemcpyDeviceToHost, s));
-  ZH_HIP(ctx, hipStreamSynchronize(s));
-  if (dev_alloc(ctx, d_hits, (size_t)n_hits * 8 + 256) != hipSuccess) return ZH_ERR_NOMEM;
-  uint64_t* const hits = reinterpret_cast<uint64_t*>(d_hits.p);
-  if (evs.ok) (void)hipEventRecord(evs.e[2], s);
-  if (n_hits)
-    hipLaunchKernelGGL((zh_sig_scan_kernel<true, ZipSignature>), dim3(n_groups), wg, 0, s, in, scan_bytes, dimgs, n_img, gsums, hits);
-  if (evs.ok) {
-    (void)hipEventRecord(evs.e[3], s);
-    fprintf(stderr, "[zh] %-28s %8.3f ms (HIP events; count pass: %llu bytes read)\n", "zip read: scan kernel 1",
-            evs.ms(0, 1), (unsigned long long)scan_bytes);
-    fprintf(stderr, "[zh] %-28s %8.3f ms (HIP events; write pass: %u hits, at most %llu bytes read)\n",
-            "zip read: scan kernel 2", evs.ms(2, 3), n_hits,
-            (unsigned long long)std::min<uint64_t>(scan_bytes, (uint64_t)n_hits * kScanGroupBytes));
-  }
-  tr.mark(ctx, "zip read: scan");
+  const uint32_t n_img = S.n_img, n_hits = H.n_hits;
+  const uint8_t* const in = S.d_in.p;
+  const ZhZrImg* const dimgs = S.imgs();
+  const uint64_t* const hits = H.hits();
 
   // ---- 4. the walk ----
-  // after `rounds` rounds every node up to 2^rounds - 1 steps from a start is marked; a chain has no more records
-  // than there are hits, nor than its image has room for
-  max_chain = std::min<uint64_t>(max_chain, n_hits);
-  uint32_t rounds = 0;
-  while ((1ull << rounds) < max_chain + 1) rounds++;
   // behind the walk's scratch: what the loop finds behind every hit (succ), every image's range of hits
-  const uint32_t N = n_hits + n_img;
+  const uint32_t rounds = H.rounds, N = n_hits + n_img;
   int32_t* succ;
   uint32_t* hit_ranges;
   Arena ex;
   ex.add(succ, n_hits);
   ex.add(hit_ranges, (size_t)n_img * 2);
   Walk w;
-  if ((st = walk_alloc(ctx, w, N, ex.size + 256))) return st;
-  ex.base = w.extra;
-  ex.bind();
-  // (plain pointers for the launches: a launch must not take a DevBuf, or the Walk that holds one, along)
+  if ((st = scan_walk_alloc(ctx, S, H, ex, w))) return st;
   uint32_t *const j0 = w.j0, *const mark = w.mark;
   const uint32_t *const ord = w.ord, *const list = w.list;
   // the per-image outputs live in the block that is downloaded with the records (below); the start statuses are
@@ -333,10 +268,9 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   if (dev_alloc(ctx, d_start, (size_t)n_img * 4 + 256) != hipSuccess) return ZH_ERR_NOMEM;
   int32_t* const start = reinterpret_cast<int32_t*>(d_start.p);
   const dim3 node_grid((N + 255) / 256), img_grid((n_img + 255) / 256);
-  hipLaunchKernelGGL(zh_zipr_ranges_kernel, img_grid, wg, 0, s, dimgs, n_img, (const uint64_t*)hits, n_hits, hit_ranges,
-                     start);
-  hipLaunchKernelGGL(zh_zipr_next_kernel, node_grid, wg, 0, s, in, dimgs, n_img, (const uint64_t*)hits,
-                     n_hits, (const uint32_t*)hit_ranges, N, j0, mark, succ);
+  hipLaunchKernelGGL(zh_zipr_ranges_kernel, img_grid, wg, 0, s, dimgs, n_img, hits, n_hits, hit_ranges, start);
+  hipLaunchKernelGGL(zh_zipr_next_kernel, node_grid, wg, 0, s, in, dimgs, n_img, hits, n_hits,
+                     (const uint32_t*)hit_ranges, N, j0, mark, succ);
   walk_double(w, rounds, s);
   walk_scan(w, s);
   uint32_t n_rec = 0;
@@ -359,9 +293,9 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
   if (out.alloc(ctx, d_rec, 256) != hipSuccess) return ZH_ERR_NOMEM;
   out.bind();
   if (n_rec)
-    hipLaunchKernelGGL(zh_zipr_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, in, dimgs, n_img,
-                       (const uint64_t*)hits, list, (const int32_t*)succ, n_rec, d_recs, d_rstat);
-  hipLaunchKernelGGL(zh_zipr_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord, d_ranges);
+    hipLaunchKernelGGL(zh_zipr_parse_kernel, dim3((n_rec + 3) / 4), wg, 0, s, in, dimgs, n_img, hits, list,
+                       (const int32_t*)succ, n_rec, d_recs, d_rstat);
+  hipLaunchKernelGGL(zh_walk_rec_ranges_kernel, img_grid, wg, 0, s, (const uint32_t*)hit_ranges, n_img, ord, d_ranges);
   hipLaunchKernelGGL(zh_zip_reduce_kernel, dim3(n_img), wg, 0, s, (const uint32_t*)d_ranges, (const int32_t*)d_rstat,
                      (const uint8_t*)nullptr, d_bad, d_any);
   ZH_HIP(ctx, hipGetLastError());
@@ -415,7 +349,7 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
         // never above the stream's expansion bound: a tiny image cannot claim gigabytes
         const uint64_t cap = e.method == 8 ? std::min<uint64_t>(e.usize, (uint64_t)e.csize * 1032 + 64) : e.csize;
         slot_of[i] = slots.size();
-        slots.push_back(ZipSlot{t, i, up_off[t] + e.data_off, e.csize, out_total, cap, e.crc, e.usize, ZH_OK, e.method});
+        slots.push_back(ZipSlot{t, i, S.up_off[t] + e.data_off, e.csize, out_total, cap, e.crc, e.usize, ZH_OK, e.method});
         out_total += round_up8(cap);
         std::string key((const char*)image + e.name_off, e.name_len);
         if (e.backslash) std::replace(key.begin(), key.end(), '\\', '/');  // toUnixPath
@@ -463,7 +397,7 @@ extern "C" int zh_zip_read_batch(zh_ctx* ctx, const void* const* images, const s
       return st;
     // A stream that outgrew its slot decodes to more than its header claims: CRC comes before size (:208-217), so it
     // is decoded again in full (zip_redo).  None of them can end well: at best the length is not the header's.
-    if ((st = zip_redo(ctx, tr, "zip read", slots, eranges, images, up_off, own, est, ebad,
+    if ((st = zip_redo(ctx, tr, "zip read", slots, eranges, images, S.up_off, own, est, ebad,
                        [&](size_t j, int32_t rst, uint32_t rcrc, size_t rout, void*&) {
                          const ZipSlot& sl = slots[j];
                          return rst != ZH_OK ? rst : rcrc != sl.want_crc ? ZH_ERR_ZIP_CRC

@@ -109,6 +109,19 @@ def check_write_residues(eng):
     check_read(eng, [out], want=[bm.OK])
 
 
+def check_write_whole_chunks(eng):
+    """1700 bytes of noise at level 0, b = 100: every member is 18 + 105 + 8 = 131 bytes, and 131 mod 16 = 3 is coprime
+    to 16 -- the CDATA of sixteen consecutive members starts at every residue mod 16, each with five or six whole 16-byte
+    chunks (check_write_residues' members are shorter than 30 bytes: no whole chunk)"""
+    src = noise(1700, 5)
+    out = check_write(eng, [src], 0, 100)[0]
+    st, idx, eof = bm.index(out)
+    assert [c for c, _ in idx[:17]] == [131 * k for k in range(17)]
+    assert {(c + 18) % 16 for c, _ in idx[:16]} == set(range(16))
+    assert all((c + 18 + 105) // 16 - (c + 18 + 15) // 16 >= 5 for c, _ in idx[:16])
+    check_read(eng, [out], want=[bm.OK])
+
+
 def fallback_pair():
     return noise(65505, 11), noise(65450, 12)
 

@@ -1,5 +1,5 @@
 """The stand-alone sanitized programs of test_zip_open_sanitize.py, test_zip_read_sanitize.py,
-test_tar_read_sanitize.py and test_arena_sanitize.py: zippy_amd/csrc built by g++ under AddressSanitizer and UndefinedBehaviorSanitizer against
+test_tar_read_sanitize.py, test_zip_write_sanitize.py and test_arena_sanitize.py: zippy_amd/csrc built by g++ under AddressSanitizer and UndefinedBehaviorSanitizer against
 the emulator runtime of tests/hipemu -- once a pytest process, into a temporary directory --, each test's main linked
 against those objects and run directly.  Nothing is built under the tree."""
 import atexit

@@ -25,6 +25,10 @@ def test_emu_bgzf_write_every_residue(eng):
     bc.check_write_residues(eng)
 
 
+def test_emu_bgzf_write_whole_chunks(eng):
+    bc.check_write_whole_chunks(eng)
+
+
 def test_emu_bgzf_write_fallback(eng):
     bc.check_fallback(eng)
 

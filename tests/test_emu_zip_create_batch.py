@@ -126,6 +126,33 @@ def test_emu_zipc_batch_of_one_equals_zh_zip_create(eng, k):
     assert sts == [0] and outs[0] == eng.create_zip(entries, T, D)
 
 
+def _raw_create(eng, table):
+    """zh_zip_create through ctypes; contents None: a NULL pointer with the length given -> (rc, archive or None)"""
+    n = len(table)
+    names = (c.c_char_p * n)(*[p for p, _, _ in table])
+    nlens = (c.c_size_t * n)(*[len(p) for p, _, _ in table])
+    blobs = (c.c_void_p * n)(*[c.cast(c.c_char_p(b), c.c_void_p) if b else None for _, b, _ in table])
+    blens = (c.c_size_t * n)(*[ln for _, _, ln in table])
+    dst, dlen = c.c_void_p(0xDEAD000), c.c_size_t(12345)
+    rc = eng.lib.zh_zip_create(eng._h, names if n else None, nlens if n else None, blobs if n else None,
+                               blens if n else None, n, T, D, c.byref(dst), c.byref(dlen))
+    try:
+        return rc, c.string_at(dst, dlen.value) if dst.value else None
+    finally:
+        eng.lib.zh_free(dst)
+
+
+def test_emu_zip_create_precedence(eng):
+    """zh_zip_create's own checks run last to first and the entry processed first decides: a missing path reads
+    ZH_ERR_ZIP_NAME, missing contents ZH_ERR_ARGUMENT (zh_zip_create_batch's call-level checks would say otherwise);
+    no entries with NULL arrays: the 98 bytes"""
+    assert _raw_create(eng, [(b"ok", None, 5), (b"", b"x", 1)]) == (zm.ZH_ERR_ZIP_NAME, None)
+    assert _raw_create(eng, [(b"", b"x", 1), (b"ok", None, 5)]) == (zm.ZH_ERR_ARGUMENT, None)
+    assert _raw_create(eng, [(b"a", b"1", 1), (b"a", b"2", 1)]) == (zm.ZH_ERR_ZIP_DUPLICATE, None)
+    assert _raw_create(eng, []) == (0, zm.image([], T, D))
+    assert len(zm.image([], T, D)) == 98
+
+
 def test_emu_zipc_whole_batch_equals_one_by_one(eng):
     outs, sts = eng.create_zips(ENTRY_SETS, T, D)
     assert sts == [0] * len(ENTRY_SETS)

@@ -10,19 +10,14 @@ import pytest
 import emu
 import synth
 import zip_v1_writer_model as zm
+import zip_write_cases
+from zip_write_cases import SIZES, blob as _blob
 from zippy_amd.common import ZippyError
 
 
 @pytest.fixture(scope="module")
 def eng():
     return emu.engine()
-
-
-def _blob(n, seed=1):
-    return bytes((i * 131 + seed * 7 + (i >> 7) + (i * i >> 11)) & 0xFF for i in range(n))
-
-
-SIZES = [0, 1, 3, 4, 15, 16, 17, 140000]
 
 
 def test_emu_zip_entry_sizes(eng):
@@ -47,6 +42,10 @@ def test_emu_zip_record_alignments(eng):
     img = eng.write_zip(entries)
     assert img == zm.image(entries)
     assert all(img[at - len(p):at] == p.encode() for (p, _), at in zip(entries[::2], starts))
+
+
+def test_emu_zip_end_record_alignments(eng):
+    zip_write_cases.check_end_record_alignments(eng)
 
 
 def test_emu_zip_directories_and_paths(eng):

@@ -31,6 +31,10 @@ def test_gpu_bgzf_write_every_residue(eng):
     bc.check_write_residues(eng)
 
 
+def test_gpu_bgzf_write_whole_chunks(eng):
+    bc.check_write_whole_chunks(eng)
+
+
 def test_gpu_bgzf_write_fallback(eng):
     bc.check_fallback(eng)
 

@@ -9,6 +9,7 @@ import pytest
 
 import synth
 import zip_v1_writer_model as zm
+import zip_write_cases
 from zippy_amd.common import BestSpeed, DefaultCompression, ZippyError, to_msdos
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +51,10 @@ def test_gpu_zip_bagnon_written_back(eng):
     assert eng.write_zip(entries) == img
     with zipfile.ZipFile(io.BytesIO(img)) as zf:
         assert zf.testzip() is None
+
+
+def test_gpu_zip_end_record_alignments(eng):
+    zip_write_cases.check_end_record_alignments(eng)
 
 
 def test_gpu_zip_libressl_entries(eng):

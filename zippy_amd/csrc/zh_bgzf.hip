@@ -324,9 +324,8 @@ __global__ __launch_bounds__(256) void zh_bgzf_image_len_kernel(const uint32_t* 
 }
 
 // One wave per task (four a workgroup).  A member's first task writes its 18-byte header and its trailer (or the
-// marker) one byte a lane; every task moves its piece of the CDATA from the slot to its place: the bytes in front of
-// the first and behind the last aligned 16-byte chunk of the place one a lane, the chunks in between with one 16-byte
-// store each, their bytes gathered from the (differently aligned) slot.
+// marker) one byte a lane; every task moves its piece of the CDATA from the slot to its (differently aligned) place
+// by zh_gather.h's copy_range.
 __global__ __launch_bounds__(256) void zh_bgzf_assemble_kernel(const uint8_t* __restrict__ slots0,
                                                                const uint8_t* __restrict__ slots1,
                                                                uint8_t* __restrict__ d_out,
@@ -361,15 +360,7 @@ __global__ __launch_bounds__(256) void zh_bgzf_assemble_kernel(const uint8_t* __
   if (t.lo >= clen) return;
   const uint8_t* __restrict__ src = m.which == 0 ? slots0 : slots1;
   const uint64_t a = at + 18 + t.lo, b = at + 18 + (clen < t.lo + kTaskBytes ? clen : t.lo + kTaskBytes);
-  const uint64_t delta = m.slot - (at + 18);  // (slot byte = output byte + delta, mod 2^64)
-  const uint64_t A = (a + 15) & ~(uint64_t)15, B = b & ~(uint64_t)15;
-  if (A >= B) {  // no whole chunk inside: at most 30 bytes
-    if (a + lane < b) d_out[a + lane] = src[a + lane + delta];
-    return;
-  }
-  if (a + lane < A) d_out[a + lane] = src[a + lane + delta];
-  if (B + lane < b) d_out[B + lane] = src[B + lane + delta];
-  for (uint64_t c = A + 16ull * lane; c < B; c += 1024) *reinterpret_cast<Chunk16*>(d_out + c) = gather16(src, c + delta);
+  copy_range(d_out, a, b, src, m.slot - (at + 18), lane);  // (slot byte = output byte + delta)
 }
 
 // ---------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 // .tar.gz the images are then compressed in place as one batch (compress(data, level, dfGzip), :269).
 #include <unordered_set>
 
+#include "zh_gather.h"
 #include "zh_host.h"
 
 namespace {
@@ -17,10 +18,6 @@ struct ZhTarHdrDesc {
   uint32_t tail_at;
   uint16_t head_len, tail_len;
   uint32_t kind, pad;
-};
-
-struct alignas(16) Chunk16 {
-  uint32_t w[4];
 };
 
 constexpr uint64_t kOct11 = 1ull << 33;  // 8^11: toOct(x, 11) keeps every digit below this

@@ -95,9 +95,8 @@ struct ZhZipFinTask {
   uint32_t entry, first;
 };
 
-// One wave per task (four a workgroup): a slice of a stored entry's bytes goes from its image to its slot -- the
-// bytes in front of the first and behind the last aligned 16-byte chunk of the slot one a lane, the chunks in between
-// with one 16-byte store each, their bytes gathered from the (differently aligned) source.  The wave of an entry's
+// One wave per task (four a workgroup): a slice of a stored entry's bytes goes from its image to its (differently
+// aligned) slot by zh_gather.h's copy_range.  The wave of an entry's
 // first task also settles the entry, by the first of these that applies: a local header that failed; the decoder's
 // status (deflated entries: the plan's status, length and CRC-32); the CRC-32 against the header's; with check_len,
 // the length against the header's.  elen (if given): the entry's length, 0 when it failed.
@@ -127,16 +126,7 @@ __global__ __launch_bounds__(256) void zh_zip_finish_kernel(const uint8_t* __res
     est[t.entry] = st;
     if (elen) elen[t.entry] = len;
   }
-  if (t.lo >= t.hi) return;
-  const uint64_t a = e.dst + t.lo, b = e.dst + t.hi, delta = e.src - e.dst;  // (source byte = slot byte + delta, mod 2^64)
-  const uint64_t A = (a + 15) & ~(uint64_t)15, B = b & ~(uint64_t)15;
-  if (A >= B) {  // no whole chunk inside: at most 30 bytes
-    if (a + lane < b) d_out[a + lane] = d_in[a + lane + delta];
-    return;
-  }
-  if (a + lane < A) d_out[a + lane] = d_in[a + lane + delta];
-  if (B + lane < b) d_out[B + lane] = d_in[B + lane + delta];
-  for (uint64_t c = A + 16ull * lane; c < B; c += 1024) *reinterpret_cast<Chunk16*>(d_out + c) = gather16(d_in, c + delta);
+  copy_range(d_out, e.dst + t.lo, e.dst + t.hi, d_in, e.src - e.dst, lane);  // (source byte = slot byte + delta)
 }
 
 // One decode, the stored entries and every verdict: the slots' data goes from the upload buffer d_in into their places

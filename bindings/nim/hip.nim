@@ -671,3 +671,35 @@ proc hipBgzfReadRange*(image: string, index: seq[ZhBgzfEntry], off, len: uint64)
   let rc = zh_bgzf_read_ranges(engine(), p.addr, ilen.addr, 1, (if index.len > 0: index[0].unsafeAddr else: nil),
                                first[0].addr, 1, ri.addr, ro.addr, rl.addr, dst.addr, dstLen.addr, st.addr)
   take(dst, dstLen, if rc != 0: rc else: st.cint)
+
+# ---- seek indexes for foreign deflate streams (no counterpart in the reference) ----
+proc zh_seek_index_batch(ctx: ZhCtx, srcs: ptr pointer, lens: ptr csize_t, n: csize_t, dataFormat: cint, span: uint64,
+                         indexes: ptr pointer, indexLens: ptr csize_t, dsts: ptr pointer, dstLens: ptr csize_t,
+                         statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_seek_read_ranges(ctx: ZhCtx, srcs: ptr pointer, lens: ptr csize_t, nStreams: csize_t, indexes: ptr pointer,
+                         indexLens: ptr csize_t, nRanges: csize_t, rangeStream, rangeOff, rangeLen: ptr uint64,
+                         dsts: ptr pointer, dstLens: ptr csize_t,
+                         statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipSeekIndex*(src: string, dataFormat = dfDetect, span = 0'u64): string {.raises: [ZippyError].} =
+  ## the seek index of a zlib / gzip / raw deflate stream of any writer: a blob that may be stored (the layout is
+  ## include/zippy_hip.h's); span: uncompressed bytes between points (0: 1 MiB, else at least 32768)
+  var p = if src.len > 0: src[0].unsafeAddr.pointer else: nil
+  var len = src.len.csize_t
+  var idx: pointer; var idxLen: csize_t; var st: int32
+  let rc = zh_seek_index_batch(engine(), p.addr, len.addr, 1, dataFormat.cint, span, idx.addr, idxLen.addr, nil, nil,
+                               st.addr)
+  take(idx, idxLen, if rc != 0: rc else: st.cint)
+
+proc hipSeekReadRange*(src, index: string, off, len: uint64): string {.raises: [ZippyError].} =
+  ## bytes [off, off + len) of the uncompressed data: only the intervals the range touches and their windows are
+  ## uploaded and decoded, each verified by its CRC-32.  Reads like pread (clipped at the end, empty behind it).
+  var p = if src.len > 0: src[0].unsafeAddr.pointer else: nil
+  var slen = src.len.csize_t
+  var ip = if index.len > 0: index[0].unsafeAddr.pointer else: nil
+  var ilen = index.len.csize_t
+  var ri = 0'u64; var ro = off; var rl = len
+  var dst: pointer; var dstLen: csize_t; var st: int32
+  let rc = zh_seek_read_ranges(engine(), p.addr, slen.addr, 1, ip.addr, ilen.addr, 1, ri.addr, ro.addr, rl.addr,
+                               dst.addr, dstLen.addr, st.addr)
+  take(dst, dstLen, if rc != 0: rc else: st.cint)

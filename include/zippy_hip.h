@@ -472,6 +472,84 @@ int zh_bgzf_read_ranges(zh_ctx *ctx, const void *const *images, const size_t *le
                         void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
+ * Seek indexes for FOREIGN deflate streams (zlib, pigz, gzip, zip     *
+ * entries: every block reaches up to 32 KiB back into the one before) *
+ * -- the idea of zlib's zran.c: decode the stream once, keep at       *
+ * chosen block boundaries the bit position, the output position and   *
+ * the 32 KiB of output before it; from then on a byte range needs the *
+ * compressed bytes of the intervals it touches and their windows, and *
+ * every interval decodes on its own.  The index is built from a fully *
+ * decoded, container-verified stream and carries a CRC-32 per         *
+ * interval: every range read is verified.                             *
+ * ------------------------------------------------------------------ */
+/* The index of one stream is one flat little-endian blob (library-allocated, zh_free; it may be written to disk):
+ *   zh_seek_header, 64 bytes | n_points records of zh_seek_point, 32 bytes each | the window store, window_bytes.
+ * Point k: the deflate block whose header's first bit is bit_off, counted from the first byte of the buffer (container
+ * header included, as in zh_block_entry), begins at byte out_off of the uncompressed data; the win_len = min(out_off,
+ * 32768) bytes of output before it lie at win_off of the window store (a multiple of 16; every window is padded with
+ * zeros to a multiple of 16); crc32 is the CRC-32 of the uncompressed bytes [out_off, next point's out_off).  The last
+ * point is the closing entry: the bit just behind the final block's end-of-block code, `total`, win_len 0, crc32 0.
+ * Which block boundaries become points: point 0 is the first block (out_off 0, no window); going through the later
+ * block starts in stream order, a block start becomes a point when its out_off minus the last point's out_off is at
+ * least `span` (of several empty blocks at one out_off, the first that qualifies).  Points lie at block boundaries
+ * ONLY: a stream of one 4 MiB block has point 0 and the closing entry whatever the span.  The blob is pinned by this
+ * rule: the same stream and span give the same bytes. */
+#define ZH_SEEK_MAGIC "ZHSKIDX1"
+#define ZH_SEEK_VERSION 1u
+#define ZH_SEEK_WINDOW 32768u
+#define ZH_SEEK_DEFAULT_SPAN 1048576u /* span 0 (zran's default) */
+typedef struct zh_seek_header {
+  char magic[8];         /* ZH_SEEK_MAGIC */
+  uint32_t version;      /* ZH_SEEK_VERSION */
+  uint32_t data_format;  /* resolved: ZH_DF_ZLIB, ZH_DF_GZIP or ZH_DF_DEFLATE */
+  uint64_t src_len;      /* bytes of the compressed buffer */
+  uint64_t total;        /* bytes of the uncompressed data */
+  uint64_t span;         /* as resolved (never 0) */
+  uint64_t n_points;     /* closing entry included */
+  uint64_t window_bytes; /* bytes of the window store */
+  uint64_t reserved;     /* 0 */
+} zh_seek_header;
+typedef struct zh_seek_point {
+  uint64_t bit_off, out_off, win_off;
+  uint32_t win_len, crc32;
+} zh_seek_point;
+
+/* One index per stream (indexes[i] / index_lens[i], zh_free), and with dsts / dst_lens (both or neither) the decoded
+ * data as well (otherwise it is not downloaded).  statuses[i] is what zh_uncompress_batch gives stream i: container
+ * header, CRC-32 / Adler-32 and ISIZE are all checked; an index exists only for a stream that decodes with ZH_OK, a
+ * bad stream gives NULL / 0 and does not disturb its neighbours.  span: 0 means ZH_SEEK_DEFAULT_SPAN, otherwise at
+ * least ZH_SEEK_WINDOW (anything else: ZH_ERR_ARGUMENT for the call).  n == 0 launches nothing.  Every stream takes
+ * the one-workgroup-a-stream decoder, which records the points as it goes (large single streams are not decoded
+ * segment-wise here). */
+int zh_seek_index_batch(zh_ctx *ctx, const void *const *srcs, const size_t *lens, size_t n, int data_format,
+                        uint64_t span, void **indexes, size_t *index_lens, void **dsts, size_t *dst_lens,
+                        int32_t *statuses);
+/* Byte ranges of the uncompressed data of streams with seek indexes, like pread and word for word like
+ * zh_uncompress_ranges: a range is clipped at `total`; range_off at or beyond it, or range_len 0, gives 0 bytes and
+ * ZH_OK and touches nothing; range_off + range_len beyond 2^64 is clipped; range_stream[r] >= n_streams and NULL
+ * arrays are ZH_ERR_ARGUMENT; two ranges that share an interval decode it twice.
+ * A blob that cannot be right fails every range of THAT stream, and no other, with ZH_ERR_INVALID_BUFFER: wrong magic
+ * or version, a length that does not match its own counts, src_len != lens[s], fewer than two points, out_off[0] != 0,
+ * bit_off not strictly rising or at or beyond 8 * src_len (beyond, for the closing entry), out_off falling, win_len !=
+ * min(out_off, 32768), a window outside the store or not at a multiple of 16, an interval that promises more than
+ * 1032 * (its compressed bytes) + 64 bytes.
+ * Of stream s only the bytes [bit_off[k0] / 8, ceil(bit_off[k1 + 1] / 8)) of the intervals k0 .. k1 a range touches
+ * are uploaded -- spans of one stream that overlap or touch once -- and the windows of exactly those intervals;
+ * zh_debug_range_stats reports those bytes (spans plus windows), 0 intervals in place and the intervals decoded.
+ * Every touched interval decodes on its own into a scratch slot [window | output] (scratch bounded by
+ * ZH_SCRATCH_MB: groups of ranges take turns): it starts at bit_off[k] with the window as its history -- a match that
+ * reaches beyond the window is ZH_ERR_INVALID_BUFFER --, and stops at a block boundary at bit_off[k + 1] (a block
+ * boundary beyond it, or a final block that ends elsewhere: ZH_ERR_INVALID_BUFFER).  Verified per interval, in this
+ * order: the decoder's status; exactly out_off[k + 1] - out_off[k] bytes made (else ZH_ERR_INVALID_BUFFER); their
+ * CRC-32 equal to the point's (else ZH_ERR_CHECKSUM).  A range's status is that of its lowest failing interval, its
+ * length then 0; ranges that touch no bad interval succeed.  The container's header and trailer are not looked at:
+ * the build verified them. */
+int zh_seek_read_ranges(zh_ctx *ctx, const void *const *srcs, const size_t *lens, size_t n_streams,
+                        const void *const *indexes, const size_t *index_lens, size_t n_ranges,
+                        const uint64_t *range_stream, const uint64_t *range_off, const uint64_t *range_len,
+                        void **dsts, size_t *dst_lens, int32_t *statuses);
+
+/* ------------------------------------------------------------------ *
  * ZIP archives as batch clients of the codec. *
  * Record parsing / assembly of src/zippy/ziparchives.nim on the host, *
  * every entry's deflate stream and CRC-32 in ONE GPU batch.  The file *

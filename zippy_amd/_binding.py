@@ -114,6 +114,13 @@ _SIGS = {
                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
                                        _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
+    "zh_seek_index_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.c_int, _c.c_uint64, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
+    "zh_seek_read_ranges": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                       _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
     "zh_crc32_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                   _c.POINTER(_c.c_uint32)]),
     "zh_compress_batch_crc32": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
@@ -940,6 +947,62 @@ class Engine:
         flat, first, (rs, ro, rl) = self._range_tables(indexes, ranges)
         dsts, dlens, sts = (_c.c_void_p * max(1, nr))(), (_c.c_size_t * max(1, nr))(), (_c.c_int32 * max(1, nr))()
         rc = self.lib.zh_bgzf_read_ranges(self._h, srcs, lens, ns, flat, first, nr, rs, ro, rl, dsts, dlens, sts)
+        outs = []
+        try:
+            for r in range(nr):
+                outs.append(_c.string_at(dsts[r], dlens[r]) if dsts[r] and sts[r] == 0 else None)
+        finally:
+            for r in range(nr):
+                if dsts[r]:
+                    self.lib.zh_free(dsts[r])
+        self._check(rc)
+        return outs, list(sts)[:nr]
+
+    # ---- seek indexes for foreign deflate streams ----
+    def seek_index_batch(self, srcs, dataFormat=dfDetect, span=0, want_data=False):
+        """One seek index (a blob of bytes, include/zippy_hip.h) per stream (zh_seek_index_batch); span: uncompressed
+        bytes between points (0: 1 MiB).  -> (indexes, statuses), with want_data (indexes, statuses, outputs); an index
+        and an output are None where the stream's status is not 0."""
+        n = len(srcs)
+        keep = [bytes(b) for b in srcs]
+        ptrs = (_c.c_void_p * max(1, n))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * max(1, n))(*[len(k) for k in keep])
+        idx, ilens, sts = (_c.c_void_p * max(1, n))(), (_c.c_size_t * max(1, n))(), (_c.c_int32 * max(1, n))()
+        dsts, dlens = ((_c.c_void_p * max(1, n))(), (_c.c_size_t * max(1, n))()) if want_data else (None, None)
+        rc = self.lib.zh_seek_index_batch(self._h, ptrs, lens, n, int(dataFormat), int(span), idx, ilens, dsts, dlens, sts)
+        blobs, outs = [], []
+        try:
+            for i in range(n):
+                blobs.append(_c.string_at(idx[i], ilens[i]) if idx[i] and sts[i] == 0 else None)
+                if want_data:
+                    outs.append(_c.string_at(dsts[i], dlens[i]) if dsts[i] and sts[i] == 0 else None)
+        finally:
+            for i in range(n):
+                if idx[i]:
+                    self.lib.zh_free(idx[i])
+                if want_data and dsts[i]:
+                    self.lib.zh_free(dsts[i])
+        self._check(rc)
+        return (blobs, list(sts)[:n], outs) if want_data else (blobs, list(sts)[:n])
+
+    def seek_read_ranges(self, streams, indexes, ranges):
+        """Bytes [off, off + len) of the uncompressed data of streams[stream] for every (stream, off, len) of `ranges`,
+        one call (zh_seek_read_ranges); indexes[s]: stream s's blob as seek_index_batch returns it (None, what it
+        returns for a stream that failed, is a blob of no bytes: that stream's ranges fail with status 13).
+        -> (list of bytes | None, statuses)"""
+        if len(indexes) != len(streams):
+            raise ValueError("indexes: one per stream")
+        ns, nr = len(streams), len(ranges)
+        keep = [bytes(b) for b in streams]
+        blobs = [bytes(b) if b is not None else b"" for b in indexes]
+        srcs = (_c.c_void_p * max(1, ns))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * max(1, ns))(*[len(k) for k in keep])
+        idx = (_c.c_void_p * max(1, ns))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in blobs])
+        ilens = (_c.c_size_t * max(1, ns))(*[len(k) for k in blobs])
+        m64 = (1 << 64) - 1
+        rs, ro, rl = [_u64([int(r[k]) & m64 for r in ranges]) for k in range(3)]
+        dsts, dlens, sts = (_c.c_void_p * max(1, nr))(), (_c.c_size_t * max(1, nr))(), (_c.c_int32 * max(1, nr))()
+        rc = self.lib.zh_seek_read_ranges(self._h, srcs, lens, ns, idx, ilens, nr, rs, ro, rl, dsts, dlens, sts)
         outs = []
         try:
             for r in range(nr):

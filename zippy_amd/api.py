@@ -122,6 +122,37 @@ def bgzf_read_range(image, index, off, length):
     return eng._raise_first(outs, sts)[0]
 
 
+def seek_index_batch(srcs, dataFormat=dfDetect, span=0, want_data=False):
+    """Seek indexes for foreign deflate streams (zlib, gzip, raw; from zlib, pigz or this library), in one call: every
+    stream is decoded and verified once, and at block boundaries at least `span` uncompressed bytes apart (0: 1 MiB, else
+    at least 32768) the index keeps the bit position, the output position and the 32 KiB of output before it, with a
+    CRC-32 per interval.  -> (indexes, statuses), with want_data (indexes, statuses, outputs); an index is a blob of
+    bytes that may be stored, None where the stream's status is not 0."""
+    return engine().seek_index_batch(srcs, dataFormat, span, want_data)
+
+
+def seek_index(src, dataFormat=dfDetect, span=0):
+    """seek_index_batch for one stream -> the blob; raises ZippyError where the stream does not decode."""
+    eng = engine()
+    blobs, sts = eng.seek_index_batch([src], dataFormat, span)
+    return eng._raise_first(blobs, sts)[0]
+
+
+def seek_read_ranges(streams, indexes, ranges):
+    """Random access into streams with seek indexes: bytes [off, off + len) of the uncompressed data of
+    streams[stream] for every (stream, off, len) of `ranges`, in one call -- only the intervals a range touches, and
+    their windows, are uploaded and decoded, each verified by its CRC-32.  Ranges read like pread.
+    -> (outputs, statuses); an output is None where its status is not 0."""
+    return engine().seek_read_ranges(streams, indexes, ranges)
+
+
+def seek_read_range(src, index, off, length):
+    """seek_read_ranges for one range of one stream -> bytes; raises ZippyError where the range cannot be read."""
+    eng = engine()
+    outs, sts = eng.seek_read_ranges([src], [index], [(0, off, length)])
+    return eng._raise_first(outs, sts)[0]
+
+
 def openZipArchive(image):
     """ziparchives.nim:183 openZipArchive on the bytes of an archive -> reader with walk_files(),
     extract_file(path), extract_batch(indices)."""

@@ -134,6 +134,25 @@ struct ZhInflateArgs {
   uint32_t first_buf;
 };
 
+// Seek indexes (zh_seek.hip); arguments of their own, so that ZhInflateArgs, which every inflate kernel takes by value,
+// stays as it is.
+// An index build: the recording tokens kernel (zh_inflate_tokens_kernel<.., kRec>) leaves stream i's chosen points --
+// pairs (bit_off, out_off), the closing entry last -- in points[2 * off[i] ..], at most cap[i] of them, and how many the
+// rule chose in n[i] (more than cap[i]: the list is cut short, run again with room).
+struct ZhRecArgs {
+  uint64_t span;
+  uint64_t* points;  // null: nothing is recorded
+  const uint64_t* off;
+  const uint32_t* cap;
+  uint32_t* n;
+};
+// A range read (zh_seek_inflate_kernel): "stream" i's slot already holds hist_len[i] bytes of history in front of its
+// output, and its decode ends at the block boundary stop_bit[i] (counted like ZhInflateArgs::start_bit)
+struct ZhSeekStop {
+  const uint32_t* hist_len;
+  const uint64_t* stop_bit;
+};
+
 // One large stream decoded by many workgroups (zh_inflate_seg.hip).  The compressed bytes are cut
 // into segments; a segment's decoder starts at the first deflate block found at or behind the
 // segment's nominal first bit and stops at the block boundary where the next segment's begins.

@@ -112,13 +112,18 @@ struct RunResult {
 // zippy.nim:130-165, zh_host_batch.hip): the same decode, but no record is written and no room is asked for -- the
 // stream's output bytes are summed and left in out_len.  An instantiation of its own: the batches' kernel keeps its
 // registers and its code.
-template <uint32_t kSplitThreads, bool kSeg, bool kCount = false>
+// kRec: the decoder of an INDEX BUILD (zh_seek.hip, ZhRecArgs rec): the batches' kernel, which also keeps the
+// produced byte count as the two forms above do and, at the top of the block loop, where the bit position of every
+// header is known, applies the point rule of include/zippy_hip.h -- only chosen points are written, all are counted.
+// It reads every stored block's header by itself (no chain of 64 at once: each is a block start).  An instantiation
+// of its own for the same reason.
+template <uint32_t kSplitThreads, bool kSeg, bool kCount = false, bool kRec = false>
 __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : kSplitThreads < 256 ? 4 : 1) void zh_inflate_tokens_kernel(const uint8_t* __restrict__ d_src,
                                                                 ZhInflateArgs a,
                                                                 uint32_t* __restrict__ tok_pool,
                                                                 const uint64_t* __restrict__ tok_off,
                                                                 const uint64_t* __restrict__ tok_cap,
-                                                                ZhSegArgs g, int phase) {
+                                                                ZhSegArgs g, int phase, ZhRecArgs rec) {
   constexpr uint32_t kSuperBits = kSplitThreads * kSubBits;
   constexpr uint32_t kStageWords = (kSplitThreads + 1u) * kSubStride;
   constexpr uint32_t kWaves = kSplitThreads / 64u;
@@ -199,6 +204,8 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
   // stream position in bits (from asrc)
   uint64_t pos = kSeg ? (uint64_t)mis * 8 + (sub_first ? g.sub_hdr[sid] : seg_start) : ((uint64_t)mis + a.body_pos[sid]) * 8;
   uint64_t ntok = 0, out_bytes = 0;
+  uint64_t rec_last = 0;   // kRec: the last point's out_off ...
+  uint32_t rec_count = 0;  // ... and the points so far (the same in every thread)
   KPROF_DECL(8);  // cycles: 0 header + tables, 1 staging, 2 sync turns, 3 scan, 4 token pass; counts: 5 superchunks, 6 turns, 7 streams
   int st = ZH_OK;
   bool final_block = false;
@@ -344,7 +351,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
         if (!last) r.bytes += rec & 0x1ffu;
       } else if (out && !last) {
         out[r.n] = rec;
-        if (kSeg) r.bytes += rec & 0x1ffu;
+        if (kSeg || kRec) r.bytes += rec & 0x1ffu;
       }
       r.n += last ? 0u : 1u;
       go = !last && p < limit;
@@ -525,6 +532,15 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
 #endif
       if (seg_target == rel && !g.is_sub[seg_tj]) break;  // that segment's decoder takes over
     }
+    if (kRec && (rec_count == 0u || out_bytes - rec_last >= rec.span)) {
+      if (tid == 0 && rec_count < rec.cap[sid]) {
+        uint64_t* pt = rec.points + 2u * (rec.off[sid] + rec_count);
+        pt[0] = pos - (uint64_t)mis * 8;
+        pt[1] = out_bytes;
+      }
+      rec_count++;
+      rec_last = out_bytes;
+    }
     const uint64_t hdr_at = pos;
     parse_header();
     if (kSeg) cur_hdr = hdr_at - (uint64_t)mis * 8;
@@ -572,7 +588,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
       // knows the reference's error for it).  One record a block, as before.  In segment mode a decoder stops at the
       // found start it lands on: a step goes no further than the next one (a found start inside a block's bytes is a
       // wrong guess and is run past with the block).
-      if (len == ZH_STORED_MAX && !final_block) {
+      if (!kRec && len == ZH_STORED_MAX && !final_block) {
         for (;;) {
           uint64_t seg_stop = ~0ull;  // (stream bit: the chain takes no block that starts at or behind it)
           if (kSeg) {
@@ -623,13 +639,13 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
               s_c_pos = (o + 5u + blen) * 8u;                             // behind the last block taken
               s_c_final = h & 1u;
             }
-            if (kSeg || kCount) {  // the bytes the records make (blocks 0 .. nfit - 1; an empty last one adds nothing)
+            if (kSeg || kCount || kRec) {  // the bytes the records make (blocks 0 .. nfit - 1; an empty last one adds nothing)
               const uint32_t made = zh_wave_sum(lane < nfit ? blen : 0u);
               if (lane == 0) s_wbytes[0] = made;
             }
           }
           __syncthreads();
-          if (kSeg || kCount) out_bytes += s_wbytes[0];
+          if (kSeg || kCount || kRec) out_bytes += s_wbytes[0];
           const uint32_t took = s_c_stored_len, nrec = s_c_endrel;
           const bool over = s_c_term != 0u;
           if (took) {
@@ -836,7 +852,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
       // scattered 4-byte stores of the speculative turns cost more than this second decode)
       uint32_t made = 0;
       if (active && r.n) made = run(std::true_type{}, my_start, limit, end_rel, kCount ? nullptr : tok + ntok + before).bytes;
-      if (kSeg || kCount) {
+      if (kSeg || kCount || kRec) {
         made = zh_wave_sum(made);
         if (lane == 0) s_wbytes[tid >> 6] = made;
         __syncthreads();
@@ -856,6 +872,14 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
   }
   if (tid == 0) {
     if (!kCount) tok[ntok] = kRecSpecial | kRecEnd | ((uint32_t)st << 16);
+    if (kRec) {  // the closing entry: the bit behind the final block's end-of-block code, the total
+      if (rec_count < rec.cap[sid]) {
+        uint64_t* pt = rec.points + 2u * (rec.off[sid] + rec_count);
+        pt[0] = pos - (uint64_t)mis * 8;
+        pt[1] = out_bytes;
+      }
+      rec.n[sid] = rec_count + 1u;
+    }
     if (kCount) {  // the sizing pass's answer (what zh_inflate_kernel leaves when it only counts)
       a.out_len[sid] = out_bytes;
       a.status[sid] = st;
@@ -1355,23 +1379,33 @@ static uint32_t zh_writer_width(uint32_t nbufs) {
 }
 
 extern "C" void zh_launch_inflate_tokens(hipStream_t stream, const uint8_t* d_src, ZhInflateArgs a,
-                                         uint32_t* tok_pool, const uint64_t* tok_off, const uint64_t* tok_cap) {
+                                         uint32_t* tok_pool, const uint64_t* tok_off, const uint64_t* tok_cap,
+                                         const ZhRecArgs* rec) {
   if (!a.nbufs) return;
+  if (rec) {  // an index build: the recording form, routed alike
+    if (zh_tokens_width(a.nbufs) == 1024u) {
+      hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, false, false, true>), dim3(a.nbufs), dim3(1024), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 1, *rec);
+    } else {
+      hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false, false, true>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 9, *rec);
+      hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false, false, true>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 8, *rec);
+    }
+    return;
+  }
   if (zh_tokens_width(a.nbufs) == 1024u)
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, false>), dim3(a.nbufs), dim3(1024), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 1);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, false>), dim3(a.nbufs), dim3(1024), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 1, ZhRecArgs{});
   else {  // (phase 9: the streams of one block, 8: the others -- see the kernel)
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 9);
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 8);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 9, ZhRecArgs{});
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, tok_pool, tok_off, tok_cap, ZhSegArgs{}, 8, ZhRecArgs{});
   }
 }
 // A sizing pass over a batch (count_only): the same routing, no token pool.
 extern "C" void zh_launch_inflate_count(hipStream_t stream, const uint8_t* d_src, ZhInflateArgs a) {
   if (!a.nbufs) return;
   if (zh_tokens_width(a.nbufs) == 1024u) {
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, false, true>), dim3(a.nbufs), dim3(1024), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 1);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, false, true>), dim3(a.nbufs), dim3(1024), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 1, ZhRecArgs{});
   } else {
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false, true>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 9);
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false, true>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 8);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false, true>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 9, ZhRecArgs{});
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false, true>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 8, ZhRecArgs{});
   }
 }
 // phase 0: sub-starts for the segments inside long blocks
@@ -1380,9 +1414,9 @@ extern "C" void zh_launch_seg_tokens(hipStream_t stream, const uint8_t* d_src, Z
                                      ZhSegArgs g, int phase) {
   if (!g.nsegs) return;
   if (g.nsegs <= 512u)  // (segments are short: a wide workgroup only pays while there is a CU for each or so)
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, true>), dim3(g.nsegs), dim3(1024), 0, stream, d_src, a, tok_pool, nullptr, nullptr, g, phase);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, true>), dim3(g.nsegs), dim3(1024), 0, stream, d_src, a, tok_pool, nullptr, nullptr, g, phase, ZhRecArgs{});
   else
-    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, true>), dim3(g.nsegs), dim3(256), 0, stream, d_src, a, tok_pool, nullptr, nullptr, g, phase);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, true>), dim3(g.nsegs), dim3(256), 0, stream, d_src, a, tok_pool, nullptr, nullptr, g, phase, ZhRecArgs{});
 }
 extern "C" void zh_launch_seg_write(hipStream_t stream, const uint8_t* d_src, ZhInflateArgs a, const uint32_t* tok_pool,
                                     ZhSegArgs g) {

@@ -462,7 +462,9 @@ static int run_uncompress(zh_plan* p, const uint8_t* d_src, uint8_t* d_dst) {
   const ZhInflateArgs& a = p->ia;
   prof_mark(p, "zh_unwrap_kernel");
   zh_launch_unwrap(s, d_src, a);
-  const bool split_ok = !p->indexed && inflate_split_enabled(ctx) && plan_token_pool(p);
+  // (an index build, zh_seek.hip, records its points in the tokens kernel: the split decode whatever the switch says)
+  const ZhRecArgs* const rec = p->rec.points ? &p->rec : nullptr;
+  const bool split_ok = !p->indexed && (inflate_split_enabled(ctx) || rec) && plan_token_pool(p);
   const bool split = split_ok && !a.count_only;
   ZhInflateArgs a1 = a;
   // both checksums: with dfDetect the format is only known per stream on the device
@@ -495,12 +497,12 @@ static int run_uncompress(zh_plan* p, const uint8_t* d_src, uint8_t* d_dst) {
       SideLane half(p, s);
       ZH_TRY(half.fork());
       half.mark("zh_inflate_tokens_kernel");
-      zh_launch_inflate_tokens(half.side, d_src, ah[1], p->tok_pool, p->tok_off, p->tok_cap);
+      zh_launch_inflate_tokens(half.side, d_src, ah[1], p->tok_pool, p->tok_off, p->tok_cap, rec);
       half.mark("zh_inflate_write_kernel");
       zh_launch_inflate_write(half.side, d_src, d_dst, ah[1], p->tok_pool, p->tok_off);
       ZH_TRY(half.done());
       prof_mark(p, "zh_inflate_tokens_kernel");
-      zh_launch_inflate_tokens(s, d_src, ah[0], p->tok_pool, p->tok_off, p->tok_cap);
+      zh_launch_inflate_tokens(s, d_src, ah[0], p->tok_pool, p->tok_off, p->tok_cap, rec);
       prof_mark(p, "zh_inflate_write_kernel");
       zh_launch_inflate_write(s, d_src, d_dst, ah[0], p->tok_pool, p->tok_off);
       // (the first half's output is complete: its checksum pieces fill what the second half's tail leaves idle
@@ -515,7 +517,7 @@ static int run_uncompress(zh_plan* p, const uint8_t* d_src, uint8_t* d_dst) {
       ZH_TRY(half.join());
     } else if (p->tok_groups.size() <= 1) {
       prof_mark(p, "zh_inflate_tokens_kernel");
-      zh_launch_inflate_tokens(s, d_src, a1, p->tok_pool, p->tok_off, p->tok_cap);
+      zh_launch_inflate_tokens(s, d_src, a1, p->tok_pool, p->tok_off, p->tok_cap, rec);
       prof_mark(p, "zh_inflate_write_kernel");
       zh_launch_inflate_write(s, d_src, d_dst, a1, p->tok_pool, p->tok_off);
     } else {
@@ -524,7 +526,7 @@ static int run_uncompress(zh_plan* p, const uint8_t* d_src, uint8_t* d_dst) {
         ag.first_buf = g.first;
         ag.nbufs = g.second;
         prof_mark(p, "zh_inflate_tokens_kernel");
-        zh_launch_inflate_tokens(s, d_src, ag, p->tok_pool, p->tok_off, p->tok_cap);
+        zh_launch_inflate_tokens(s, d_src, ag, p->tok_pool, p->tok_off, p->tok_cap, rec);
         prof_mark(p, "zh_inflate_write_kernel");
         zh_launch_inflate_write(s, d_src, d_dst, ag, p->tok_pool, p->tok_off);
       }

@@ -477,6 +477,302 @@ def check_call_errors(eng):
     assert eng.seek_read_ranges([], [], []) == ([], [])
 
 
+# ---- points at any block boundary: histories of any length (the engine itself only builds with span >= 32768) ----
+def every_block(j, b):
+    return True
+
+
+def one_in_four(seed):
+    """a seeded subset: every block start kept with probability 1/4"""
+    rng = random.Random(seed)
+    return lambda j, b: rng.random() < 0.25
+
+
+def youngest(data, fmt):
+    """the first block and the single block start with the largest out_off below 32768 (none: the first block alone)"""
+    blocks = sm.walk(data, sm.resolve_format(data, fmt))[1]
+    young = [j for j, b in enumerate(blocks) if j and 0 < b[1] < sm.WINDOW]
+    pick = max(young, key=lambda j: (blocks[j][1], -j)) if young else None
+    return lambda j, b: j == pick
+
+
+def dense_streams(small=False):
+    """[(stream, format, source)]"""
+    out = [(family(-15)[1], sm.DF_DEFLATE, mix()), (double_flush(), sm.DF_DEFLATE, mix()[:100000])]
+    if not small:
+        out += [(family(15)[2], sm.DF_ZLIB, mix()), (family(31)[3], sm.DF_GZIP, mix())]
+        out += [(d, fmt, mix()[:70000 if fmt == sm.DF_DEFLATE else 150000]) for d, fmt in flushed_streams()]
+        out += [(zeros_stream(), sm.DF_ZLIB, bytes(1 << 20))]
+    return out
+
+
+def dense_point_sets(small=False):
+    """[(name, [blob a stream of dense_streams()])]: every block start, three seeded quarters, the youngest"""
+    streams = dense_streams(small)
+    sets = [("every block", [every_block] * len(streams))]
+    sets += [("a quarter, seed %d" % seed, [one_in_four(1000 * seed + s) for s in range(len(streams))]) for seed in (1, 2, 3)]
+    sets += [("the youngest", [youngest(d, fmt) for d, fmt, _ in streams])]
+    return [(name, [sm.index_at(d, fmt, keep)[0] for (d, fmt, _), keep in zip(streams, keeps)]) for name, keeps in sets]
+
+
+def dense_ranges(s, blob):
+    """The read cases of one stream under one point set: the whole stream; two bytes across a point at up to 64
+    points, every point with a window shorter than 32768 among them; a range strictly inside each of the first four
+    intervals; a range across an empty interval where there is one."""
+    b = sm.Blob(blob)
+    offs = [p[1] for p in b.points]
+    out = [(s, 0, b.total)]
+    inner = [k for k in range(1, b.n_points - 1) if offs[k] > 0]
+    short = [k for k in inner if b.points[k][3] < sm.WINDOW]
+    assert len(short) <= 64
+    rest = [k for k in inner if b.points[k][3] == sm.WINDOW]
+    room = 64 - len(short)
+    picked = short + (rest if len(rest) <= room else [rest[(2 * i + 1) * len(rest) // (2 * room)] for i in range(room)])
+    out += [(s, offs[k] - 1, 2) for k in sorted(set(picked))]
+    for k in range(min(4, b.n_points - 1)):
+        if offs[k + 1] - offs[k] >= 3:
+            out.append((s, offs[k] + 1, min(100, offs[k + 1] - offs[k] - 2)))
+    empty = [k for k in range(1, b.n_points - 1) if offs[k] == offs[k + 1] and 3 <= offs[k] <= b.total - 4]
+    if empty:
+        out.append((s, offs[empty[0]] - 3, 7))
+    return out
+
+
+def check_dense(eng, small=False):
+    """one read call a point set, all streams in it; the bytes, and the upload and the intervals decoded by the model"""
+    streams = dense_streams(small)
+    for name, blobs in dense_point_sets(small):
+        bs = [sm.Blob(b) for b in blobs]
+        ranges = [r for s in range(len(streams)) for r in dense_ranges(s, blobs[s])]
+        # (... and the short ranges once more in a call of their own: beside a range of the whole stream every span
+        # is part of that range's, and the upload says nothing of where a short range's span begins)
+        for rs in (ranges, [r for r in ranges if r[2] != bs[r[0]].total]):
+            check_read(eng, [src for _, _, src in streams], [d for d, _, _ in streams], blobs, rs)
+            up, in_place, via = eng.debug_range_stats()
+            assert up == sm.upload_bytes(bs, [len(d) for d, _, _ in streams], rs), name
+            assert in_place == 0 and via == sum(len(sm.decoded(bs[s], o, n)) for s, o, n in rs), name
+
+
+# ---- the hand-built streams of tests/parity_cases.py through both seek kernels ----
+HISTORIES = (1, 17, 4097, 32767, 32768)
+
+
+def parity_crafted(small):
+    import parity_cases as pc
+    return pc.crafted_streams(small)
+
+
+def check_crafted_all(eng, small=False):
+    """all of them in one build: an accepted stream's blob and data are the model's and the builder's, a rejected one
+    has none and the status uncompress_batch gives it in the same batch"""
+    cases = parity_crafted(small)
+    raws = [c[1] for c in cases]
+    blobs, sts, outs = build(eng, raws, sm.DF_DEFLATE, SPAN)
+    _, want_sts = eng.uncompress_batch(raws, sm.DF_DEFLATE)
+    assert sts == want_sts
+    n_good = 0
+    for (name, raw, plain, _), blob, st, out in zip(cases, blobs, sts, outs):
+        if plain is None:
+            assert st != OK and blob is None and out is None, name
+            continue
+        n_good += 1
+        assert st == OK and out == plain, (name, st)
+        want_blob, want_plain = model(raw, sm.DF_DEFLATE)
+        assert want_plain == plain and blob == want_blob, (name, sm.Blob(blob).points[:3], sm.Blob(want_blob).points[:3])
+    assert 0 < n_good < len(cases)
+    if not small:  # (the chain of 258-byte matches outgrows the room a raw stream is given: the sizing pass runs)
+        big = [c for c in cases if c[0] == "W2/chain_len258_dist1"][0]
+        assert len(big[2]) > 4 * len(big[1]) + 65536
+
+
+def behind_history(small=False):
+    """Every accepted crafted stream behind a non-final stored block of H filler bytes (a stored block ends at a byte
+    boundary: the concatenation is a stream, its plaintext filler + plaintext) -> [(name, H, stream, plaintext)]"""
+    out = []
+    good = [c for c in parity_crafted(small) if c[2] is not None]
+    for i, (name, raw, plain, _) in enumerate(good):
+        h = 4097 if small else HISTORIES[i % len(HISTORIES)]
+        filler = mix()[2000 + i:2000 + i + h]
+        s = dc.Stream()
+        s.stored(filler, False)
+        head, _, status = s.finish()
+        assert status is None and len(head) == 5 + h
+        out.append((name, h, head + raw, filler + plain))
+    return out
+
+
+def check_crafted_behind_history(eng, small=False):
+    """indexed at every block start: the crafted body decodes through the seek decoder with a history of min(H, 32768)
+    bytes and a stop bit; and the same streams through the build"""
+    cases = behind_history(small)
+    streams = [c[2] for c in cases]
+    blobs = [sm.index_at(d, sm.DF_DEFLATE, every_block)[0] for d in streams]
+    ranges = [r for s, (_, h, _, plain) in enumerate(cases) for r in ((s, 0, len(plain)), (s, h - 1, 2), (s, h, 300))]
+    check_read(eng, [c[3] for c in cases], streams, blobs, ranges)
+    del blobs
+    got, sts, outs = build(eng, streams, sm.DF_DEFLATE, SPAN)
+    for (name, _, d, plain), blob, st, out in zip(cases, got, sts, outs):
+        assert st == OK and out == plain and blob == sm.build_index(d, sm.DF_DEFLATE, SPAN)[0], (name, st)
+
+
+# ---- a match at, and one past, the window's first byte ----
+def edge_code(long_dist=False):
+    """A complete dynamic code zlib accepts: every literal, the end of block, lengths 3 and 258, all 30 distances.
+    long_dist: the distance codes the cases use are 12 and 13 bits long, beyond the decoders' distance tables (8
+    bits) -- such a match is no part of a round, the decode wave hands it over alone."""
+    lit = [8] * 254 + [9, 9, 9, 10] + [0] * 27 + [10]
+    dist = [4] * 2 + [5] * 28
+    if long_dist:
+        dist = [12] * 3 + [1, 2, 3, 4, 5, 6, 7, 8] + [12] * 7 + [13] * 12
+        assert all(dist[k] > 8 for k in (0, 1, 2, 12, 16, 24, 29))
+    assert len(lit) == 286 and len(dist) == 30 and dc.kraft(lit) == 32768 and dc.kraft(dist) == 32768
+    return lit, dist
+
+
+@functools.lru_cache(maxsize=None)
+def window_edge_cases():
+    """A stored block of P bytes, then one final block of j literals and a match of distance P + j -- it reaches output
+    byte 0 --, a literal and the end of block; the final block fixed, dynamic, and dynamic with distance codes too long
+    for the decoders' tables -> [(name, P, stream, plaintext)]"""
+    out = []
+    filler = mix()[5000:5000 + SPAN]
+    for kind in ("fixed", "dynamic", "long distance codes"):
+        for p in (1, 2, 258, 4097, 32767, 32768):
+            for j in (0, 1, 70):
+                if p + j > 32768:
+                    continue
+                for length in (3, 258):
+                    s = dc.Stream()
+                    s.stored(filler[:p], False)
+                    if kind == "fixed":
+                        s.fixed_block(True)
+                    else:
+                        s.dynamic_block(*edge_code(kind != "dynamic"), True)
+                    _lits(s, bytes((7 * i + 3) & 0xff for i in range(j)))
+                    s.match(length, p + j)
+                    s.lit(0x21)
+                    s.eob()
+                    raw, plain, status = s.finish()
+                    assert status is None and len(plain) == p + j + length + 1
+                    out.append(("%s P=%d j=%d len=%d" % (kind, p, j, length), p, raw, plain))
+    assert len(out) == 90
+    return out
+
+
+def honest_blob(raw):
+    return sm.index_at(raw, sm.DF_DEFLATE, every_block)[0]
+
+
+def forged_past(raw):
+    """Every out_off behind point 0 lowered by one, the plaintext without its first byte: it passes every static rule;
+    interval 1 has a window of min(P, 32768) - 1 bytes, and its match reaches one byte beyond it; interval 0 makes one
+    byte more than promised."""
+    plain, blocks, end_bit = sm.walk(raw, sm.DF_DEFLATE)
+    assert len(blocks) == 2
+    points = [blocks[0], (blocks[1][0], blocks[1][1] - 1), (end_bit, len(plain) - 1)]
+    return sm.write_blob(sm.DF_DEFLATE, len(raw), SPAN, points, plain[1:])
+
+
+def check_window_edge(eng):
+    """One call.  Every forged range lies behind sound ranges of another stream: a forged interval's slot is never
+    the scratch's first, so a decoder that read before its slot would read inside the allocation and be seen by its
+    status or its bytes."""
+    streams, srcs, blobs, ranges, bad = [], [], [], [], {}
+    for name, p, raw, plain in window_edge_cases():
+        s = len(streams)
+        streams += [raw, raw]
+        srcs += [plain, plain[1:]]
+        blobs += [honest_blob(raw), forged_past(raw)]
+        ranges += [(s, 0, len(plain)), (s, p - 1, 2), (s, p, 5)]
+        forged = [(s + 1, p - 1, 3), (s + 1, 0, len(plain))] + ([(s + 1, 0, 1)] if p > 1 else [])
+        for r in forged:
+            bad[len(ranges)] = -1
+            ranges.append(r)
+    check_read(eng, srcs, streams, blobs, ranges, bad)
+
+
+# ---- a clean decode of the wrong length ----
+@functools.lru_cache(maxsize=None)
+def short_interval_case(k=20):
+    """Every block of the stream a point but block k + 1, and point k's bit_off that of block k + 1: interval k parses
+    cleanly from there to its stop bit and makes fewer bytes than it promises; interval k - 1 runs on through block k.
+    (With block k + 1 a point as well the two bit_offs would be equal, which no decoder gets to see.)
+    -> (stream, blob, k)"""
+    data = family(-15)[3]
+    blocks = sm.walk(data, sm.DF_DEFLATE)[1]
+    d = sm.Blob(sm.index_at(data, sm.DF_DEFLATE, lambda j, b: j != k + 1)[0])
+    assert d.points[k][0] == blocks[k][0] and d.points[k + 1][0] == blocks[k + 2][0]
+    d.points[k][0] = blocks[k + 1][0]
+    return data, d.pack(), k
+
+
+def check_short_interval(eng):
+    data, blob, k = short_interval_case()
+    b = sm.Blob(blob)
+    offs = [p[1] for p in b.points]
+    ranges = [(0, offs[j] + 1, 20) for j in range(b.n_points - 1)] + [(0, offs[k - 1] - 1, 2), (0, offs[k + 1] - 1, 2)]
+    bad = {k - 1: INVALID_BUFFER, k: INVALID_BUFFER, len(ranges) - 2: INVALID_BUFFER, len(ranges) - 1: INVALID_BUFFER}
+    check_read(eng, [mix()], [data], [blob], ranges, bad)
+
+
+# ---- a batch beyond the wide kernels' reach ----
+@functools.lru_cache(maxsize=None)
+def batch800():
+    """800 streams of both detectable containers: 734 of 0 to 3000 source bytes (eight of none, some stored, some with
+    a flush in the middle; one of them with a damaged trailer), 66 of 100 to 140 KB at the settings of FAMILY (one of
+    them truncated) -> (streams, sources, the two bad ones)"""
+    rng = random.Random(800)
+    jobs = []
+    for i in range(734):
+        n = 0 if i < 8 else rng.randrange(1, 3001)
+        o = rng.randrange(len(mix()) - 3000)
+        jobs.append((mix()[o:o + n], rng.choice((0, 0, 1, 6, 6, 9)), 8, n // 2 if 8 <= i < 60 and n >= 200 else 0))
+    for i in range(66):
+        n = 100000 + 601 * i
+        lv, mem = FAMILY[i % 4]
+        jobs.append((mix()[1000 * i:1000 * i + n], lv, mem, 0))
+    rng.shuffle(jobs)
+    streams, srcs = [], []
+    for i, (src, lv, mem, flush_every) in enumerate(jobs):
+        streams.append(deflate(src, lv, 31 if i % 3 else 15, mem, flush_every))
+        srcs.append(src)
+    hurt = next(i for i, s in enumerate(srcs) if 0 < len(s) <= 3000 and i % 3)  # (gzip: its CRC-32)
+    cut = next(i for i, s in enumerate(srcs) if len(s) >= 100000)
+    bad = bytearray(streams[hurt])
+    bad[-6] ^= 0x40
+    streams[hurt] = bytes(bad)
+    streams[cut] = streams[cut][:len(streams[cut]) * 2 // 3]
+    return streams, srcs, (hurt, cut)
+
+
+def check_batch800(eng, monkeypatch):
+    """The index build's narrow recording kernels (batches above ZH_INFLATE_WIDE streams, 768 unless set: the
+    library reads it once a process, so it is asserted here, not set)."""
+    assert int(os.environ.get("ZH_INFLATE_WIDE", "768")) < 800
+    streams, srcs, bad = batch800()
+    blobs, sts, outs = build(eng, streams, sm.DF_DETECT, SPAN)
+    _, want_sts = eng.uncompress_batch(streams, sm.DF_DETECT)
+    assert sts == want_sts and sts.count(OK) == 798
+    want = [None if i in bad else model(d, sm.DF_DETECT)[0] for i, d in enumerate(streams)]
+    for i in range(800):
+        if i in bad:
+            assert sts[i] != OK and blobs[i] is None and outs[i] is None, i
+        else:
+            assert blobs[i] == want[i] and outs[i] == srcs[i], i
+    ranges, badr = [], {}
+    for s in range(800):
+        if s in bad:
+            badr[len(ranges)] = INVALID_BUFFER
+            ranges.append((s, 0, 10))
+            continue
+        b = sm.Blob(want[s])
+        ranges.append((s, b.points[1][1] - 1, 2) if b.n_points > 2 else (s, len(srcs[s]) // 3, 50))
+    check_read(eng, srcs, streams, blobs, ranges, badr)
+    monkeypatch.setenv("ZH_SEEK_FIRST_CAP", "2")
+    again, sts2 = eng.seek_index_batch(streams, sm.DF_DETECT, SPAN)
+    assert again == want and sts2 == sts
+
+
 # ---- the sanitized program's cases ----
 def dump(path):
     """Writes the cases of tests/seek_main.cpp: cases.txt "NAME STREAMS FORMAT SPAN" a line; NAME_<s>.bin the stream,
@@ -540,6 +836,18 @@ def dump(path):
     rs, touching = neighbour_ranges(0, b, k)
     ranges = [r + ((CHECKSUM if st == CHECKSUM else -1) if j in touching else OK,) for j, r in enumerate(rs)]
     put("flipped", -1, SPAN, [bytes(flipped)], [mix()], [None], [blob], ranges)
+    # points at every block start, empty intervals among them
+    d, fmt, src = dense_streams(True)[1]
+    blob = dense_point_sets(True)[0][1][1]
+    put("dense", -1, SPAN, [d], [src], [None], [blob], [r + (OK,) for r in dense_ranges(0, blob)])
+    # a match one byte past the window: the forged range first and alone, its slot the scratch's first
+    name, p, raw, plain = next(c for c in window_edge_cases() if c[0] == "dynamic P=4097 j=1 len=258")
+    put("past", -1, SPAN, [raw], [plain[1:]], [None], [forged_past(raw)], [(0, p - 1, 3, -1)])
+    # a clean decode of the wrong length
+    data, blob, k = short_interval_case()
+    offs = [q[1] for q in sm.Blob(blob).points]
+    ranges = [(0, offs[j] + 1, 20, INVALID_BUFFER if j in (k - 1, k) else OK) for j in range(k - 2, k + 2)]
+    put("swap", -1, SPAN, [data], [mix()], [None], [blob], ranges)
     with open(os.path.join(path, "cases.txt"), "w") as f:
         f.write("\n".join(cases) + "\n")
     return len(cases), n_ranges

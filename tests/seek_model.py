@@ -3,6 +3,7 @@ from RFC 1951 and the header's prose: an inflate that starts at any bit position
 bit and reports every block start; the point rule; the blob writer and reader; the arithmetic of a range read (the
 intervals a range touches, the bytes its upload carries).  No engine and no zlib in here: tests/test_seek_model.py
 holds it against zlib.decompress."""
+import functools
 import struct
 import zlib
 
@@ -305,3 +306,56 @@ def upload_bytes(blobs, src_lens, ranges):
     for _, lo, hi in merged:
         total = pad16(total) + hi - lo
     return total
+
+
+@functools.lru_cache(maxsize=64)
+def walk(data, fmt):
+    """inflate() of a whole stream of a resolved format, made once a stream: (plaintext, block starts, end bit)"""
+    return inflate(data, body_bit(data, fmt))
+
+
+def index_at(data, fmt, keep, span=WINDOW):
+    """The blob whose points are the first block and the true block starts j = 1, 2 .. for which keep(j, (bit_off,
+    out_off)) holds, and the closing entry -- whatever the point rule would choose.  -> (blob, plaintext)"""
+    fmt = resolve_format(data, fmt)
+    plain, blocks, end_bit = walk(data, fmt)
+    points = [b for j, b in enumerate(blocks) if j == 0 or keep(j, b)]
+    return write_blob(fmt, len(data), span, points + [(end_bit, len(plain))], plain), plain
+
+
+def sound(blob, src_len):
+    """The rules of include/zippy_hip.h for a blob that can be right, one by one in the order of its prose: what a
+    reader may say of a blob without decoding anything."""
+    if len(blob) < 64:
+        return False
+    magic, version, _, _, _, _, n_points, window_bytes, _ = struct.unpack_from("<8sIIQQQQQQ", blob, 0)
+    if magic != MAGIC or version != 1:
+        return False
+    if len(blob) != 64 + 32 * n_points + window_bytes:          # a length that does not match its own counts
+        return False
+    b = Blob(blob)
+    if b.src_len != src_len or b.n_points < 2:
+        return False
+    p = b.points
+    if p[0][1] != 0 or p[-1][1] != b.total:                     # (the closing entry holds `total`)
+        return False
+    for k, (bit_off, out_off, win_off, win_len, _) in enumerate(p):
+        closing = k + 1 == len(p)
+        if bit_off > 8 * src_len if closing else bit_off >= 8 * src_len:
+            return False
+        if win_len != (0 if closing else min(out_off, WINDOW)):
+            return False
+        if win_off % 16 or win_off + pad16(win_len) > b.window_bytes:
+            return False
+        if closing:
+            break
+        if p[k + 1][0] <= bit_off or p[k + 1][1] < out_off:     # bit_off strictly rising, out_off not falling
+            return False
+        if p[k + 1][1] - out_off > 1032 * ((p[k + 1][0] + 7) // 8 - bit_off // 8) + 64:
+            return False
+    return True
+
+
+def decoded(blob, off, length):
+    """the intervals of a range the engine decodes: those it touches that are not empty"""
+    return [k for k in blob.touched(off, length) if blob.points[k + 1][1] > blob.points[k][1]]

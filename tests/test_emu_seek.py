@@ -88,3 +88,24 @@ def test_emu_seek_api(eng, monkeypatch):
     assert sts[0] == 0 and sts[1] != 0 and blobs == [blob, None]
     outs, sts = api.seek_read_ranges([data], [blob], [(0, 5, 10)])
     assert (outs, sts) == ([sc.mix()[5:15]], [0])
+
+
+# ---- points at any block boundary (histories of any length), the hand-built streams, forged windows ----
+def test_emu_seek_dense_point_sets(eng):
+    sc.check_dense(eng, small=True)
+
+
+def test_emu_seek_crafted_streams_build(eng):
+    sc.check_crafted_all(eng, small=True)
+
+
+def test_emu_seek_crafted_behind_history(eng):
+    sc.check_crafted_behind_history(eng, small=True)
+
+
+def test_emu_seek_window_edge(eng):
+    sc.check_window_edge(eng)
+
+
+def test_emu_seek_short_interval(eng):
+    sc.check_short_interval(eng)

@@ -73,3 +73,29 @@ def test_gpu_seek_damaged_window_and_point(eng):
 def test_gpu_seek_static_damage_and_call_errors(eng):
     sc.check_static_damage(eng)
     sc.check_call_errors(eng)
+
+
+# ---- points at any block boundary (histories of any length), the hand-built streams, forged windows ----
+def test_gpu_seek_dense_point_sets(eng):
+    sc.check_dense(eng)
+
+
+def test_gpu_seek_crafted_streams_build(eng):
+    sc.check_crafted_all(eng)
+
+
+def test_gpu_seek_crafted_behind_history(eng):
+    sc.check_crafted_behind_history(eng)
+
+
+def test_gpu_seek_window_edge(eng):
+    sc.check_window_edge(eng)
+
+
+def test_gpu_seek_short_interval(eng):
+    sc.check_short_interval(eng)
+
+
+def test_gpu_seek_batch_of_800(eng, monkeypatch):
+    """above ZH_INFLATE_WIDE streams the build takes the narrow recording kernels, which the emulator alone ran so far"""
+    sc.check_batch800(eng, monkeypatch)

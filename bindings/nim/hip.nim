@@ -703,3 +703,40 @@ proc hipSeekReadRange*(src, index: string, off, len: uint64): string {.raises: [
   let rc = zh_seek_read_ranges(engine(), p.addr, slen.addr, 1, ip.addr, ilen.addr, 1, ri.addr, ro.addr, rl.addr,
                                dst.addr, dstLen.addr, st.addr)
   take(dst, dstLen, if rc != 0: rc else: st.cint)
+
+# ---- any gzip file: several members, FEXTRA / FNAME / FCOMMENT / FHCRC (no counterpart in the reference) ----
+type
+  ZhGzipMember* {.bycopy.} = object
+    coff*, cdataOff*, cdataLen*: uint64  # in the file: first header byte, first deflate byte, deflate bytes
+    uoff*, ulen*: uint64                 # in the uncompressed data
+    crc*, isize*, mtime*: uint32         # trailer, header
+    flg*, xfl*, os*, pad*: uint8
+    extraOff*, extraLen*, nameOff*, nameLen*, commentOff*, commentLen*: uint32  # from coff; 0 / 0 when absent
+
+proc zh_gzip_read_batch(ctx: ZhCtx, images: ptr pointer, lens: ptr csize_t, n: csize_t, dsts: ptr pointer,
+                        dstLens: ptr csize_t, statuses: ptr int32, members: ptr ptr ZhGzipMember,
+                        first: ptr csize_t): cint {.importc, cdecl, dynlib: zhLib.}
+proc zh_debug_gzip_stats(ctx: ZhCtx, candidates, speculativeBytes,
+                         frontierRounds: ptr uint64): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc uncompressGzipFile*(image: string): string {.raises: [ZippyError].} =
+  ## the uncompressed data of a gzip file of any shape: its members' data back to back (cat a.gz b.gz, appended logs,
+  ## pigz -i, .warc.gz; FEXTRA, FNAME, FCOMMENT, FHCRC), every member verified by its CRC-32 and ISIZE
+  var p = if image.len > 0: image[0].unsafeAddr.pointer else: nil
+  var len = image.len.csize_t
+  var dst: pointer; var dstLen: csize_t; var st: int32
+  let rc = zh_gzip_read_batch(engine(), p.addr, len.addr, 1, dst.addr, dstLen.addr, st.addr, nil, nil)
+  take(dst, dstLen, if rc != 0: rc else: st.cint)
+
+proc hipGzipMembers*(image: string): seq[ZhGzipMember] {.raises: [ZippyError].} =
+  ## the members of a gzip file, each decoded and verified on the device; no data comes down
+  var p = if image.len > 0: image[0].unsafeAddr.pointer else: nil
+  var len = image.len.csize_t
+  var mem: ptr ZhGzipMember; var first: array[2, csize_t]; var st: int32
+  let rc = zh_gzip_read_batch(engine(), p.addr, len.addr, 1, nil, nil, st.addr, mem.addr, first[0].addr)
+  if rc == 0 and st == 0 and first[1] > 0:
+    result = newSeq[ZhGzipMember](first[1].int)
+    copyMem(result[0].addr, mem, first[1].int * sizeof(ZhGzipMember))
+  if mem != nil: zh_free(mem)
+  if rc != 0 or st != 0:
+    raise newException(ZippyError, $zh_strerror(if rc != 0: rc else: st.cint))

@@ -472,6 +472,65 @@ int zh_bgzf_read_ranges(zh_ctx *ctx, const void *const *images, const size_t *le
                         void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
+ * Any gzip file (RFC 1952): several members back to back (cat a.gz    *
+ * b.gz, appended logs, pigz -i, .warc.gz), FEXTRA, FNAME, FCOMMENT    *
+ * and FHCRC fields -- what every gunzip reads.  zh_uncompress* keeps  *
+ * the reference's contract (one member, no FEXTRA, the trailer the    *
+ * image's last eight bytes); this call is the way to read the rest.   *
+ * A plain member does not say how long it is: every position that     *
+ * could start one is sized on the device at once, and the chain from  *
+ * byte 0 is proved afterwards.  Host buffers in, library-allocated    *
+ * results out (zh_free), as in zh_bgzf_read_batch.                    *
+ * ------------------------------------------------------------------ */
+/* One reached member.  coff, cdata_off, cdata_len: in the image -- its first header byte, its first deflate byte, its
+ * deflate bytes (whole bytes); uoff, ulen: in the image's uncompressed data; crc, isize: its trailer; mtime, flg, xfl,
+ * os: its header, reported and not judged; the optional fields' places count from coff, lengths without the closing
+ * NUL, 0 / 0 for a field that is absent (FEXTRA's are the bytes behind XLEN; subfields are not interpreted). */
+typedef struct zh_gzip_member {
+  uint64_t coff, cdata_off, cdata_len;
+  uint64_t uoff, ulen;
+  uint32_t crc, isize, mtime;
+  uint8_t flg, xfl, os, pad;
+  uint32_t extra_off, extra_len, name_off, name_len, comment_off, comment_len;
+} zh_gzip_member;
+
+/* The uncompressed data of every image: its members' data back to back.  dsts / dst_lens may both be NULL: the members
+ * are still decoded and verified on the device, no data comes down.  members / first (n + 1 values) may both be NULL;
+ * else *members (zh_free) holds the lists of all images back to back, image i's members are members[first[i] ..
+ * first[i + 1]) (an image that failed has none).  NULL images / lens / statuses with n > 0, or one of a pair without
+ * the other: ZH_ERR_ARGUMENT.  The return value is ZH_OK unless the call as a whole could not run; an image that
+ * failed gives NULL / 0 and does not disturb its neighbours.
+ * The member at position p of an image, in this order, the first failure decides:
+ *   1. fewer than 18 bytes left: ZH_ERR_INVALID_BUFFER;
+ *   2. ID bytes: ZH_ERR_GZIP_ID;  3. CM != 8: ZH_ERR_UNSUPPORTED_METHOD;  4. FLG & 0xe0: ZH_ERR_RESERVED_FLAGS;
+ *   5. FEXTRA: 12 + XLEN beyond the image ZH_ERR_INVALID_BUFFER;
+ *   6. FNAME, then FCOMMENT: no NUL before the image's end ZH_ERR_INVALID_BUFFER;
+ *   7. FHCRC: its two bytes beyond the image ZH_ERR_INVALID_BUFFER (it is verified below);
+ *   8. a header of more than 4 GiB (the fields' places are 32 bits wide): ZH_ERR_INVALID_BUFFER.
+ * The deflate stream runs from cdata_off to its own final block: the decoder's statuses are those of
+ * zh_uncompress(.., ZH_DF_DEFLATE), its input is bounded by the image's end minus 8, and the member ends at the final
+ * block's last byte plus the 8 trailer bytes (beyond the image: ZH_ERR_INVALID_BUFFER).  Where a member ends, the
+ * image ends too (a clean end), or all remaining bytes are zero (a clean end: tape and block padding, as gzip and
+ * Python's gzip accept it), or a member must start there and the checks above give the status.  An image of 0 bytes
+ * gives ZH_OK, 0 bytes and 0 members; zeros alone are no member (ZH_ERR_GZIP_ID from 18 bytes on).
+ * Every reached member is settled by the first of these that applies: its header's status; the decoder's; FHCRC, when
+ * present, against the low 16 bits of the CRC-32 of the header bytes before it (ZH_ERR_CHECKSUM); the CRC-32 of its
+ * data against the trailer's (ZH_ERR_CHECKSUM); ulen mod 2^32 against ISIZE (ZH_ERR_SIZE); what stands behind it.  An
+ * image's status is that of its first failing member in file order.
+ * The sizing of candidates that are no members is bounded: a workgroup of the pass stops once the pass's workgroups
+ * together have paid ZH_GZIP_SPEC_BYTES input bytes (the environment; default 2 x the call's image bytes + 64 MiB).  A
+ * workgroup pays, and looks, where it reads a block header or stages a superchunk, so the pass reads at most the budget
+ * plus what every workgroup resident on the device consumes between two looks: 64 KiB, 65540 bytes for a full stored
+ * block.  The members the chain still needs are then sized one round of the chain's ends at a time -- the same
+ * results.  The searches for the NUL of FNAME / FCOMMENT pay into the same sum, 4 KiB at a time: an image without a
+ * zero byte cannot buy more header reading than that either. */
+int zh_gzip_read_batch(zh_ctx *ctx, const void *const *images, const size_t *lens, size_t n, void **dsts,
+                       size_t *dst_lens, int32_t *statuses, zh_gzip_member **members, size_t *first);
+/* The last zh_gzip_read_batch of the context: the positions sized as members, the input bytes the budgeted sizing pass
+ * consumed, the rounds that sized chain ends the budget had left out. */
+int zh_debug_gzip_stats(zh_ctx *ctx, uint64_t *candidates, uint64_t *speculative_bytes, uint64_t *frontier_rounds);
+
+/* ------------------------------------------------------------------ *
  * Seek indexes for FOREIGN deflate streams (zlib, pigz, gzip, zip     *
  * entries: every block reaches up to 32 KiB back into the one before) *
  * -- the idea of zlib's zran.c: decode the stream once, keep at       *

@@ -114,6 +114,11 @@ _SIGS = {
                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
                                        _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
+    "zh_gzip_read_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                      _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32),
+                                      _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t)]),
+    "zh_debug_gzip_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                       _c.POINTER(_c.c_uint64)]),
     "zh_seek_index_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                        _c.c_int, _c.c_uint64, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
                                        _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
@@ -179,6 +184,19 @@ _SIGS = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)  # every entry point include/zippy_hip.h declares
+
+
+class GzipMember(_c.Structure):
+    """zh_gzip_member (include/zippy_hip.h)"""
+    _fields_ = [("coff", _c.c_uint64), ("cdata_off", _c.c_uint64), ("cdata_len", _c.c_uint64),
+                ("uoff", _c.c_uint64), ("ulen", _c.c_uint64),
+                ("crc", _c.c_uint32), ("isize", _c.c_uint32), ("mtime", _c.c_uint32),
+                ("flg", _c.c_uint8), ("xfl", _c.c_uint8), ("os", _c.c_uint8), ("pad", _c.c_uint8),
+                ("extra_off", _c.c_uint32), ("extra_len", _c.c_uint32), ("name_off", _c.c_uint32),
+                ("name_len", _c.c_uint32), ("comment_off", _c.c_uint32), ("comment_len", _c.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "pad"}
 
 
 def load_library(path):
@@ -957,6 +975,47 @@ class Engine:
                     self.lib.zh_free(dsts[r])
         self._check(rc)
         return outs, list(sts)[:nr]
+
+    # ---- any gzip file: several members, FEXTRA / FNAME / FCOMMENT / FHCRC ----
+    def gzip_read_batch(self, images, want_data=True, want_members=True):
+        """The uncompressed data and the members of gzip files of any shape (zh_gzip_read_batch) -> (list of bytes |
+        None, statuses, members); members[i]: image i's list of dicts with zh_gzip_member's fields, None where the
+        image failed.  want_data=False: every member is still decoded and verified, no data comes down (outputs are
+        None); want_members=False: members is None."""
+        n = len(images)
+        keep = [bytes(b) for b in images]
+        srcs = (_c.c_void_p * max(1, n))(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * max(1, n))(*[len(k) for k in keep])
+        dsts = (_c.c_void_p * max(1, n))() if want_data else None
+        dlens = (_c.c_size_t * max(1, n))() if want_data else None
+        sts = (_c.c_int32 * max(1, n))()
+        mem = _c.c_void_p() if want_members else None
+        first = (_c.c_size_t * (n + 1))() if want_members else None
+        rc = self.lib.zh_gzip_read_batch(self._h, srcs, lens, n, dsts, dlens, sts, _c.byref(mem) if want_members else None,
+                                         first)
+        outs, members = [None] * n, None
+        try:
+            for i in range(n):
+                if want_data and dsts[i] and sts[i] == 0:
+                    outs[i] = _c.string_at(dsts[i], dlens[i])
+            if want_members and rc == 0:
+                arr = _c.cast(mem, _c.POINTER(GzipMember))
+                members = [[arr[k].as_dict() for k in range(first[i], first[i + 1])] if sts[i] == 0 else None
+                           for i in range(n)]
+        finally:
+            for i in range(n):
+                if want_data and dsts[i]:
+                    self.lib.zh_free(dsts[i])
+            if want_members and mem:
+                self.lib.zh_free(mem)
+        self._check(rc)
+        return outs, list(sts)[:n], members
+
+    def debug_gzip_stats(self):
+        """(candidates, input bytes the budgeted sizing pass consumed, frontier rounds) of the last gzip_read_batch."""
+        c, b, r = _c.c_uint64(), _c.c_uint64(), _c.c_uint64()
+        self._check(self.lib.zh_debug_gzip_stats(self._h, _c.byref(c), _c.byref(b), _c.byref(r)))
+        return c.value, b.value, r.value
 
     # ---- seek indexes for foreign deflate streams ----
     def seek_index_batch(self, srcs, dataFormat=dfDetect, span=0, want_data=False):

@@ -122,6 +122,29 @@ def bgzf_read_range(image, index, off, length):
     return eng._raise_first(outs, sts)[0]
 
 
+def gzip_read_batch(images, want_data=True):
+    """Gzip files of any shape -- several members back to back (cat a.gz b.gz, appended logs, pigz -i, .warc.gz), FEXTRA,
+    FNAME, FCOMMENT and FHCRC fields --, in one call; every member verified by its CRC-32 and ISIZE.  -> (outputs,
+    statuses, members): an output is the members' data back to back (None where the status is not 0, and everywhere
+    with want_data=False, which still decodes and verifies); members[i] is the list of image i's members as dicts
+    with zh_gzip_member's fields."""
+    return engine().gzip_read_batch(images, want_data)
+
+
+def gzip_read(image):
+    """gzip_read_batch for one file -> bytes; raises ZippyError."""
+    eng = engine()
+    outs, sts, _ = eng.gzip_read_batch([image])
+    return eng._raise_first(outs, sts)[0]
+
+
+def gzip_members(image):
+    """The members of one gzip file, decoded and verified, without its data -> list of dicts; raises ZippyError."""
+    eng = engine()
+    _, sts, members = eng.gzip_read_batch([image], want_data=False)
+    return eng._raise_first(members, sts)[0]
+
+
 def seek_index_batch(srcs, dataFormat=dfDetect, span=0, want_data=False):
     """Seek indexes for foreign deflate streams (zlib, gzip, raw; from zlib, pigz or this library), in one call: every
     stream is decoded and verified once, and at block boundaries at least `span` uncompressed bytes apart (0: 1 MiB, else

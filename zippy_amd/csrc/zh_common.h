@@ -145,6 +145,12 @@ struct ZhRecArgs {
   const uint64_t* off;
   const uint32_t* cap;
   uint32_t* n;
+  // The speculative sizing pass of zh_gzip.hip (zh_inflate_tokens_kernel<.., kCount, kRec> together: it counts like the
+  // one and closes like the other, and writes neither record nor point): points[i] = the bit behind stream i's final
+  // block, n[i] = 1 where the stream was given up because the call's workgroups together had consumed spec_budget
+  // input bytes (*spec_used: what they paid, a block or a superchunk at a time), else 0.  off, cap, span: unused.
+  unsigned long long* spec_used;
+  uint64_t spec_budget;  // (~0: none)
 };
 // A range read (zh_seek_inflate_kernel): "stream" i's slot already holds hist_len[i] bytes of history in front of its
 // output, and its decode ends at the block boundary stop_bit[i] (counted like ZhInflateArgs::start_bit)

@@ -57,6 +57,7 @@ void zh_launch_inflate_tokens(hipStream_t, const uint8_t* d_src, ZhInflateArgs a
 void zh_launch_inflate_write(hipStream_t, const uint8_t* d_src, uint8_t* d_dst, ZhInflateArgs a,
                              const uint32_t* tok_pool, const uint64_t* tok_off);
 void zh_launch_inflate_count(hipStream_t, const uint8_t* d_src, ZhInflateArgs a);
+void zh_launch_inflate_spec(hipStream_t, const uint8_t* d_src, ZhInflateArgs a, ZhRecArgs rec);
 void zh_launch_segments_reduce(hipStream_t, ZhInflateArgs seg, ZhInflateArgs whole);
 void zh_launch_seg_find(hipStream_t, const uint8_t* d_src, ZhInflateArgs a, ZhSegArgs g);
 void zh_launch_seg_fake_start(hipStream_t, ZhSegArgs g, uint64_t bit);
@@ -164,6 +165,8 @@ struct zh_ctx {
   std::vector<DevBlock> dev_blocks;
   // zh_debug_range_stats: the last ranges call / plan run (bytes over the link, blocks decoded in place / via scratch)
   uint64_t rg_uploaded = 0, rg_in_place = 0, rg_via_scratch = 0;
+  // zh_debug_gzip_stats: the last zh_gzip_read_batch (candidates, input bytes its speculative pass consumed, frontier rounds)
+  uint64_t gz_candidates = 0, gz_spec_bytes = 0, gz_rounds = 0;
   size_t dev_cached = 0, dev_cache_max = 0;
   uint64_t dev_stamp = 0;
   bool dev_poison = false;

@@ -117,6 +117,12 @@ struct RunResult {
 // header is known, applies the point rule of include/zippy_hip.h -- only chosen points are written, all are counted.
 // It reads every stored block's header by itself (no chain of 64 at once: each is a block start).  An instantiation
 // of its own for the same reason.
+// kCount and kRec TOGETHER: the speculative sizing pass over the candidate members of a multi-member gzip image
+// (zh_gzip.hip; ZhRecArgs, zh_common.h): the bytes are summed as kCount does, the bit behind the final block's
+// end-of-block code is left as kRec's closing entry has it, and neither a record nor a point is written.  Most of its
+// streams are no streams at all, so the call's workgroups share a budget of input bytes: a workgroup pays what it
+// consumed where a block's header is read and where a superchunk is staged (one vector atomic by one lane), and gives
+// its stream up -- unresolved, no error -- once the sum has reached the budget.  An instantiation of its own again.
 template <uint32_t kSplitThreads, bool kSeg, bool kCount = false, bool kRec = false>
 __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : kSplitThreads < 256 ? 4 : 1) void zh_inflate_tokens_kernel(const uint8_t* __restrict__ d_src,
                                                                 ZhInflateArgs a,
@@ -145,6 +151,8 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
   // block / superchunk control words written by one thread, read by all
   __shared__ uint32_t s_c_btype, s_c_final, s_c_st, s_c_stored_len, s_c_term, s_c_endrel, s_c_hlit, s_c_hdist;
   __shared__ uint64_t s_c_pos;
+  __shared__ uint32_t s_c_over;  // kCount && kRec: the budget is spent
+  constexpr bool kSpec = kCount && kRec;
 
   const uint32_t tid = threadIdx.x;
   const unsigned lane = zh_lane();
@@ -206,6 +214,13 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
   uint64_t ntok = 0, out_bytes = 0;
   uint64_t rec_last = 0;   // kRec: the last point's out_off ...
   uint32_t rec_count = 0;  // ... and the points so far (the same in every thread)
+  uint64_t spec_paid = pos >> 3;  // kSpec: the input byte (from asrc) up to which the budget has been paid ...
+  bool spec_stop = false;         // ... and whether it ran out (the same in every thread)
+  // one lane pays for the bytes up to `pos` and says whether the call's sum has reached the budget
+  auto spec_pay = [&]() -> uint32_t {
+    const unsigned long long due = (pos >> 3) > spec_paid ? (pos >> 3) - spec_paid : 0ull;
+    return atomicAdd(rec.spec_used, due) + due >= rec.spec_budget ? 1u : 0u;
+  };
   KPROF_DECL(8);  // cycles: 0 header + tables, 1 staging, 2 sync turns, 3 scan, 4 token pass; counts: 5 superchunks, 6 turns, 7 streams
   int st = ZH_OK;
   bool final_block = false;
@@ -405,6 +420,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
         s_c_st = (uint32_t)hst;
         s_c_stored_len = hdr.stored_len;
         s_c_pos = hbase * 32 + bp;  // behind the header (stored: the first raw byte)
+        if (kSpec) s_c_over = spec_pay();
       }
     }
     __syncthreads();
@@ -532,7 +548,7 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
 #endif
       if (seg_target == rel && !g.is_sub[seg_tj]) break;  // that segment's decoder takes over
     }
-    if (kRec && (rec_count == 0u || out_bytes - rec_last >= rec.span)) {
+    if (kRec && !kCount && (rec_count == 0u || out_bytes - rec_last >= rec.span)) {
       if (tid == 0 && rec_count < rec.cap[sid]) {
         uint64_t* pt = rec.points + 2u * (rec.off[sid] + rec_count);
         pt[0] = pos - (uint64_t)mis * 8;
@@ -545,6 +561,13 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
     parse_header();
     if (kSeg) cur_hdr = hdr_at - (uint64_t)mis * 8;
     const uint32_t btype = s_c_btype;
+    if (kSpec) {
+      spec_paid = hdr_at >> 3;
+      if (s_c_over) {
+        spec_stop = true;
+        break;
+      }
+    }
 #ifdef ZH_EMU
     if (tid == 0 && getenv("ZH_DBG_BLOCKS"))
       fprintf(stderr, "block at bit %llu type %u (region %u)\n", (unsigned long long)(hdr_at - mis * 8), btype, sid);
@@ -699,12 +722,20 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
       if (tid == 0) {
         s_first_dirty[0] = s_first_dirty[1] = kSplitThreads;
         s_first_term[0] = s_first_term[1] = kSplitThreads;
+        if (kSpec) s_c_over = spec_pay();
       }
       const uint64_t end_bit = end * 8;
       const uint32_t end_rel = end_bit > base_bit
                                    ? (uint32_t)(end_bit - base_bit < 0xfffffff0ull ? end_bit - base_bit : 0xfffffff0ull)
                                    : 0u;
       __syncthreads();
+      if (kSpec) {
+        spec_paid = pos >> 3;
+        if (s_c_over) {
+          spec_stop = true;
+          break;
+        }
+      }
 #ifdef ZH_KPROF_HDR
       KPROF_MARK(2);
 #else
@@ -869,10 +900,15 @@ __global__ __launch_bounds__(kSplitThreads, kSplitThreads == 256 ? ZH_TOK_OCC : 
       pos = base_bit + s_end[kSeg && cut_t < kSplitThreads ? cut_t : kSplitThreads - 1u];
     }
     if (kSeg && seg_landed) break;
+    if (kSpec && spec_stop) break;
   }
   if (tid == 0) {
     if (!kCount) tok[ntok] = kRecSpecial | kRecEnd | ((uint32_t)st << 16);
-    if (kRec) {  // the closing entry: the bit behind the final block's end-of-block code, the total
+    if (kSpec) {  // what the closing entry holds, and whether the budget ended the stream before its end
+      rec.points[sid] = pos - (uint64_t)mis * 8;
+      rec.n[sid] = spec_stop ? 1u : 0u;
+      if (!spec_stop) (void)spec_pay();
+    } else if (kRec) {  // the closing entry: the bit behind the final block's end-of-block code, the total
       if (rec_count < rec.cap[sid]) {
         uint64_t* pt = rec.points + 2u * (rec.off[sid] + rec_count);
         pt[0] = pos - (uint64_t)mis * 8;
@@ -1406,6 +1442,16 @@ extern "C" void zh_launch_inflate_count(hipStream_t stream, const uint8_t* d_src
   } else {
     hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false, true>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 9, ZhRecArgs{});
     hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false, true>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 8, ZhRecArgs{});
+  }
+}
+// The speculative sizing pass of zh_gzip.hip (kCount and kRec together): the same routing again.
+extern "C" void zh_launch_inflate_spec(hipStream_t stream, const uint8_t* d_src, ZhInflateArgs a, ZhRecArgs rec) {
+  if (!a.nbufs) return;
+  if (zh_tokens_width(a.nbufs) == 1024u) {
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<1024, false, true, true>), dim3(a.nbufs), dim3(1024), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 1, rec);
+  } else {
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<256, false, true, true>), dim3(a.nbufs), dim3(256), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 9, rec);
+    hipLaunchKernelGGL((zh_inflate_tokens_kernel<128, false, true, true>), dim3(a.nbufs), dim3(128), 0, stream, d_src, a, nullptr, nullptr, nullptr, ZhSegArgs{}, 8, rec);
   }
 }
 // phase 0: sub-starts for the segments inside long blocks

@@ -2686,3 +2686,375 @@ def huffman_depth(f):
         a, b = heapq.heappop(h), heapq.heappop(h)
         heapq.heappush(h, (a[0] + b[0], max(a[1], b[1]) + 1))
     return h[0][1]
+
+
+# ---- family C: crafted inputs for the hash-chain matcher (levels 2..9 and -1), each built to expose named mutants of
+# tests/chain_model.py or to reach one structure of zh_chain_match.hip; what each reaches is asserted in
+# tests/test_chain_craft.py from the model's statistics, the oracle's tokens and numpy ----
+CHAIN_HASH_MUL = 0x1e35a7bd
+CHAIN_HASH_INV = pow(CHAIN_HASH_MUL, -1, 1 << 32)
+CHAIN_ALL_LEVELS = (2, 3, 4, 5, -1, 6, 7, 8, 9)
+CHAIN_CONFIG = {2: (4, 16, 8), 3: (4, 32, 32), 4: (4, 16, 16), 5: (8, 32, 32), 6: (8, 128, 128), 7: (8, 256, 256),
+                8: (32, 258, 1024), 9: (32, 258, 4096)}   # level: (good, nice, chain), internal.nim:177-189
+CHAIN_DEVICE_LEVELS = (2, -1, 9)   # one level of wide link records, two of narrow ones
+CHAIN_PERIODS = (1, 2, 3, 7, 129, 257, 258, 259)
+CHAIN_GRID_AT = (0, 1, 32767, 32768, 32769, 65536)
+CHAIN_GRID_DIST = (100, 32766, 32767, 32768, 32769)
+CHAIN_BLOCK_SIZES = (32768, 65536)
+CHAIN_TILE = 16384   # ZH_CHAIN_LINKS_TILE
+chain_case_info = {}   # name -> what tests/test_chain_craft.py asserts of the case
+
+
+def chain_hash(b, at=0):
+    return ((int.from_bytes(b[at:at + 4], "little") * CHAIN_HASH_MUL) & 0xffffffff) >> 15
+
+
+def chain_word(h, low15):
+    """one of the 32 768 four-byte words of hash h"""
+    return ((CHAIN_HASH_INV * ((h << 15) | low15)) & 0xffffffff).to_bytes(4, "little")
+
+
+def chain_tag(b5):
+    """zh_chain_tag of a position's first five bytes (zh_chain_match.hip), restated"""
+    lo = int.from_bytes(b5[:4], "little")
+    return ((lo * 0x9e3779b1 + b5[4] * 0x85ebca6b) & 0xffffffff) >> 16
+
+
+def _c_decoy(h, avoid, rnd):
+    """a word of hash h whose repeats hold no other position of hash h, and that shares no byte with `avoid`'s place"""
+    while True:
+        w = chain_word(h, rnd.randrange(32768))
+        if w[0] != avoid[0] and all(chain_hash((w * 2)[k:k + 4]) != h for k in (1, 2, 3)):
+            return w
+
+
+def _c_levels(level):
+    return (-1, 6) if level == 6 else (level,)
+
+
+def _c_kills(level, *mutants):
+    return {(lv, m) for lv in _c_levels(level) for m in mutants}
+
+
+def _c_depth_cases(rnd):
+    """depth: `n` words of the searcher's hash between a 20-byte target and its repeat; the target is candidate n + 1"""
+    out = []
+    for level, (good, nice, chain) in CHAIN_CONFIG.items():
+        for n in (chain - 1, chain):
+            h = rnd.randrange(1 << 17)
+            x = chain_word(h, rnd.randrange(32768)) + rnd.randbytes(16)
+            w = _c_decoy(h, x, rnd)
+            pre = rnd.randbytes(37)
+            src = pre + x + w * n + x + rnd.randbytes(9)
+            found = n + 1 <= chain
+            want = ["chain-1" if found else "chain+1"]
+            for m, d in (("config-1", -1), ("config+1", 1)):
+                other = CHAIN_CONFIG.get(level + d, (4, 8, 4) if level + d == 1 else None)
+                if other is not None and (n + 1 <= other[2]) != found:
+                    want.append(m)
+            name = "C/depth/level%d_%d_decoys" % (level, n)
+            chain_case_info[name] = dict(searcher=len(pre) + 20 + 4 * n, tried=chain, why=None if found else "tries",
+                                         match=(len(pre) + 20 + 4 * n, 20 + 4 * n, 20) if found else None)
+            out.append((name, src, _c_levels(level), _c_kills(level, *want)))
+    return out
+
+
+def _c_good_cases(rnd):
+    """good: the nearest candidate matches good - 1 or good bytes; a 40-byte one is candidate 2 + ((chain - 1) >> 2),
+    one more than a cut walk reaches and within what `tries >>= 1` would leave.  (good - 1 = 3 bytes at levels 2..4 is
+    no candidate at all: words that share three bytes differ in the top byte, which the odd multiplier carries into the
+    hash's top bits.)  cut: two candidates of `good` bytes, then 3 + (((chain - 1) >> 2) - 1 >> 2) deep the long one:
+    the reference cuts once, `cut_always` twice.  At level 2 `cut_always` cannot show: after the first cut one try is
+    left, ((8 - 1) >> 2) = 1, and the candidate that takes it is the last either way."""
+    out = []
+    for level, (good, nice, chain) in CHAIN_CONFIG.items():
+        t1 = (chain - 1) >> 2
+        for kind in ("good", "good-1", "cut"):
+            if (kind == "good-1" and good - 1 < 4) or (kind == "cut" and level == 2):
+                continue
+            h = rnd.randrange(1 << 17)
+            x = chain_word(h, rnd.randrange(32768)) + rnd.randbytes(36)
+            w = _c_decoy(h, x, rnd)
+            pre = rnd.randbytes(41)
+            g = good - 1 if kind == "good-1" else good
+            f1, f2 = x[:g] + bytes([x[g] ^ 0x55]), x[:g] + bytes([x[g] ^ 0xaa])
+            if kind == "cut":
+                body = w * ((t1 - 1) >> 2) + f2 + f1
+                kills = _c_kills(level, "cut_always")
+            else:
+                body = w * t1 + f1
+                kills = _c_kills(level, "good_gt", "shr1", *(("tag4",) if good == 4 else ())) if kind == "good" else set()
+            src = pre + x + body + x + rnd.randbytes(9)
+            at = len(pre) + 40 + len(body)
+            name = "C/good/level%d_%s" % (level, kind)
+            if kind == "good":
+                chain_case_info[name] = dict(searcher=at, tried=1 + t1, why="tries", longest=g, cuts=1)
+            else:
+                chain_case_info[name] = dict(searcher=at, tried=t1 + 2 if kind == "good-1" else 3 + ((t1 - 1) >> 2),
+                                             longest=40, cuts=1 if kind == "good-1" else 2, match=(at, len(body) + 40, 40))
+            out.append((name, src, _c_levels(level), kills))
+    return out
+
+
+def _c_nice_cases(rnd):
+    """nice: the nearest candidate matches nice - 1 or nice bytes, a longer one lies behind it.  Levels 8 and 9: nice
+    is 258, the limit itself -- no candidate is longer than a 258-byte one, so `nice_gt` cannot show there; the
+    257-byte case still tells level 8 from level 7 (`config-1`: nice 256 stops at 257 bytes)."""
+    out = []
+    for level, (good, nice, chain) in CHAIN_CONFIG.items():
+        for m in (nice - 1, nice):
+            if m == 258:
+                continue
+            h = rnd.randrange(1 << 17)
+            x = chain_word(h, rnd.randrange(32768)) + rnd.randbytes(296)
+            pre = rnd.randbytes(43)
+            long_len = min(m + 20, 258)
+            src = pre + x[:m + 20] + rnd.randbytes(5) + x[:m] + bytes([x[m] ^ 0x55]) + x[:m + 20] + rnd.randbytes(9)
+            at = len(pre) + m + 20 + 5 + m + 1
+            stops = m >= nice
+            kills = _c_kills(level, "nice_gt") if stops else (_c_kills(level, "config-1") if level == 8 else set())
+            name = "C/nice/level%d_%d_bytes" % (level, m)
+            chain_case_info[name] = dict(searcher=at, tried=1 if stops else 2, why="nice" if stops else None,
+                                         match=(at, m + 1, m) if stops else (at, at - len(pre), long_len))
+            out.append((name, src, _c_levels(level), kills))
+    return out
+
+
+def _c_every_level_cases(rnd):
+    """the decisions that no level's tuple touches: tie, min, sentinel, wrap, skip-insert, the block's last positions,
+    the limit -- each input at every chain level"""
+    out = []
+    every = lambda *mutants: {(lv, m) for lv in CHAIN_ALL_LEVELS for m in mutants}
+
+    def add(name, src, kills, **info):
+        chain_case_info["C/" + name] = info
+        out.append(("C/" + name, src, CHAIN_ALL_LEVELS, kills))
+    # tie: two candidates of six bytes; the nearer one wins
+    x = rnd.randbytes(6)
+    src = rnd.randbytes(29) + x + b"\x01" + rnd.randbytes(10) + x + b"\x02" + rnd.randbytes(10) + x + b"\x03" + rnd.randbytes(9)
+    add("tie/two_of_six_bytes", src, every("ge_longest"), match=(29 + 34, 17, 6))
+    # min: longest matches of exactly 4, 5 and 6 bytes
+    src, want = rnd.randbytes(31), []
+    for n in (4, 5, 6):
+        x = rnd.randbytes(n)
+        src += x + b"\x01" + rnd.randbytes(12)
+        if n > 4:
+            want.append((len(src), n + 13, n))
+        else:
+            four_at = len(src)
+        src += x + b"\x02" + rnd.randbytes(12)
+    add("min/4_5_6_bytes", src, every("min4", "min6"), matches=want, searcher=four_at, longest=4)
+    # skip-insert: a string that begins inside a hop (at its positions 1 and length - 1) is found there later
+    a, e1, b, e2 = rnd.randbytes(30), rnd.randbytes(12), rnd.randbytes(30), rnd.randbytes(20)
+    src = rnd.randbytes(33) + a + rnd.randbytes(9) + a + e1 + rnd.randbytes(9)
+    want = [(len(src), 9 + 41, 41)]
+    src += a[1:] + e1 + rnd.randbytes(9) + b + rnd.randbytes(9) + b + e2 + rnd.randbytes(9)
+    want.append((len(src), 9 + 21, 21))
+    src += b[29:] + e2 + rnd.randbytes(9)
+    add("skip_insert/hop_positions_1_and_last", src, every("no_skip_insert"), matches_in=want, count=4)
+    # the last positions: block_end - 5 is searched and finds its five bytes; block_end - 4 is not
+    x = rnd.randbytes(5)
+    src = rnd.randbytes(35) + x + rnd.randbytes(20) + x
+    add("tail/five_bytes_at_end", src, every("min6"), match=(len(src) - 5, 25, 5))
+    src = rnd.randbytes(35) + x + rnd.randbytes(20) + x[:4]
+    add("tail/four_bytes_at_end", src, set(), matches=[])
+    # limit: a repeat of 257, 258, 259 and 600 bytes
+    for n in (257, 258, 259, 600):
+        r = rnd.randbytes(n)
+        src = rnd.randbytes(39) + r + rnd.randbytes(7) + r + rnd.randbytes(7)
+        want = [(39 + n + 7 + k, n + 7, min(258, n - k)) for k in range(0, n, 258) if n - k > 4]
+        add("limit/repeat_%d" % n, src, every("limit_259") if n > 258 else set(), matches=want)
+    # ... and one that runs into the block's end (the search's 8-byte compare and its byte-by-byte tail)
+    for k in (5, 8, 9, 257, 258):
+        r = rnd.randbytes(300)
+        src = rnd.randbytes(39) + r + rnd.randbytes(11) + r[:k]
+        add("limit/%d_bytes_to_block_end" % k, src, set(), matches=[(350, 311, k)])
+    # sentinel: a key in window slot 0 is never found; wrap: nor is one exactly a window back
+    key = rnd.randbytes(20)
+    add("sentinel/key_at_0_again_at_100", key + rnd.randbytes(80) + key + rnd.randbytes(10), every("no_sentinel"),
+        matches=[(101, 100, 19)])   # (from the key's second byte on)
+    key = rnd.randbytes(20)
+    add("wrap/key_at_1_again_at_32769", b"\x00" + key + rnd.randbytes(32768 - 20) + key + rnd.randbytes(10), every("wrap_eq"),
+        matches=[], searcher=32769, why="offset0")
+    return out
+
+
+def _c_grid_cases(rnd):
+    """sentinel and wrap: a 20-byte key at block positions 0, 1, 32 767, 32 768, 32 769 and 65 536, again 100, 32 766,
+    32 767, 32 768 and 32 769 bytes on, in noise.  Found: keys outside window slot 0 up to distance 32 767."""
+    out = []
+    for d in CHAIN_GRID_DIST:
+        rest, part = list(CHAIN_GRID_AT), 0
+        while rest:
+            taken, spans = [], []
+            for p in list(rest):
+                mine = [(p, p + 20), (p + d, p + d + 20)]
+                if all(hi <= lo2 or hi2 <= lo for lo, hi in mine for lo2, hi2 in spans):
+                    taken.append(p)
+                    spans += mine
+                    rest.remove(p)
+            src = bytearray(rnd.randbytes(max(taken) + d + 20 + 50))
+            for p in taken:
+                key = rnd.randbytes(20)
+                src[p:p + 20] = key
+                src[p + d:p + d + 20] = key
+            name = "C/grid/distance_%d_part_%d" % (d, part)
+            chain_case_info[name] = dict(grid=[(p, d, p % 32768 != 0 and d <= 32767) for p in taken])
+            out.append((name, bytes(src), CHAIN_DEVICE_LEVELS, set()))
+            part += 1
+    return out
+
+
+def _c_boundary(src, at, rnd):
+    """around the block border `at`: a 40-byte string whose repeat starts 10 bytes in front of the border (clipped
+    there), and a 30-byte string in the block's last bytes that comes again 50 bytes into the next block (not found)"""
+    r, q = rnd.randbytes(40), rnd.randbytes(30)
+    src[at - 2000:at - 1960] = r
+    src[at - 10:at + 30] = r
+    src[at - 40:at - 10] = q
+    src[at + 50:at + 80] = q
+
+
+def _c_block_cases(rnd):
+    out = []
+    src = bytearray(rnd.randbytes(65536 + 5000))
+    _c_boundary(src, 32768, rnd)
+    _c_boundary(src, 65536, rnd)
+    kills = {(lv, m) for lv in CHAIN_ALL_LEVELS for m in ("head_survives_block", "limit_ignores_block_end")}
+    chain_case_info["C/block/borders_32768_65536"] = dict(borders=(32768, 65536))
+    out.append(("C/block/borders_32768_65536", bytes(src), CHAIN_ALL_LEVELS, kills))
+    # two deflate blocks: most of the first is a run of one byte, which the parse crosses in 16 K hops
+    src = bytearray(rnd.randbytes(3000) + b"\x6b" * (FULL_BLOCK - 6000) + rnd.randbytes(3000 + 70000))
+    _c_boundary(src, FULL_BLOCK, rnd)
+    chain_case_info["C/block/two_deflate_blocks"] = dict(borders=(FULL_BLOCK,), small=False)
+    out.append(("C/block/two_deflate_blocks", bytes(src), (2, 9), set()))
+    return out
+
+
+def _c_tiny_cases():
+    out = []
+    for n in range(5, 14):
+        out.append(("C/tiny/one_byte_%d" % n, b"\xc4" * n, CHAIN_ALL_LEVELS, set()))
+        out.append(("C/tiny/distinct_%d" % n, bytes(range(65, 65 + n)), CHAIN_ALL_LEVELS, set()))
+        # (position 1's candidate is window slot 0, the sentinel; position 2 finds position 1 from 7 bytes on)
+        chain_case_info["C/tiny/one_byte_%d" % n] = dict(matches=[(2, 1, n - 2)] if n >= 7 else [])
+        chain_case_info["C/tiny/distinct_%d" % n] = dict(matches=[])
+    return out
+
+
+def _c_tag_case(rnd):
+    """tags: five-byte strings of the searcher's hash AND the searcher's zh_chain_tag whose bytes differ, as candidates
+    in front of a true 20-byte match: the narrow records say "may match", the bytes say no"""
+    h = rnd.randrange(1 << 17)
+    words = (np.uint32(CHAIN_HASH_INV) * ((np.uint32(h) << np.uint32(15)) | np.arange(32768, dtype=np.uint32)))
+    tags = (words * np.uint32(0x9e3779b1))[:, None] + np.arange(256, dtype=np.uint32)[None, :] * np.uint32(0x85ebca6b) >> np.uint32(16)
+    mine = int(tags[0, 0x41])
+    hits = [(int(i), int(b)) for i, b in np.argwhere(tags == mine) if i != 0][:5]
+    assert len(hits) == 5
+    s5 = int(words[0]).to_bytes(4, "little") + b"\x41"
+    cands = [int(words[i]).to_bytes(4, "little") + bytes([b]) for i, b in hits]
+    x = s5 + rnd.randbytes(15)
+    pre = rnd.randbytes(45)
+    body = b"".join(c + rnd.randbytes(2) for c in cands)
+    src = pre + x + rnd.randbytes(3) + body + x + rnd.randbytes(9)
+    at = len(pre) + 23 + len(body)
+    chain_case_info["C/tags/equal_tag_other_bytes"] = dict(searcher=at, tried=6, match=(at, 23 + len(body), 20), searcher5=s5,
+                                                          candidates=cands)
+    return [("C/tags/equal_tag_other_bytes", src, (2, 5, -1, 9), set())]
+
+
+def chain_classes(src):
+    """the class (low five bits of the hash) of every inserted position of a one-block input"""
+    a = np.frombuffer(src, np.uint8).astype(np.uint32)
+    n = len(src) - 4
+    w = a[:n] | a[1:n + 1] << 8 | a[2:n + 2] << 16 | a[3:n + 3] << 24
+    return ((w * np.uint32(CHAIN_HASH_MUL)) >> np.uint32(15)) & np.uint32(31)
+
+
+def _c_class_case(rnd):
+    """classes and tiles: 3 tiles + 100 positions; the first tile is a run (one class holds all of it), the second
+    and third noise over two letters (<= 16 classes), and in the third a stretch of a third letter brings a class
+    that no earlier position has; <= 23 classes in all, so some stay empty"""
+    total = 3 * CHAIN_TILE + 100
+    for _ in range(1000):
+        a, b, c = rnd.sample(range(256), 3)
+        two = lambda n: bytes(rnd.choice((a, b)) for _ in range(n))
+        third = two(8000) + bytes([a] * 4 + [c] * 8 + [a] * 4)
+        src = bytes([a]) * CHAIN_TILE + bytes([a] * 3) + two(CHAIN_TILE - 3) + third
+        src += two(total + 4 - len(src))
+        cls = chain_classes(src)
+        early = set(cls[:2 * CHAIN_TILE].tolist())
+        if len(set(cls[:CHAIN_TILE].tolist())) == 1 and set(cls[2 * CHAIN_TILE:].tolist()) - early:
+            return [("C/classes/three_tiles", src, CHAIN_DEVICE_LEVELS, set())]
+    raise AssertionError("no letters found")
+
+
+def _c_device_cases(rnd):
+    out = []
+
+    def add(name, src, keep=True, **info):
+        chain_case_info["C/" + name] = dict(info, small=keep)
+        out.append(("C/" + name, src, CHAIN_DEVICE_LEVELS, set()))
+    # never-meeting walks: back-to-back 258-byte matches over three fragments and a bit
+    for p in CHAIN_PERIODS:
+        unit = bytes(rnd.sample(range(256), min(p, 256))) + rnd.randbytes(max(0, p - 256))
+        add("runs/period_%d" % p, (unit * (3 * FRAG // p + 1000))[:3 * FRAG + 1000], p in (1, 258), period=p)
+    # spill: matches that end at a fragment's border and 1, 2, 257 bytes behind it, or start 1 and 5 bytes in front
+    for start, n in ((FRAG - 100, 100), (FRAG - 99, 100), (FRAG - 98, 100), (FRAG - 1, 258), (FRAG - 5, 100)):
+        src = bytearray(rnd.randbytes(FRAG + 1500))
+        src[start:start + n] = src[1000:1000 + n]
+        add("spill/match_%d_of_%d" % (start, n), bytes(src), (start, n) in ((FRAG - 100, 100), (FRAG - 1, 258)),
+            matches_at=(start, start - 1000, n))
+    # crowded fragment: 5459 five-byte words, each behind a separator that ends the match
+    words = set()
+    while len(words) < 5459:
+        words.add(rnd.randbytes(5))
+    words = sorted(words)
+    rnd.shuffle(words)
+    first = b"".join(w + bytes([1 + i % 100]) for i, w in enumerate(words))
+    second = b"".join(w + bytes([101 + i % 100]) for i, w in enumerate(words))
+    add("crowded/fragment_of_5459_matches", rnd.randbytes(8) + first + rnd.randbytes(FRAG - 8 - len(first)) + second + b"\xee\xee")
+    return out
+
+
+_chain_craft_cache = {}
+
+
+def chain_crafted_inputs(small=False):
+    """Family C -> [(name, bytes, levels, kills)]; kills: the (level, mutant) pairs of tests/chain_model.py that the
+    input is built to tell from the reference.  small: the emulator's subset -- every cell, at levels 2, -1 and 9 only,
+    without the two-block input."""
+    if False not in _chain_craft_cache:
+        rnd = random.Random(2718)
+        cases = (_c_depth_cases(rnd) + _c_good_cases(rnd) + _c_nice_cases(rnd) + _c_every_level_cases(rnd) + _c_grid_cases(rnd) +
+                 _c_block_cases(rnd) + _c_tiny_cases() + _c_tag_case(rnd) + _c_class_case(rnd) + _c_device_cases(rnd))
+        assert len({c[0] for c in cases}) == len(cases)
+        _chain_craft_cache[False] = cases
+        keep = []
+        for name, src, levels, kills in cases:
+            levels = tuple(lv for lv in levels if lv in CHAIN_DEVICE_LEVELS)
+            if levels and chain_case_info.get(name, {}).get("small", True) and \
+                    (name.split("/")[1] != "grid" or name.endswith("part_0")) and \
+                    (name.split("/")[1] != "tiny" or name.endswith(("_5", "_7", "_8", "_13"))):
+                keep.append((name, src, levels, {k for k in kills if k[0] in levels}))
+        _chain_craft_cache[True] = keep
+    return list(_chain_craft_cache[small])
+
+
+def chain_block_cases(small=False):
+    """the cases of family C that go through the block-parallel form (check_blocks) as well"""
+    return [c for c in chain_crafted_inputs(small) if c[0] == "C/block/borders_32768_65536"]
+
+
+def check_chain_crafted(eng, small=False, levels=None):
+    """family C on a device: the oracle's bytes (gzip, one batch a level), then the oracle's tokens case by case"""
+    cases = chain_crafted_inputs(small)
+    if levels is not None:
+        cases = [(n, s, tuple(lv for lv in own if lv in levels), k) for n, s, own, k in cases]
+    check_crafted_compress(eng, [(n, s, own, GZIP_ONLY) for n, s, own, _ in cases])
+    for name, src, own, _ in cases:
+        for level in own:
+            try:
+                check_tokens(eng, src, level)
+            except AssertionError as e:
+                raise AssertionError("%s: %s" % (name, e))

@@ -401,6 +401,17 @@ def test_emu_crafted_chain_levels(eng):
     pc.check_crafted_compress(eng, cases, levels=(-1, 9))
 
 
+def test_emu_chain_crafted(eng):
+    """the small subset of family C (parity_cases.chain_crafted_inputs: the hash-chain matcher at its decision edges,
+    every cell with wide link records and with narrow ones): the oracle's bytes, then the oracle's tokens"""
+    pc.check_chain_crafted(eng, small=True)
+
+
+def test_emu_chain_crafted_blocks(eng):
+    for name, src, levels, _ in pc.chain_block_cases(small=True):
+        pc.check_blocks(eng, src, levels, pc.CHAIN_BLOCK_SIZES)
+
+
 def test_emu_crafted_matcher_tokens(eng):
     for name, src, _, _ in _family(True, "M"):
         pc.check_tokens(eng, src, 1)

@@ -571,6 +571,41 @@ def test_gpu_crafted_chain_levels(eng):
     pc.check_crafted_compress(eng, cases, levels=pc.CHAIN_LEVELS)
 
 
+def test_gpu_chain_crafted(eng):
+    """Family C (parity_cases.chain_crafted_inputs): the hash-chain matcher at its decision edges -- depth, good,
+    nice, ties, the shortest match, the sentinel slot and the window's far end, hops, the limit, block ends -- and
+    at what its kernels are built from: walks that never meet, spills over fragment borders, a crowded fragment, hash
+    classes and tiles, equal tags over other bytes.  The oracle's bytes (one batch a level), then the oracle's
+    tokens case by case, where a mismatch names the case."""
+    pc.check_chain_crafted(eng)
+
+
+def test_gpu_chain_crafted_blocks(eng):
+    for name, src, levels, _ in pc.chain_block_cases():
+        pc.check_blocks(eng, src, levels, pc.CHAIN_BLOCK_SIZES)
+
+
+def test_gpu_chain_crafted_in_order_links():
+    """What a device runs that fails zh_create's LDS-order probe (ZH_LDS_ORDER_PROBE=fail pretends one, in a child
+    process of the product library): the in-order link kernels and wide records at every level, on family C at
+    levels 2, -1 and 9."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import torch; torch.cuda.init()\n"
+            "import parity_cases as pc\n"
+            "from zippy_amd import api\n"
+            "eng = api.engine(); eng.set_gzip_fname_len(0)\n"
+            "assert not eng.chain_links_parallel()\n"
+            "assert b'in-order' in eng.lib.zh_last_error(eng._h)\n"
+            "pc.check_chain_crafted(eng, levels=pc.CHAIN_DEVICE_LEVELS)\n" % (os.path.join(root, "tests"), root))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, ZH_LDS_ORDER_PROBE="fail"), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+
+
 def test_gpu_crafted_matcher_tokens(eng):
     for name, src, _, _ in _family("M"):
         pc.check_tokens(eng, src, 1)

@@ -134,7 +134,9 @@ void zh_set_inflate_mode(zh_ctx *ctx, int mode);
  * enters the hash table and the greedy selection runs chunk-parallel, so the token stream differs
  * from zippy's while meeting the encoder contract -- a valid RFC 1951/1950/1952 stream that zippy's
  * uncompress() decodes to the input bit for bit, compressed size within 2 % of zippy's at level 1
- * (tests/test_gpu_parity.py: test_gpu_parallel_parse_*).  < 0 = the default (0, or the
+ * (tests/test_gpu_parity.py: test_gpu_parallel_parse_*); its tokens are those of the serial rule
+ * of tests/l1p_model.py, token for token (test_gpu_l1p_tokens, test_gpu_l1p_streams,
+ * test_gpu_l1p_alignment: crafted family P of tests/parity_cases.py).  < 0 = the default (0, or the
  * ZH_L1_PARSE=parallel environment variable).  All other levels are unaffected. */
 void zh_set_l1_parse(zh_ctx *ctx, int mode);
 
@@ -923,7 +925,9 @@ int zh_zip_create_batch(zh_ctx *ctx, const zh_zip_new_entry *entries, const size
 /* Level-1 parse of one buffer as the u16 token stream of SURVEY.md 8a row a4
  * (snappy.nim:33-64 format), block by block, fragment by fragment: lets tests
  * compare the device matcher with the oracle token-for-token.  tokens is
- * library-allocated (zh_free). */
+ * library-allocated (zh_free).  At level 1 it follows zh_set_l1_parse / ZH_L1_PARSE as compress does: in contract
+ * mode the tokens are the parallel parse's (zh_l1p_match.hip), which the tests hold against the rule of
+ * tests/l1p_model.py token for token (check_l1p_tokens); with the switch off nothing changes. */
 int zh_debug_tokens(zh_ctx *ctx, const void *src, size_t len, int level, uint16_t **tokens,
                     size_t *num_tokens);
 /* Debug hook: ONE prefix code from a histogram of num_freq <= 288 symbols (deflate.nim:13-151 huffmanCodes:

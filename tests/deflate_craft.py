@@ -4,7 +4,8 @@ code-length code and the exact sequence of 0-15 / 16 / 17 / 18 symbols, any leng
 are no code at all.  The expected plaintext is kept by construction (a literal appends a byte, a match copies byte by
 byte, a stored block appends its data): it comes from no decoder.  A stream that is meant to fail records None and the
 status its single fault must give.  The bit positions of every token and block header are recorded, so a test can
-assert which bit phases it covered."""
+assert which bit phases it covered.  read_blocks is the way back for sound streams: block types, the headers' code
+lengths and the tokens, as an encoder wrote them."""
 
 LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 LEN_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
@@ -257,3 +258,98 @@ class Stream:
         if self.status is not None:
             return bytes(self.buf), None, self.status
         return bytes(self.buf), bytes(self.out), None
+
+
+# ---- a reader, for the streams an encoder wrote ----
+def _decode_table(lens):
+    """{(length, code read first bit first): symbol} of a canonical code"""
+    return {(n, c): s for s, (n, c) in enumerate(zip(lens, canonical_codes(lens))) if n}
+
+
+def read_blocks(raw):
+    """A plain RFC 1951 reader of a sound stream -> one dict a block: 'type' (0 stored, 1 fixed, 2 dynamic), 'final',
+    'lit_lens' / 'dist_lens' (the header's code lengths, HLIT / HDIST entries; the fixed code's for type 1; None for
+    type 0) and 'tokens': ('lit', byte) / ('match', length, distance) in order, a stored block's bytes as literals.
+    The end-of-block symbol is no token.  Bits behind the final block up to the byte boundary are not looked at."""
+    pos = 0
+
+    def bits(n):
+        nonlocal pos
+        v = 0
+        for i in range(n):
+            v |= (raw[pos >> 3] >> (pos & 7) & 1) << i
+            pos += 1
+        return v
+
+    def symbol(table):
+        code = n = 0
+        while True:
+            code = code << 1 | bits(1)
+            n += 1
+            assert n <= 15, "no such code"
+            if (n, code) in table:
+                return table[(n, code)]
+
+    out = []
+    while True:
+        final, btype = bits(1), bits(2)
+        assert btype != 3
+        blk = {"type": btype, "final": bool(final), "lit_lens": None, "dist_lens": None, "tokens": []}
+        out.append(blk)
+        if btype == 0:
+            pos = (pos + 7) & ~7
+            n, nn = bits(16), bits(16)
+            assert n ^ nn == 0xffff
+            blk["tokens"] = [("lit", b) for b in raw[pos >> 3:(pos >> 3) + n]]
+            assert len(blk["tokens"]) == n
+            pos += 8 * n
+        else:
+            if btype == 1:
+                lit_lens, dist_lens = list(FIXED_LIT_LENS), list(FIXED_DIST_LENS)
+            else:
+                hlit, hdist, hclen = bits(5) + 257, bits(5) + 1, bits(4) + 4
+                cl_lens = [0] * 19
+                for k in range(hclen):
+                    cl_lens[CL_ORDER[k]] = bits(3)
+                cl, lens = _decode_table(cl_lens), []
+                while len(lens) < hlit + hdist:
+                    s = symbol(cl)
+                    if s <= 15:
+                        lens.append(s)
+                    elif s == 16:
+                        lens += [lens[-1]] * (3 + bits(2))
+                    else:
+                        lens += [0] * (3 + bits(3) if s == 17 else 11 + bits(7))
+                assert len(lens) == hlit + hdist
+                lit_lens, dist_lens = lens[:hlit], lens[hlit:]
+            blk["lit_lens"], blk["dist_lens"] = lit_lens, dist_lens
+            lit, dist = _decode_table(lit_lens), _decode_table(dist_lens)
+            while True:
+                s = symbol(lit)
+                if s < 256:
+                    blk["tokens"].append(("lit", s))
+                elif s == 256:
+                    break
+                else:
+                    assert s <= 285
+                    length = LEN_BASE[s - 257] + bits(LEN_EXTRA[s - 257])
+                    d = symbol(dist)
+                    assert d <= 29
+                    blk["tokens"].append(("match", length, DIST_BASE[d] + bits(DIST_EXTRA[d])))
+        if final:
+            assert (pos + 7) >> 3 == len(raw), "bytes behind the final block"
+            return out
+
+
+def replay(blocks):
+    """the plaintext of read_blocks' tokens"""
+    out = bytearray()
+    for blk in blocks:
+        for t in blk["tokens"]:
+            if t[0] == "lit":
+                out.append(t[1])
+            else:
+                assert 1 <= t[2] <= len(out)
+                for _ in range(t[1]):
+                    out.append(out[-t[2]])
+    return bytes(out)

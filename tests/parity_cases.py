@@ -3058,3 +3058,304 @@ def check_chain_crafted(eng, small=False, levels=None):
                 check_tokens(eng, src, level)
             except AssertionError as e:
                 raise AssertionError("%s: %s" % (name, e))
+
+
+# ---- family P: crafted inputs for the parallel BestSpeed parse (contract mode, zh_l1p_match.hip), each built to expose
+# named mutants of tests/l1p_model.py or to reach one thing the kernel's speculation has to get right; what each reaches
+# is asserted in tests/test_l1p_craft.py from the model alone ----
+L1P_CHUNK = 32      # positions a parse thread of the kernel
+L1P_WAVE = 2048     # positions a wave of parse threads
+L1P_TAIL_LENGTHS = (15, 16, 17, 19, 20, 63, 64, 65, 32767, 32768, 32768 + 15, 32768 + 16, 32768 + 19)
+L1P_BACK_TO_BACK = (31, 32, 33)
+L1P_PERIODS = (1, 31, 33, 258, 259)
+L1P_DENSE_WORDS = 97   # a prime: every ordered pair of different words once (97 * 96 * 4 bytes > a fragment)
+L1P_ALIGN_TEXT = "P/text/40001"
+l1p_case_info = {}   # name -> what tests/test_l1p_craft.py asserts of the case
+
+
+def l1p_hash(b, at=0):
+    return (int.from_bytes(b[at:at + 4], "little") * CHAIN_HASH_MUL) & 0xffffffff
+
+
+def every_pair_once(k):
+    """0 .. k-1 (k prime) in an order where every ordered pair of different neighbours comes exactly once: for each
+    step d the cycle 0, d, 2d, ... back to 0"""
+    seq = [0]
+    for d in range(1, k):
+        seq += [j * d % k for j in range(1, k + 1)]
+    return seq
+
+
+def _p_units(rnd, k, size):
+    """k strings of `size` bytes with pairwise different first bytes and pairwise different slots of their first words"""
+    units, slots = [], set()
+    while len(units) < k:
+        u = bytes([32 + len(units)]) + rnd.randbytes(size - 1)
+        if l1p_hash(u) >> 18 not in slots:
+            slots.add(l1p_hash(u) >> 18)
+            units.append(u)
+    return units
+
+
+def _p_two_frags(rnd):
+    """the word at 300 in fragment 0 and at 100 and 400 in fragment 1; fragment 0 is a byte ramp behind 400 (few
+    words, few slots), and the word is drawn until no later position of fragment 0 takes its slot"""
+    import l1p_model as lm
+    ramp = bytes(range(256)) * (FRAG // 256)
+    f0 = rnd.randbytes(300)
+    f1 = rnd.randbytes(600)
+    for _ in range(64):
+        key = rnd.randbytes(16)
+        src = f0 + key + ramp[316:] + f1[:100] + key + f1[116:400] + key + f1[416:]
+        if lm.model(src, "table_survives") != lm.model(src):
+            return src
+    raise AssertionError("no word found")
+
+
+def l1p_crafted_inputs():
+    """Family P -> [(name, bytes, kills)]; kills: the mutants of tests/l1p_model.py that the input is built to tell from
+    the rule.  At most three fragments each."""
+    if "P" in _compress_craft_cache:
+        return list(_compress_craft_cache["P"])
+    rnd = random.Random(1618)
+    alice = synth.corpus_file("alice29.txt")
+    html = synth.corpus_file("html")
+    out = []
+    info = l1p_case_info
+
+    def add(name, src, kills=(), **claims):
+        out.append(("P/" + name, bytes(src), frozenset(kills)))
+        info["P/" + name] = claims
+
+    # -- the last 15 bytes: a repeat that starts exactly 16, and one exactly 15, bytes before the end
+    key = rnd.randbytes(16)
+    body = rnd.randbytes(484)
+    add("tail/repeat_at_n-16", body[:100] + key + body[100:] + key, {"tail17"}, has=[(500, 400, 16)])
+    add("tail/repeat_at_n-15", body[:100] + key[:15] + body[100:] + key[:15], {"tail15"}, none_from=499)
+    # -- the cap: a 300-byte repeat
+    key = rnd.randbytes(300)
+    add("cap/repeat_300", body[:50] + key + body[50:100] + key + body[100:200], {"lim257", "lim259"},
+        has=[(400, 350, 258)])
+    add("cap/run_300", body[:50] + b"\x5a" * 300 + body[50:150], {"lim257", "lim259"}, has=[(51, 1, 258), (309, 1, 41)])
+    # -- a repeat cut by the fragment's end whose continuation matches in the next fragment
+    key = rnd.randbytes(200)
+    noise = rnd.randbytes(FRAG + 500)
+    add("frag/repeat_cut_at_32768", noise[:FRAG - 400] + key + noise[FRAG - 200:FRAG - 100] + key + noise[FRAG + 100:],
+        {"lim_past_frag"}, has=[(FRAG - 100, 300, 100)])
+    # -- position 0 is no candidate
+    key = rnd.randbytes(16)
+    add("pos0/only_occurrence_at_0", key + body[:100] + key + body[100:150], {"pos0"}, has=[(117, 116, 15)], none_at=[116])
+    # -- the minimum: a four-byte repeat
+    add("min/four_byte_repeat", body[:40] + b"WXYZ" + body[40:90] + b"WXYZ" + body[90:140], {"min5"}, has=[(94, 54, 4)])
+    # -- a candidate inside a taken match: every position enters the table
+    key = rnd.randbytes(30)
+    add("table/candidate_inside_a_match", body[:10] + key + body[10:20] + key + body[20:60] + key[5:25] + body[60:100],
+        {"visited_only"}, has=[(50, 40, 30), (120, 65, 20)])
+    # -- a word, its repeat and a third copy inside one 64-position step: the earlier one is the candidate, never the later
+    key = rnd.randbytes(8)
+    add("same-step/three_in_64_127", body[:70] + key + body[70:82] + key + body[82:94] + key + body[94:250],
+        {"step_granular"}, has=[(90, 20, 8), (110, 20, 8)])
+    add("two-frags/table_of_fragment_0", _p_two_frags(rnd), {"table_survives"}, has=[(FRAG + 400, 300, 16)])
+    # -- fragment lengths: text, the last 8 + k bytes one letter (so that a last fragment of k bytes has something to find)
+    for n in L1P_TAIL_LENGTHS:
+        k = n % FRAG or FRAG
+        src = (alice[3000:3000 + n - k] + b"q" * k) if k <= 65 else alice[3000:3000 + n - 40] + b"q" * 40
+        add("len/%d" % n, src, has=[(n - k + 2, 1, k - 2)] if 19 <= k <= 65 else [], none_from=n - k if k < 18 else n - 15)
+    # -- zeros up to and across a fragment's end (the kernel's compare runs into zeroed slack behind the fragment)
+    add("zeros/up_to_fragment_end", noise[:FRAG - 1000] + bytes(1000) + noise[FRAG:], ends_at=[FRAG])
+    add("zeros/across_fragment_end", noise[:FRAG - 500] + bytes(1000) + noise[FRAG:FRAG + 300], {"lim_past_frag"},
+        ends_at=[FRAG], has=[(FRAG + 2, 1, 258)])
+    add("zeros/two_fragments_and_19", bytes(2 * FRAG + 19), ends_at=[FRAG, 2 * FRAG, 2 * FRAG + 19])
+    # -- periods: matches of 258 back to back, whose phase against the kernel's chunks drifts
+    for p in L1P_PERIODS:
+        add("period/%d" % p, (rnd.randbytes(p) * (2200 // p + 2))[:2200], period=p)
+    add("period/258_two_fragments", (rnd.randbytes(258) * 200)[:FRAG + 1000], period=258)
+    add("period/259_two_fragments", (rnd.randbytes(259) * 200)[:FRAG + 1000], period=259)
+    # -- matches of 31, 32, 33 bytes back to back through a whole fragment: 37 strings in an order where no pair of
+    # neighbours repeats, so every match ends where its string ends
+    for size in L1P_BACK_TO_BACK:
+        units = _p_units(rnd, 37, size)
+        add("spec/back_to_back_%d" % size, b"".join(units[i] for i in every_pair_once(37))[:FRAG], back_to_back=size)
+    # -- a match that ends exactly on a chunk edge, and one on a wave edge
+    key = rnd.randbytes(40)
+    add("spec/ends_on_chunk_edge", body[:5] + key[:20] + body[5:56] + key[:20] + body[56:250], has=[(76, 71, 20)])
+    add("spec/ends_on_wave_edge", noise[:1900] + key + noise[1940:2008] + key + noise[2048:2300], has=[(2008, 108, 40)])
+    # -- a phase pair: period 33 through a whole fragment; the second input's periodicity begins 6 bytes earlier
+    pattern = rnd.randbytes(33)
+    head = rnd.randbytes(19) + bytes([pattern[-1] ^ 0x55])
+    add("spec/phase_a", head + (pattern * 1000)[:FRAG - 20])
+    add("spec/phase_b", head[:14] + pattern[-6:] + (pattern * 1000)[:FRAG - 20])
+    # -- text: walks from different entries meet (a thread that walks its chunk again knows some lengths already)
+    add("text/one_fragment", alice[20000:20000 + FRAG])
+    add("text/40001", html[5000:45001])
+    add("text/three_fragments", alice[:40000] + html[:2 * FRAG + 19 - 40000])
+    # -- dense: a four-byte match every four bytes, close to the fragment's room for match records
+    units = _p_units(rnd, L1P_DENSE_WORDS, 4)
+    add("dense/four_byte_matches", b"".join(units[i] for i in every_pair_once(L1P_DENSE_WORDS))[:FRAG], {"min5"})
+    assert len({c[0] for c in out}) == len(out) and all(len(c[1]) <= 3 * FRAG for c in out)
+    _compress_craft_cache["P"] = out
+    return list(out)
+
+
+_l1p_model_cache = {}
+
+
+def l1p_model_of(name, src):
+    """tests/l1p_model.py's matches of a named input, worked out once a process"""
+    import l1p_model as lm
+    if name not in _l1p_model_cache:
+        _l1p_model_cache[name] = (src, lm.model(src))
+    assert _l1p_model_cache[name][0] == src, name
+    return _l1p_model_cache[name][1]
+
+
+def l1p_token_cases(small=False):
+    """what check_l1p_tokens runs: family P, edge_inputs(), two `synth` mix buffers of 70000 bytes and family M
+    (small: M's subset for the emulator) -> [(name, bytes)]"""
+    cases = [(n, s) for n, s, _ in l1p_crafted_inputs()]
+    cases += [("edge/%d" % i, s) for i, s in enumerate(edge_inputs())]
+    cases += [("mix/%d" % i, b.tobytes()) for i, b in enumerate(synth.gen_batch("mix", 2, 70000, first_index=40))]
+    cases += [(c[0], c[1]) for c in crafted_inputs(small) if c[0].startswith("M/")]
+    return cases
+
+
+def l1p_same_step_cases(cases):
+    """the names of the cases whose tokens, by the model, depend on a candidate that entered the table in the same
+    64-position step as its position (a device that serves a step's lanes in another order may not see it)"""
+    import l1p_model as lm
+    return {name for name, src in cases if lm.model(src, "step_granular") != l1p_model_of(name, src)}
+
+
+def check_l1p_tokens(eng, cases, skip=()):
+    """Contract mode's tokens (zh_debug_tokens follows the switch) are the rule's, token for token: the matches of
+    tests/l1p_model.py in order, covering the input.  skip: names left out, each printed with its reason."""
+    bad = []
+    eng.set_l1_parse(1)
+    try:
+        for name, src in cases:
+            if name in skip:
+                print("check_l1p_tokens: %s left out: its tokens depend on a same-step candidate, and this device does "
+                      "not serve a step's lanes in ascending order" % name)
+                continue
+            got, covered = token_matches(eng.debug_tokens(src, 1))
+            want = l1p_model_of(name, src)
+            if got != want or covered != len(src):
+                k = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+                bad.append((name, "token %d" % k, "device", got[k:k + 2], "model", want[k:k + 2], "covered", covered, len(src)))
+    finally:
+        eng.set_l1_parse(-1)
+    assert not bad, bad
+
+
+def l1p_multi_fragment_cases():
+    """the cases one workgroup has to take fragment after fragment under ZH_L1P_SLOTS=1: family P's inputs of more than
+    one fragment"""
+    return [(n, s) for n, s, _ in l1p_crafted_inputs() if len(s) > FRAG]
+
+
+def check_l1p_one_slot(preamble, skip=()):
+    """check_l1p_tokens over l1p_multi_fragment_cases() in a child process with ZH_L1P_SLOTS=1 (read once a process):
+    one persistent workgroup takes every fragment of a buffer.  preamble: Python source that leaves the engine in `eng`;
+    skip: as check_l1p_tokens takes it."""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (here, os.path.dirname(here)) + preamble +
+            "\nimport parity_cases as pc\n"
+            "pc.check_l1p_tokens(eng, pc.l1p_multi_fragment_cases(), %r)\n" % (tuple(sorted(skip)),))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, ZH_L1P_SLOTS="1"), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def check_l1p_alignment(eng, upload, download, alloc):
+    """One family P text at source offsets of all four alignments modulo 4, level 1 in contract mode: in one
+    compress_batch with 1-, 2- and 3-byte buffers between the copies, and through the device plan API at unaligned
+    offsets -- every copy gives the bytes the buffer gives alone, and its tokens are the model's.  (The host batch
+    stages every source in a slot of its own, aligned: it is the device plan that moves the fragments off the dwords.
+    A full fragment there once lost its last 1..3 bytes to the zeroed slack: streams that did not decode.)"""
+    name, text = next((n, s) for n, s, _ in l1p_crafted_inputs() if n == L1P_ALIGN_TEXT)
+    assert len(text) == 40001
+    eng.set_gzip_fname_len(0)
+    eng.set_l1_parse(1)
+    try:
+        alone = eng.compress(text, 1, oracle.dfDeflate)
+        assert zlib.decompress(alone, -15) == text
+        batch = [text, b"a", text, b"bc", text, b"def", text]
+        outs, sts = eng.compress_batch(batch, 1, oracle.dfDeflate)
+        assert all(st == 0 for st in sts)
+        assert [outs[i] == alone for i in (0, 2, 4, 6)] == [True] * 4, "the stream depends on the source's alignment"
+        blob, soff = bytearray(), []
+        for want, pad in zip((3, 2, 1, 0), (3, 1, 7, 2)):   # at least `pad` bytes of something else in front, then up to `want`
+            blob += b"\xaa" * pad
+            blob += b"\xaa" * ((want - len(blob)) % 4)
+            soff.append(len(blob))
+            blob += text
+        assert [o % 4 for o in soff] == [3, 2, 1, 0]
+        d_src, keep_src = upload(bytes(blob) + b"\0" * 64)
+        cap = eng.compress_bound(len(text))
+        doff = [5 + i * (cap + 3) for i in range(4)]
+        d_dst, keep_dst = alloc(doff[-1] + cap + 64, 0xAB)
+        plan = eng.plan_compress(soff, [len(text)] * 4, doff, [cap] * 4, 1, oracle.dfDeflate)
+        plan.run(d_src, d_dst)
+        lens, sts = plan.results()
+        assert list(sts) == [0] * 4
+        host = download(keep_dst)
+        for o, n in zip(doff, lens):
+            assert host[o:o + n] == alone, "device API: the stream depends on the source's alignment (offset %d)" % o
+    finally:
+        eng.set_l1_parse(-1)
+    assert _stream_matches(dc.read_blocks(alone)) == l1p_model_of(name, text)
+
+
+def _stream_matches(blocks):
+    """read_blocks' tokens -> [(position, offset, length)]"""
+    out, pos = [], 0
+    for blk in blocks:
+        for t in blk["tokens"]:
+            if t[0] == "lit":
+                pos += 1
+            else:
+                out.append((pos, t[2], t[1]))
+                pos += t[1]
+    return out
+
+
+def check_l1p_streams(eng):
+    """Family P compressed to dfDeflate in contract mode, read back with deflate_craft.read_blocks: the stream's
+    matches are the model's and its tokens cover the input (the literal runs need not be cut alike); in every dynamic
+    block the header's code lengths are those zh_debug_huffman(contract) makes of the histogram counted from that
+    block's own tokens plus the end-of-block symbol, for both alphabets -- so the fragment histograms the matcher wrote
+    are exact.  -> the number of dynamic blocks that hold matches."""
+    cases = l1p_crafted_inputs()
+    eng.set_l1_parse(1)
+    try:
+        outs, sts = eng.compress_batch([c[1] for c in cases], 1, oracle.dfDeflate)
+    finally:
+        eng.set_l1_parse(-1)
+    dynamic_with_matches = 0
+    for (name, src, _), out, st in zip(cases, outs, sts):
+        assert st == 0, (name, st)
+        blocks = dc.read_blocks(out)
+        assert dc.replay(blocks) == src, name
+        if {blk["type"] for blk in blocks} == {0}:   # (noise around one repeat: the block is stored, its matches dropped)
+            continue
+        assert _stream_matches(blocks) == l1p_model_of(name, src), name
+        for k, blk in enumerate(blocks):
+            if blk["type"] != 2:
+                continue
+            lit, dist = np.zeros(286, np.uint32), np.zeros(30, np.uint32)
+            lit[256] = 1
+            for t in blk["tokens"]:
+                if t[0] == "lit":
+                    lit[t[1]] += 1
+                else:
+                    lit[257 + (28 if t[1] == 258 else max(i for i in range(28) if dc.LEN_BASE[i] <= t[1]))] += 1
+                    dist[max(i for i in range(30) if dc.DIST_BASE[i] <= t[2])] += 1
+            _, lit_lens = eng.debug_huffman(lit, 257, 15, contract=True)
+            _, dist_lens = eng.debug_huffman(dist, 2, 15, contract=True)
+            assert list(lit_lens[:len(blk["lit_lens"])]) == blk["lit_lens"] and not any(lit_lens[len(blk["lit_lens"]):]), (name, k, "litlen")
+            assert list(dist_lens[:len(blk["dist_lens"])]) == blk["dist_lens"] and not any(dist_lens[len(blk["dist_lens"]):]), (name, k, "distance")
+            dynamic_with_matches += bool(dist.any())
+    assert dynamic_with_matches >= 1
+    return dynamic_with_matches

@@ -92,3 +92,53 @@ def test_crafted_streams_small_subset():
     assert len(tok48) == 512 and len(fixed) == 512 and len(dynamic) == 512
     assert sum(1 for p, bits, kind in info["T1/48_bit_tokens"][0]) <= 601
     assert sum(len(c[2]) for c in cases if c[2] is not None) < 600000
+
+
+def test_reader_against_zlib_and_oracle_streams():
+    """deflate_craft.read_blocks, the reader the parallel parse's streams are held against (check_l1p_streams): what
+    its tokens replay to is what zlib.decompressobj makes of streams zlib and the oracle wrote -- stored, fixed and
+    dynamic blocks, several blocks a stream --, and it reads the builder's own tokens and code lengths back"""
+    import random
+    import synth
+    alice, html = synth.corpus_file("alice29.txt"), synth.corpus_file("html")
+    plains = [alice[:70000], html[:40000], b"", b"a", b"\x00" * 70000, random.Random(9).randbytes(3000), b"ab" * 20000,
+              alice[:300]]
+    streams = []
+    for plain in plains:
+        for level, strategy in ((1, zlib.Z_DEFAULT_STRATEGY), (6, zlib.Z_DEFAULT_STRATEGY), (9, zlib.Z_FIXED), (0, zlib.Z_DEFAULT_STRATEGY)):
+            co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+            streams.append((co.compress(plain[:len(plain) // 2]) + co.flush(zlib.Z_FULL_FLUSH) + co.compress(plain[len(plain) // 2:]) +
+                            co.flush(), plain))
+        for level in (1, -1, -2, 0):
+            streams.append((oracle.compress(plain, level, oracle.dfDeflate), plain))
+    types = set()
+    for raw, plain in streams:
+        d = zlib.decompressobj(-15)
+        want = d.decompress(raw)
+        assert d.eof and want == plain
+        blocks = dc.read_blocks(raw)
+        assert dc.replay(blocks) == want
+        assert blocks[-1]["final"] and not any(b["final"] for b in blocks[:-1])
+        types |= {b["type"] for b in blocks}
+        for b in blocks:
+            if b["type"] == 2:
+                assert 257 <= len(b["lit_lens"]) <= 286 and 1 <= len(b["dist_lens"]) <= 30 and b["lit_lens"][256]
+                assert dc.kraft(b["lit_lens"]) <= 32768 and dc.kraft(b["dist_lens"]) <= 32768
+    assert types == {0, 1, 2}
+    # the builder's own: tokens and code lengths come back as written
+    s = dc.Stream()
+    lit, dist = pc._t1_code()
+    s.stored(bytes(range(120)), False, pad_bits=0x0a)
+    s.dynamic_block(lit, dist, False, {"symbols": dc.rle_plain(lit + dist)})
+    s.lit(0), s.lit(255), s.match(5, 2), s.match(3, 1), s.match(258, 100, length_symbol=284), s.eob()
+    s.fixed_block(True)
+    s.lit(65), s.match(4, 1), s.match(258, 5), s.eob()
+    raw, plain, status = s.finish()
+    assert status is None
+    blocks = dc.read_blocks(raw)
+    assert [b["type"] for b in blocks] == [0, 2, 1] and dc.replay(blocks) == plain
+    assert blocks[0]["tokens"] == [("lit", b) for b in range(120)]
+    assert blocks[1]["lit_lens"] == list(lit) and blocks[1]["dist_lens"] == list(dist)
+    assert blocks[1]["tokens"] == [("lit", 0), ("lit", 255), ("match", 5, 2), ("match", 3, 1), ("match", 258, 100)]
+    assert blocks[2]["tokens"] == [("lit", 65), ("match", 4, 1), ("match", 258, 5)]
+    assert blocks[2]["lit_lens"] == dc.FIXED_LIT_LENS and blocks[2]["dist_lens"] == dc.FIXED_DIST_LENS

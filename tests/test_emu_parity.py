@@ -420,3 +420,31 @@ def test_emu_crafted_matcher_tokens(eng):
 def test_emu_crafted_contract(eng):
     pc.check_crafted_contract(eng, _family(True, "R"), margin=None)
     pc.check_parallel_parse(eng, [c[1] for c in _family(True, "M")])
+
+
+def _host_memory():
+    import ctypes
+    def upload(b):
+        buf = ctypes.create_string_buffer(b, len(b))
+        return ctypes.addressof(buf), buf
+    def alloc(n, fill):
+        buf = ctypes.create_string_buffer(bytes([fill]) * n, n)
+        return ctypes.addressof(buf), buf
+    return upload, lambda keep: keep.raw, alloc
+
+
+def test_emu_l1p_tokens(eng):
+    """contract mode's tokens are the rule's of tests/l1p_model.py, token for token: family P, the edge inputs, two mix
+    buffers and family M; the inputs of several fragments once more with one workgroup for all of them"""
+    assert eng.chain_links_parallel()
+    pc.check_l1p_tokens(eng, pc.l1p_token_cases(small=True))
+    pc.check_l1p_one_slot("import emu\neng = emu.engine()")
+
+
+def test_emu_l1p_alignment(eng):
+    upload, download, alloc = _host_memory()
+    pc.check_l1p_alignment(eng, upload, download, alloc)
+
+
+def test_emu_l1p_streams(eng):
+    pc.check_l1p_streams(eng)

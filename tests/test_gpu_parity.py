@@ -615,3 +615,28 @@ def test_gpu_crafted_contract(eng):
     pc.check_crafted_contract(eng, _family("R"), margin=None)
     dev, ref = pc.check_parallel_parse(eng, [c[1] for c in _family("M")])
     print("parallel parse over the M inputs: %d B against the oracle's %d B (%.4f)" % (dev, ref, dev / ref))
+
+
+def test_gpu_l1p_tokens(eng):
+    """contract mode's tokens are the rule's of tests/l1p_model.py, token for token: family P, the edge inputs, two mix
+    buffers and family M; the inputs of several fragments once more with one workgroup for all of them (child process).
+    On a device that fails the LDS lane-order probe the cases that need a same-step candidate are left out by name."""
+    cases = pc.l1p_token_cases()
+    skip = () if eng.chain_links_parallel() else pc.l1p_same_step_cases(cases)
+    pc.check_l1p_tokens(eng, cases, skip)
+    pc.check_l1p_one_slot("import torch; torch.cuda.init()\nfrom zippy_amd import api\neng = api.engine()", skip)
+
+
+def test_gpu_l1p_alignment(eng):
+    import torch
+    def upload(b):
+        t = torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda()
+        return t.data_ptr(), t
+    def alloc(n, fill):
+        t = torch.full((n,), fill, dtype=torch.uint8, device="cuda")
+        return t.data_ptr(), t
+    pc.check_l1p_alignment(eng, upload, lambda t: t.cpu().numpy().tobytes(), alloc)
+
+
+def test_gpu_l1p_streams(eng):
+    pc.check_l1p_streams(eng)

@@ -230,7 +230,10 @@ extern "C" int zh_debug_tokens(zh_ctx* ctx, const void* src, size_t len, int lev
   zh_plan* p = pg.p;
   hipStream_t s = ctx->stream;
   const ZhCompressArgs& a = p->ca;
-  if (level == 1 || level == -2) {
+  if (level == 1 && l1_parallel(ctx)) {  // (the parse run_compress takes under the switch: same records behind it)
+    zh_launch_l1p_match(s, d_src.p, a, p->l1_tables, p->l1_counter);
+    ZH_HIP(ctx, hipGetLastError());
+  } else if (level == 1 || level == -2) {
     st = run_l1_match(p, d_src.p, false);  // (a single run: nothing to order the fragments by)
     if (st) return st;
   } else {
@@ -276,9 +279,11 @@ extern "C" int zh_debug_tokens(zh_ctx* ctx, const void* src, size_t len, int lev
     for (uint64_t o = 0; o < blen; o += ZH_FRAG_SIZE, f++) {
       const uint64_t flen = std::min<uint64_t>(blen - o, ZH_FRAG_SIZE);
       uint64_t cursor = std::max<uint64_t>(o, covered_until);
+      if (nmatch[f] > ZH_MAX_MATCHES_PER_FRAG) return ZH_ERR_COMPRESS_INTERNAL;
       for (uint32_t m = 0; m < nmatch[f]; m++) {
         const size_t k = f * ZH_MAX_MATCHES_PER_FRAG + m;
         const uint64_t mp = o + mpos[k];
+        if (mp < cursor) return ZH_ERR_COMPRESS_INTERNAL;  // (records that overlap: no parse at all -- say so, do not loop)
         run += mp - cursor;
         add_literals(run);
         run = 0;

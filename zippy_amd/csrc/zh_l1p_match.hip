@@ -5,7 +5,10 @@
 // *different*, equally valid token stream under the contract BASELINE.json's north star
 // states for the encoder: an RFC 1951 stream that zippy's uncompress() decodes to the input
 // bit for bit, with a compressed size within a stated margin of zippy's at the same level
-// (tests: every buffer through oracle.uncompress and zlib, aggregate size <= 1.02 x oracle).
+// (tests: every buffer through oracle.uncompress and zlib, aggregate size <= 1.02 x oracle; and the tokens themselves
+// against the kernel's own rule as one serial function, tests/l1p_model.py: check_l1p_tokens over the crafted family P
+// of tests/parity_cases.py, check_l1p_streams for the histograms behind them, check_l1p_alignment for sources that do
+// not start on a dword).
 // Everything behind the match list -- statistics, Huffman codes, layout, emission -- is the
 // exact path's.  Same fragment rule as the reference (snappy.nim:150-163): matches never
 // leave their 32 KiB fragment, so fragments stay independent.
@@ -173,7 +176,9 @@ __global__ __launch_bounds__(kT, 8) void zh_l1p_match_kernel(const uint8_t* __re
       for (uint32_t k = 0; k < 8192 / 4 / kT; k++)
         *reinterpret_cast<uint4*>(s_src + (k * kT + t) * 4u) = make_uint4(v[k].x, v[k].y, v[k].z, v[k].w);
     }
-    for (uint32_t i = 8192 + t; i < kSrcWords; i += kT) s_src[i] = 0;
+    // the slack behind: zeros -- but for dword 8192 of a full fragment that does not start on a dword: it holds the
+    // fragment's last `mis` bytes (left zero, they were compared and counted as zeros: streams that did not decode)
+    for (uint32_t i = 8192 + t; i < kSrcWords; i += kT) s_src[i] = i < ndw ? asrc[i] : 0u;
     __syncthreads();
     // (unaligned ds_read_b32 / b64 work on gfx950 but cost this kernel a factor of two: measured)
     auto ld32 = [&](uint32_t p) -> uint32_t { return zh_ld32(s_src, p + mis); };

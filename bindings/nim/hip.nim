@@ -704,6 +704,36 @@ proc hipSeekReadRange*(src, index: string, off, len: uint64): string {.raises: [
                                dst.addr, dstLen.addr, st.addr)
   take(dst, dstLen, if rc != 0: rc else: st.cint)
 
+# ---- resumable uncompress: a stream decoded as its bytes arrive (no counterpart in the reference) ----
+const ZhResumeDone* = 0'i32; const ZhResumeNeedInput* = 1'i32; const ZhResumeNeedOutput* = 2'i32
+proc zh_uncompress_resume_batch(ctx: ZhCtx, srcs: ptr pointer, lens: ptr csize_t, n: csize_t, dataFormat: cint,
+                                states: ptr pointer, stateLens: ptr csize_t, maxOut: ptr uint64, last: ptr uint8,
+                                dsts: ptr pointer, dstLens: ptr csize_t, consumed: ptr csize_t, newStates: ptr pointer,
+                                newStateLens: ptr csize_t, why: ptr int32,
+                                statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipUncompressResume*(tail: string, state: var string, consumed: var int, why: var int32, maxOut = 1'u64 shl 20,
+                          last = false, dataFormat = dfDetect): string {.raises: [ZippyError].} =
+  ## one step of one stream: `tail` is what the step before left unconsumed followed by what arrived since, `state` the
+  ## state that step returned ("" for a new stream; it is replaced).  Returns the bytes of the deflate blocks that became
+  ## whole; why: ZhResumeDone (trailer verified), ZhResumeNeedInput, ZhResumeNeedOutput (a block larger than maxOut).
+  var p = if tail.len > 0: tail[0].unsafeAddr.pointer else: nil
+  var len = tail.len.csize_t
+  var sp = if state.len > 0: state[0].unsafeAddr.pointer else: nil
+  var slen = state.len.csize_t
+  var mo = maxOut
+  var lf = if last: 1'u8 else: 0'u8
+  var dst, ns: pointer; var dstLen, used, nsLen: csize_t; var st: int32
+  let rc = zh_uncompress_resume_batch(engine(), p.addr, len.addr, 1, dataFormat.cint, sp.addr, slen.addr, mo.addr,
+                                      lf.addr, dst.addr, dstLen.addr, used.addr, ns.addr, nsLen.addr, why.addr, st.addr)
+  var next = newString(nsLen.int)
+  if ns != nil:
+    if nsLen > 0: copyMem(next[0].addr, ns, nsLen.int)
+    zh_free(ns)
+  state = next
+  consumed = used.int
+  take(dst, dstLen, if rc != 0: rc else: st.cint)
+
 # ---- any gzip file: several members, FEXTRA / FNAME / FCOMMENT / FHCRC (no counterpart in the reference) ----
 type
   ZhGzipMember* {.bycopy.} = object

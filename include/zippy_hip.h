@@ -611,6 +611,82 @@ int zh_seek_read_ranges(zh_ctx *ctx, const void *const *srcs, const size_t *lens
                         void **dsts, size_t *dst_lens, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
+ * Resumable uncompress: streams decoded as their bytes arrive.        *
+ * Host buffers in, library-allocated results out (zh_free); statuses  *
+ * per stream; the return value is ZH_OK unless the call as a whole    *
+ * could not run.                                                      *
+ * ------------------------------------------------------------------ */
+/* What carries a stream from one call to the next is one flat little-endian blob (library-allocated, zh_free; the
+ * caller keeps it and hands it back): this header and the last win_len bytes made.  The same stream, the same
+ * chunking and the same max_out give the same bytes. */
+#define ZH_RESUME_MAGIC "ZHRESUM1"
+#define ZH_RESUME_VERSION 1u
+typedef struct zh_resume_header { /* 64 bytes, little endian; win_len bytes of window follow */
+  char magic[8];
+  uint32_t version;
+  uint32_t data_format; /* resolved: ZH_DF_ZLIB, ZH_DF_GZIP or ZH_DF_DEFLATE */
+  uint32_t phase;       /* 1: the next bit is a block header; 2: the final block is done, the trailer is due */
+  uint32_t bit_skip;    /* 0..7: that bit's place in the first byte of the next call's input (0 in phase 2) */
+  uint64_t total_in;    /* bytes consumed by all calls so far */
+  uint64_t total_out;   /* bytes made by all calls so far */
+  uint32_t check;       /* running CRC-32 (gzip) / Adler-32 (zlib) of those bytes; 0 for raw deflate */
+  uint32_t win_len;     /* min(total_out, 32768): the last win_len bytes made */
+  uint64_t reserved[2]; /* 0 */
+} zh_resume_header;
+enum { ZH_RESUME_DONE = 0, ZH_RESUME_NEED_INPUT = 1, ZH_RESUME_NEED_OUTPUT = 2 };
+
+/* One call decodes, for every stream i, as many WHOLE deflate blocks as srcs[i] holds and max_out[i] allows: every
+ * block whose last bit lies inside the input and whose output, added to what the call has made already, stays at or
+ * below max_out[i]; it stops at the first block that fails either test (empty blocks count as progress).  For a new
+ * stream (states[i] NULL; states NULL: all of them) srcs[i] starts at the container's header and data_format is
+ * resolved as in zh_uncompress_batch -- with four bytes in hand --; otherwise srcs[i] starts at the byte the call
+ * before left, srcs_prev[i] + consumed_prev[i], the unconsumed tail followed by what arrived since, the first block
+ * header at bit bit_skip of byte 0, and the format is the state's.  dsts[i] / dst_lens[i] (zh_free; NULL for no
+ * bytes) hold exactly the delivered blocks' bytes; consumed[i] is the index of the byte that holds the next block's
+ * first bit (that byte is consumed only when bit_skip is 0); new_states[i] / new_state_lens[i] (zh_free) the state to
+ * come back with.  why[i], the earliest event in stream order deciding (one exception: the output is written in rounds of
+ * up to 64 bytes, and while a stream has made fewer than 32768 bytes a distance beyond the window anywhere in a round
+ * is ZH_ERR_INVALID_BUFFER even where the budget was passed a token earlier in that round):
+ *   ZH_RESUME_DONE         the final block is delivered and the trailer verified -- CRC-32 (ZH_ERR_CHECKSUM) and
+ *                          ISIZE (ZH_ERR_SIZE), or Adler-32, nothing for raw deflate --; consumed[i] is the index just
+ *                          behind the trailer (a following member's bytes are not looked at), new_states[i] is NULL;
+ *   ZH_RESUME_NEED_INPUT   the input ended inside a block, a block header or the trailer (phase 2);
+ *   ZH_RESUME_NEED_OUTPUT  the next block would pass max_out[i].
+ * The container's header: the checks and statuses of zh_uncompress_batch (no FEXTRA, no preset dictionary; FHCRC is
+ * skipped), made once the header is whole: ten bytes of a gzip member and its name, comment and header CRC, two bytes
+ * of a zlib stream.  A header that the end of the input cuts short is ZH_RESUME_NEED_INPUT with consumed[i] 0 and no
+ * state: come back with more bytes and a NULL state.
+ * Soundness: a prefix of a stream that zh_uncompress_batch decodes with ZH_OK never yields an error, at any cut: no
+ * check is decided by a bit at or beyond 8 * lens[i].  A field, a code or a token that the end of the input cuts, a
+ * stored block whose bytes are not all there, and a pattern that no code claims with fewer bits behind it than the
+ * longest code may have (7 in a dynamic header's code-length code, 15 elsewhere) are ZH_RESUME_NEED_INPUT.
+ * last[i] != 0 (last NULL: none) promises that no more input exists: the end of the input is the end of the stream,
+ * the checks read zeros behind it as zh_uncompress_batch's do, and where ZH_RESUME_NEED_INPUT would be answered the
+ * status is the whole call's: ZH_ERR_END_OF_BUFFER inside a block, what the zeros make of a block header
+ * (ZH_ERR_INVALID_BUFFER at a block boundary), ZH_ERR_CHECKSUM inside the trailer; a new stream's header is judged
+ * with zh_uncompress_batch's own length rules (those rules speak of the whole stream's length -- more than 18 bytes of
+ * gzip, 6 of zlib --: a shorter stream that comes in several calls ends with the decoder's or the trailer's status
+ * instead).  A definite error may surface in an earlier call, with the same code; the blocks that EARLIER calls made
+ * whole were delivered by then.  The call that meets the error delivers nothing, the good blocks in front of the
+ * damaged one included: who wants what was decodable before the damage feeds smaller pieces or a smaller max_out.
+ * statuses[i] != ZH_OK gives stream i no output, no state and consumed[i] 0, and never disturbs its neighbours.  A
+ * match that reaches beyond the window is ZH_ERR_INVALID_BUFFER.  A state that cannot be right -- magic, version,
+ * format, phase outside 1..2, bit_skip > 7 or non-zero in phase 2, win_len != min(total_out, 32768), a length other
+ * than 64 + win_len, reserved != 0 -- fails its stream with ZH_ERR_INVALID_BUFFER before anything is uploaded.
+ * ZH_ERR_ARGUMENT for the call: NULL arrays; a NULL source with a non-zero length; a NULL state with a non-zero
+ * length; max_out[i] == 0; state_lens without states or states without state_lens.  n == 0 launches nothing.  A
+ * call that fails as a whole hands nothing out: every dsts[i] and new_states[i] is NULL.
+ * A call makes progress only when the input holds a whole block and max_out its output (zlib's blocks are tens of
+ * KiB, this library's up to 4 MiB of data); resuming inside a block is not offered.  One stream decodes on one
+ * workgroup: many streams side by side is the case this serves.  Scratch is bounded by ZH_SCRATCH_MB, groups of
+ * streams taking turns. */
+int zh_uncompress_resume_batch(zh_ctx *ctx, const void *const *srcs, const size_t *lens, size_t n, int data_format,
+                               const void *const *states, const size_t *state_lens, /* NULL entry: a new stream */
+                               const uint64_t *max_out, const uint8_t *last,        /* last: NULL = none */
+                               void **dsts, size_t *dst_lens, size_t *consumed,
+                               void **new_states, size_t *new_state_lens, int32_t *why, int32_t *statuses);
+
+/* ------------------------------------------------------------------ *
  * ZIP archives as batch clients of the codec. *
  * Record parsing / assembly of src/zippy/ziparchives.nim on the host, *
  * every entry's deflate stream and CRC-32 in ONE GPU batch.  The file *

@@ -126,6 +126,12 @@ _SIGS = {
                                        _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                        _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
                                        _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
+    "zh_uncompress_resume_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                              _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
+                                              _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint8),
+                                              _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t),
+                                              _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32),
+                                              _c.POINTER(_c.c_int32)]),
     "zh_crc32_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                   _c.POINTER(_c.c_uint32)]),
     "zh_compress_batch_crc32": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
@@ -1072,6 +1078,47 @@ class Engine:
                     self.lib.zh_free(dsts[r])
         self._check(rc)
         return outs, list(sts)[:nr]
+
+    # ---- resumable uncompress ----
+    def uncompress_resume_batch(self, srcs, states=None, max_out=1 << 20, last=None, dataFormat=dfDetect):
+        """One step of every stream (zh_uncompress_resume_batch): srcs[i] is the unconsumed tail of stream i followed by
+        what arrived since, states[i] the state the step before returned (None: a new stream; states None: all new),
+        max_out a number or one a stream, last None or one flag a stream.
+        -> (outputs, consumed, new_states, why, statuses); an output is b"" and a state None where nothing came."""
+        n = len(srcs)
+        m = max(1, n)
+        keep = [bytes(b) for b in srcs]
+        blobs = [bytes(b) if b is not None else None for b in (states if states is not None else [None] * n)]
+        if len(blobs) != n:
+            raise ValueError("states: one per stream")
+        budgets = list(max_out) if hasattr(max_out, "__len__") else [max_out] * n
+        flags = [1 if f else 0 for f in last] if last is not None else None
+        if len(budgets) != n or (flags is not None and len(flags) != n):
+            raise ValueError("max_out, last: one per stream")
+        ptrs = (_c.c_void_p * m)(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * m)(*[len(k) for k in keep])
+        sp = (_c.c_void_p * m)(*[_c.cast(_c.c_char_p(b), _c.c_void_p) if b is not None else None for b in blobs])
+        sl = (_c.c_size_t * m)(*[len(b) if b is not None else 0 for b in blobs])
+        mo = _u64(budgets + [0] * (m - n))
+        lf = (_c.c_uint8 * m)(*flags) if flags is not None else None
+        dsts, dlens, used = (_c.c_void_p * m)(), (_c.c_size_t * m)(), (_c.c_size_t * m)()
+        ns, nsl, why, sts = (_c.c_void_p * m)(), (_c.c_size_t * m)(), (_c.c_int32 * m)(), (_c.c_int32 * m)()
+        rc = self.lib.zh_uncompress_resume_batch(self._h, ptrs, lens, n, int(dataFormat),
+                                                 sp if states is not None else None, sl if states is not None else None,
+                                                 mo, lf, dsts, dlens, used, ns, nsl, why, sts)
+        outs, new_states = [], []
+        try:
+            for i in range(n):
+                outs.append(_c.string_at(dsts[i], dlens[i]) if dsts[i] else b"")
+                new_states.append(_c.string_at(ns[i], nsl[i]) if ns[i] else None)
+        finally:
+            for i in range(n):
+                if dsts[i]:
+                    self.lib.zh_free(dsts[i])
+                if ns[i]:
+                    self.lib.zh_free(ns[i])
+        self._check(rc)
+        return outs, list(used)[:n], new_states, list(why)[:n], list(sts)[:n]
 
     def crc32(self, src):
         src = bytes(src)

@@ -176,6 +176,66 @@ def seek_read_range(src, index, off, length):
     return eng._raise_first(outs, sts)[0]
 
 
+def uncompress_resume_batch(srcs, states=None, max_out=1 << 20, last=None, dataFormat=dfDetect):
+    """One step of many streams whose bytes arrive in pieces (zlib, gzip, raw), in one call: every stream decodes as many
+    whole deflate blocks as its input holds and max_out allows.  srcs[i]: the unconsumed tail of stream i and what arrived
+    since; states[i]: the state its step before returned (None: a new stream); last[i]: no more input will come.
+    -> (outputs, consumed, new_states, why, statuses); why: 0 done (trailer verified), 1 more input, 2 more room."""
+    return engine().uncompress_resume_batch(srcs, states, max_out, last, dataFormat)
+
+
+class Inflater:
+    """One stream decoded as its bytes arrive: feed(chunk) -> the bytes of the deflate blocks that became whole.  It
+    keeps the unconsumed tail and the state between calls, doubles its budget where a block outgrows max_out, and raises
+    ZippyError where the stream is damaged -- with last=True also where it ends early.  The call that meets the damage
+    returns nothing, the good blocks of the same chunk included: feed smaller chunks to get what was decodable before
+    it.  .done: the trailer is verified; .unused: the bytes behind it."""
+
+    def __init__(self, fmt=dfDetect, max_out=1 << 20):
+        self.fmt, self.max_out = fmt, max_out
+        self.state, self.tail, self.done = None, b"", False
+
+    @property
+    def unused(self):
+        return self.tail
+
+    def feed(self, chunk, last=False):
+        self.tail += bytes(chunk)
+        if self.done:
+            return b""
+        eng = engine()
+        made = []
+        while True:
+            outs, used, states, why, sts = eng.uncompress_resume_batch([self.tail], [self.state], self.max_out,
+                                                                       [last], self.fmt)
+            eng._raise_first(outs, sts)
+            made.append(outs[0])
+            self.tail = self.tail[used[0]:]
+            self.state = states[0]
+            if why[0] == 2:  # a block larger than the budget
+                if not outs[0]:
+                    self.max_out *= 2
+                continue
+            self.done = why[0] == 0
+            return b"".join(made)
+
+
+def uncompress_chunks(chunks, dataFormat=dfDetect, max_out=1 << 20):
+    """uncompress() of a stream that comes as an iterable of byte pieces: yields the data as its blocks become whole;
+    raises ZippyError where the stream is damaged or ends early."""
+    inf = Inflater(dataFormat, max_out)
+    held = None
+    for chunk in chunks:
+        if held is not None:
+            out = inf.feed(held)
+            if out:
+                yield out
+        held = chunk
+    out = inf.feed(held if held is not None else b"", last=True)
+    if out:
+        yield out
+
+
 def openZipArchive(image):
     """ziparchives.nim:183 openZipArchive on the bytes of an archive -> reader with walk_files(),
     extract_file(path), extract_batch(indices)."""

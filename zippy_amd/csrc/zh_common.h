@@ -158,6 +158,16 @@ struct ZhSeekStop {
   const uint32_t* hist_len;
   const uint64_t* stop_bit;
 };
+// A resumed decode (zh_resume_inflate_kernel, zh_resume.hip): "stream" i's slot holds hist_len[i] bytes of history in
+// front of its output, and its decode runs until the input or the slot gives out.  out_len[i]: the bytes of the whole
+// blocks made (the history not counted), bit[i]: the block boundary behind them (counted like
+// ZhInflateArgs::start_bit), why[i]: ZH_RESUME_*; status[i] is ZH_OK unless the stream is damaged.
+struct ZhResume {
+  const uint32_t* hist_len;
+  const uint8_t* last;  // the caller promised that no more input exists: the end of the input is the stream's
+  uint64_t* bit;
+  int32_t* why;
+};
 
 // One large stream decoded by many workgroups (zh_inflate_seg.hip).  The compressed bytes are cut
 // into segments; a segment's decoder starts at the first deflate block found at or behind the

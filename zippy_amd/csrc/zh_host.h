@@ -1,12 +1,13 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in sixteen files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in seventeen files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing -- run_compress, run_uncompress with run_segmented, run_ranges; work beside a run
 // on the context's second stream: SideLane --, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
 // wire), zh_host_batch.hip (host-buffer batches: staging, pipelined groups, sharding over contexts),
 // zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks), zh_ranges.hip (byte-range
 // reads from block-indexed streams: geometry, host call and its two kernels), zh_seek.hip (seek indexes for foreign
-// streams: build, range reads and their kernels), the batch writers
+// streams: build, range reads and their kernels), zh_resume.hip (resumable uncompress: the host call and the resuming
+// form of the wave-pair kernel), the batch writers
 // zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
 // zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
 // all four share, zh_scan.h the signature scan of zh_zip_read_batch.hip and zh_bgzf.hip with its host driver,
@@ -51,6 +52,7 @@ void zh_launch_checksum_combine(hipStream_t, const void* tabs, const ZhBufDesc* 
 void zh_launch_unwrap(hipStream_t, const uint8_t* d_src, ZhInflateArgs a);
 void zh_launch_inflate(hipStream_t, const uint8_t* d_src, uint8_t* d_dst, ZhInflateArgs a);
 void zh_launch_seek_inflate(hipStream_t, const uint8_t* d_src, uint8_t* d_dst, ZhInflateArgs a, ZhSeekStop x);
+void zh_launch_resume_inflate(hipStream_t, const uint8_t* d_src, uint8_t* d_dst, ZhInflateArgs a, ZhResume r);
 void zh_launch_verify(hipStream_t, ZhInflateArgs a, const uint32_t* buf_crc, const uint32_t* buf_adler);
 void zh_launch_inflate_tokens(hipStream_t, const uint8_t* d_src, ZhInflateArgs a, uint32_t* tok_pool,
                               const uint64_t* tok_off, const uint64_t* tok_cap, const ZhRecArgs* rec);

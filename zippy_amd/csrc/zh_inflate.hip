@@ -103,7 +103,7 @@ __global__ void zh_unwrap_kernel(const uint8_t* __restrict__ d_src, ZhInflateArg
 __global__ __launch_bounds__(128, 8) void zh_inflate_kernel(const uint8_t* __restrict__ d_src,
                                                          uint8_t* __restrict__ d_dst,
                                                          ZhInflateArgs a) {
-  zh_inflate_body<false>(d_src, d_dst, a, ZhSeekStop{});
+  zh_inflate_body<kFormBatch>(d_src, d_dst, a, ZhSeekStop{}, ZhResume{});
 }
 
 // Final check of each stream against its trailer (gzip.nim:80-88, zippy.nim:152-162).

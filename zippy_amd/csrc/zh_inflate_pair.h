@@ -1,7 +1,8 @@
 // The wave-pair inflate: the body of zh_inflate_kernel (zh_inflate.hip: batches, the blocks of block-indexed streams)
 // and of zh_seek_inflate_kernel (zh_seek.hip: the intervals of a seek index).  Each kernel is alone in its file: with
 // both in one, the table builder and the slow symbol path had two callers, were no longer inlined, and the existing
-// kernel took 176 bytes of scratch a lane instead of 72.
+// kernel took 176 bytes of scratch a lane instead of 72.  A third form, zh_resume_inflate_kernel (zh_resume.hip), does
+// not know where it will stop: it decodes whole blocks until the input or the output budget gives out.
 #pragma once
 #include "zh_common.h"
 #include "zh_kprof.h"
@@ -30,6 +31,12 @@
 namespace {
 
 constexpr uint32_t kTailNone = 0, kTailLiteral = 1, kTailMatch = 2, kTailStored = 3, kTailEnd = 4;
+// the resuming form: the decode wave stands at a block boundary, tail_off: its bit position, tail_a: the block before
+// it was the final one
+constexpr uint32_t kTailMark = 5;
+// the forms of the body, and the status with which the resuming form's decode wave says "the input ends here"
+constexpr int kFormBatch = 0, kFormSeek = 1, kFormResume = 2;
+constexpr int kStNeedInput = 1000;
 
 struct RoundDesc {
   // per lane and window: output length (9) | literal << 9 | in chain << 10 | value << 16
@@ -50,9 +57,22 @@ struct RoundDesc {
 // where its position is stop_bit, and a position beyond it, or a final block that ends elsewhere, is
 // ZH_ERR_INVALID_BUFFER.  out_len counts the history.  A kernel of its own, zh_seek_inflate_kernel (zh_seek.hip): the
 // kernel of the batches and of the block-indexed forms, zh_inflate_kernel, keeps its name and its arguments.
-template <bool kSeek>
+//
+// kFormResume (zh_resume.hip, ZhResume r): history in front of the slot as above, no stop bit.  At the top of the block
+// loop, and behind the final block, the decode wave hands the output wave a boundary mark (kTailMark); the output wave
+// records (bit, bytes made) when it comes by the mark in round order, so the last record is the last block that was
+// decoded AND written whole.  The end of the input and a full slot are no failures here: they end the stream with that
+// last boundary and the reason (ZH_RESUME_*), the earlier event in stream order deciding -- the output wave's status
+// is raised in round order and outranks the status the decode wave sends with kTailEnd.  Unless r.last[sid] is set,
+// no check is decided by a bit at or beyond the end of the input: a field, a code or a token that the end cuts (a
+// pattern without a code counts as 7 bits in the code-length code, 15 in the others) answers kStNeedInput, and the
+// tokens of a round that the end cuts never reach the output wave.  With r.last[sid] the checks read zeros behind the
+// end and give the statuses of the other forms; a token that the end cuts is kept from the output wave all the same.
+template <int kForm>
 __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_src, uint8_t* __restrict__ d_dst,
-                                                const ZhInflateArgs& a, const ZhSeekStop& x) {
+                                                const ZhInflateArgs& a, const ZhSeekStop& x, const ZhResume& r) {
+  constexpr bool kSeek = kForm == kFormSeek;
+  constexpr bool kResume = kForm == kFormResume;
   __shared__ uint32_t s_lit[(1u << kLitBits) + kLitSub];
   __shared__ uint32_t s_dst[1u << kDistBits];  // also hosts the 7-bit code-length table
   __shared__ uint32_t s_in[kInWords];          // staging ring of the compressed stream
@@ -85,6 +105,9 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
     // =========================== OUTPUT wave ===========================
     KPROF_DECL(8);  // output wave: 0 waiting for a round, 1 working; 2 rounds; 3 waves; 4 long rounds; 5 far rounds; 6 doubling turns; 7 tail matches
     uint64_t op = kSeek ? x.hist_len[sid] : 0;  // bytes produced (kSeek: behind the history the slot came with)
+    if constexpr (kResume) op = r.hist_len[sid];
+    uint64_t mark_bit = 0, mark_op = op;  // kResume: the last block boundary the output has reached
+    uint32_t mark_final = 0;
     int st = ZH_OK;
     // match sources are read back past this CU's L1 (which may hold a stale copy of a line the
     // wave has since extended), after the wave's earlier stores have completed
@@ -140,6 +163,14 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
         break;
       }
       if (st != ZH_OK) continue;  // failed: keep taking rounds until the decode wave stops
+      if constexpr (kResume) {
+        if (tail == kTailMark) {
+          mark_bit = tail_off;
+          mark_op = op;
+          mark_final = tail_a;
+          continue;
+        }
+      }
       // where every token's output goes: prefix sums of the chain's output lengths
       const bool in_chain = (recA >> 10) & 1u, is_lit = (recA >> 9) & 1u;
       const bool in_chainB = (recB >> 10) & 1u, is_litB = (recB >> 9) & 1u;
@@ -273,7 +304,19 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
       if (st != ZH_OK && lane == 0) s_ostatus = st;
     }
     if (st == ZH_OK && op > cap && !count_only) st = ZH_ERR_DST_TOO_SMALL;
-    if (lane == 0) {
+    if constexpr (kResume) {
+      // what was delivered: the bytes behind the history up to the last boundary; why the stream stopped there
+      int why = -1;
+      if (st == ZH_OK && mark_final) why = ZH_RESUME_DONE;
+      else if (st == kStNeedInput) why = ZH_RESUME_NEED_INPUT;
+      else if (st == ZH_ERR_DST_TOO_SMALL) why = ZH_RESUME_NEED_OUTPUT;
+      if (lane == 0) {
+        a.out_len[sid] = mark_op - r.hist_len[sid];
+        a.status[sid] = why >= 0 ? (int)ZH_OK : st == ZH_OK ? (int)ZH_ERR_INVALID_BUFFER : st;
+        r.bit[sid] = mark_bit - (uint64_t)mis * 8;
+        r.why[sid] = why >= 0 ? why : 0;
+      }
+    } else if (lane == 0) {
       a.out_len[sid] = op;
       a.status[sid] = st;
     }
@@ -335,6 +378,10 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
     return v;
   };
   auto past_end = [&]() -> bool { return bp > end * 8; };  // the role of `bitsBuffered < 0`
+  // kResume: the caller promised no more input / a check that needs the bits below `need_bit` cannot be decided yet
+  bool lastf = false;
+  if constexpr (kResume) lastf = r.last[sid] != 0;
+  auto short_of = [&](uint64_t need_bit) -> bool { return kResume && !lastf && need_bit > end * 8; };
   KPROF_DECL(8);  // decode wave: 0 waiting for the output wave, 1 other work; 2 rounds; 3 waves; 4 vector decode; 5 chain walks; 6 staging
   uint32_t rk = 0;  // rounds handed over so far
   int st = ZH_OK;
@@ -366,9 +413,11 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
       if (bp > stop_at) st = ZH_ERR_INVALID_BUFFER;
       break;
     }
+    if constexpr (kResume) send_tail(kTailMark, 0, 0, bp);
     hc = 0;
     need();
     const uint32_t bfinal = take(1), btype = take(2);
+    if (short_of(bp)) { st = kStNeedInput; break; }
     if (bfinal || single_block) final_block = true;
 
     if (btype == 0) {  // inflate.nim:252-266 inflateNoCompression
@@ -376,9 +425,10 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
       hc = 0;
       need();
       const uint32_t len = take(16), nlen = take(16);
+      if (short_of(bp)) { st = kStNeedInput; break; }
       if (len + nlen != 65535u) { st = ZH_ERR_INVALID_BUFFER; break; }
       const uint64_t byte_pos = bp >> 3;  // from asrc
-      if (byte_pos + len > end) { st = ZH_ERR_END_OF_BUFFER; break; }
+      if (byte_pos + len > end) { st = kResume && !lastf ? kStNeedInput : (int)ZH_ERR_END_OF_BUFFER; break; }
       send_tail(kTailStored, len, 0, byte_pos);
       seek((byte_pos + len) * 8);
       continue;
@@ -394,6 +444,7 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
       hlit = take(5) + 257;
       hdist = take(5) + 1;
       const uint32_t hclen = take(4) + 4;
+      if (short_of(bp)) { st = kStNeedInput; break; }
       if (hlit > 286 || hdist > 30) { st = ZH_ERR_INVALID_BUFFER; break; }
       zh_wave_sync();
       if (lane < 20) s_lens[lane] = 0;
@@ -403,6 +454,7 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
         const uint32_t v = take(3);
         if (lane == 0) s_lens[c_clcl_order[i]] = (uint8_t)v;
       }
+      if (short_of(bp)) { st = kStNeedInput; break; }
       st = build_table(s_lens, 19, s_dst, 7, 2, &s_tab_cl, s_val_cl, s_cnt);
       if (st != ZH_OK) break;
       uint32_t i = 0;
@@ -419,7 +471,9 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
           uint32_t nb;
           sym = decode_symbol_slow<true>((uint32_t)hb, 7, &s_tab_cl, s_val_cl, &nb);
           take(nb);
+          if (short_of(bp + 7u)) { st = kStNeedInput; break; }  // (no code among the 7 bits at bp)
         }
+        if (short_of(bp)) { st = kStNeedInput; break; }
         if (past_end()) { st = ZH_ERR_END_OF_BUFFER; break; }
         if (sym <= 15) {
           if (lane == 0) s_lens[i] = (uint8_t)sym;
@@ -428,11 +482,13 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
         } else if (sym == 16) {
           if (i == 0) { st = ZH_ERR_INVALID_BUFFER; break; }
           const uint32_t rep = take(2) + 3;
+          if (short_of(bp)) { st = kStNeedInput; break; }
           if (i + rep > 320) { st = ZH_ERR_INVALID_BUFFER; break; }
           if (lane < rep) s_lens[i + lane] = (uint8_t)prev;
           i += rep;
         } else if (sym == 17 || sym == 18) {
           const uint32_t rep = sym == 17 ? take(3) + 3 : take(7) + 11;
+          if (short_of(bp)) { st = kStNeedInput; break; }
           for (uint32_t j = lane; j < rep && i + j < 320 + 16; j += 64) s_lens[i + j] = 0;
           prev = 0;
           i += rep;
@@ -577,6 +633,17 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
 #ifndef ZH_EMU
       __builtin_amdgcn_s_setprio(0);
 #endif
+      bool cut = false;  // kResume: the end of the input lies inside the chain
+      if constexpr (kResume) {
+        // the tokens that the end of the input cuts, and all behind them, are not the output wave's: they leave the
+        // chain, and the round is the stream's last
+        const uint64_t nbits = end * 8;
+        const uint64_t inA = __ballot(bp + lane + A.tbits <= nbits);
+        const uint64_t inB = __ballot(bp + 64u + lane + B.tbits <= nbits);
+        cut = (chain & ~inA) != 0 || (useB && (chainB & ~inB) != 0);
+        chain &= inA;
+        chainB &= inB;
+      }
       // ---- hand the round over (the output wave works out the offsets) ----
       RoundDesc& d = s_desc[rk & 1u];
       d.rec[0][lane] = A.outlen | (A.is_lit ? 1u << 9 : 0u) | lane_flag(chain, 1u << 10) | (A.val << 16);
@@ -585,7 +652,9 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
       bp += pos;
       bool block_done = false;
       uint32_t tail = kTailNone, tail_a = 0, tail_b = 0;
-      if (pos < 64u || (useB && pos < 128u)) {
+      if (kResume && cut) {
+        st = lastf ? (int)ZH_ERR_END_OF_BUFFER : kStNeedInput;
+      } else if (pos < 64u || (useB && pos < 128u)) {
         // ---- the token at bp stopped the chain: decode it alone (inflate.nim:67-102) ----
         // (the builtin returns int: widen through uint32_t, or the low word sign-extends)
         uint32_t sv_lo, sv_hi, se;
@@ -600,11 +669,13 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
         }
         uint64_t sv = (uint64_t)sv_lo | ((uint64_t)sv_hi << 32);
         uint32_t used;
+        uint32_t nocode = 0;  // kResume: bits a pattern without a code counts as
         if (se == 0) {  // longer than the LUT, or unassigned
           uint32_t nb;
           const uint32_t sym = decode_symbol_slow<true>((uint32_t)sv, kLitBits, &s_tab_lit, s_val_lit, &nb);
           se = litlen_entry(sym, 0);
           used = nb;
+          if (kResume && sym == 0xffffu) nocode = 15u;
         } else {
           used = se & 15u;
         }
@@ -627,6 +698,7 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
           if (sde == 0) {
             const uint32_t dsym = decode_symbol_slow<true>((uint32_t)sv, kDistBits, &s_tab_dist, s_val_dist, &dnb);
             sde = dist_entry(dsym, 0);
+            if (kResume && dsym == 0xffffu) nocode = 15u;
           } else {
             dnb = sde & 15u;
           }
@@ -641,6 +713,11 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
             tail_b = (sde >> 16) + ((uint32_t)sv & ((1u << sdeb) - 1u));
             used += sdeb;
           }
+        }
+        if (short_of(bp + used + nocode)) {  // the end of the input cuts the token: nothing of it counts
+          st = kStNeedInput;
+          tail = kTailNone;
+          block_done = false;
         }
         bp += used;
       }
@@ -662,6 +739,9 @@ __device__ __forceinline__ void zh_inflate_body(const uint8_t* __restrict__ d_sr
     }
   }
   if (kSeek && st == ZH_OK && bp != stop_at) st = ZH_ERR_INVALID_BUFFER;  // (a final block that ends elsewhere)
+  if constexpr (kResume) {
+    if (st == ZH_OK) send_tail(kTailMark, 1, 0, bp);  // behind the final block
+  }
   send_tail(kTailEnd, (uint32_t)st, 0, 0);
   KPROF_COUNT(3, 1);
   KPROF_FLUSH(24, 8);

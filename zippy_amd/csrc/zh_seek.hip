@@ -16,7 +16,7 @@
 __global__ __launch_bounds__(128, 8) void zh_seek_inflate_kernel(const uint8_t* __restrict__ d_src,
                                                               uint8_t* __restrict__ d_dst,
                                                               ZhInflateArgs a, ZhSeekStop x) {
-  zh_inflate_body<true>(d_src, d_dst, a, x);
+  zh_inflate_body<kFormSeek>(d_src, d_dst, a, x, ZhResume{});
 }
 // the intervals of a seek index (history lengths and stop bits beside a.start_bit)
 extern "C" void zh_launch_seek_inflate(hipStream_t stream, const uint8_t* d_src, uint8_t* d_dst, ZhInflateArgs a,

@@ -734,6 +734,33 @@ proc hipUncompressResume*(tail: string, state: var string, consumed: var int, wh
   consumed = used.int
   take(dst, dstLen, if rc != 0: rc else: st.cint)
 
+# ---- streaming compress: a stream fed piece by piece, flushed, finished (no counterpart in the reference) ----
+const ZhFlushBlock* = 0'u8; const ZhFlushSync* = 1'u8; const ZhFlushFinish* = 2'u8
+proc zh_compress_stream_batch(ctx: ZhCtx, srcs: ptr pointer, lens: ptr csize_t, n: csize_t, level, dataFormat: cint,
+                              blockBytes: csize_t, states: ptr pointer, stateLens: ptr csize_t, flush: ptr uint8,
+                              dsts: ptr pointer, dstLens: ptr csize_t, newStates: ptr pointer,
+                              newStateLens: ptr csize_t, statuses: ptr int32): cint {.importc, cdecl, dynlib: zhLib.}
+
+proc hipCompressStream*(piece: string, state: var string, flush = ZhFlushSync, level = DefaultCompression,
+                        dataFormat = dfGzip, blockBytes = 0): string {.raises: [ZippyError].} =
+  ## one step of one stream: `piece` is its next bytes, `state` the state the step before returned ("" for a new stream,
+  ## which takes level, dataFormat and blockBytes -- 0: 4 MiB -- from this call; a step that succeeds replaces it, with ""
+  ## behind ZhFlushFinish, and a step that raises leaves it as it was).  Returns the whole bytes the stream has made since the step before.
+  var p = if piece.len > 0: piece[0].unsafeAddr.pointer else: nil
+  var len = piece.len.csize_t
+  var sp = if state.len > 0: state[0].unsafeAddr.pointer else: nil
+  var slen = state.len.csize_t
+  var fl = flush
+  var dst, ns: pointer; var dstLen, nsLen: csize_t; var st: int32
+  let rc = zh_compress_stream_batch(engine(), p.addr, len.addr, 1, level.cint, dataFormat.cint, blockBytes.csize_t,
+                                    sp.addr, slen.addr, fl.addr, dst.addr, dstLen.addr, ns.addr, nsLen.addr, st.addr)
+  if rc == 0 and st == 0:  # (a failed step leaves the state as it was: the caller may try again with it)
+    var next = newString(nsLen.int)
+    if ns != nil and nsLen > 0: copyMem(next[0].addr, ns, nsLen.int)
+    state = next
+  if ns != nil: zh_free(ns)
+  take(dst, dstLen, if rc != 0: rc else: st.cint)
+
 # ---- any gzip file: several members, FEXTRA / FNAME / FCOMMENT / FHCRC (no counterpart in the reference) ----
 type
   ZhGzipMember* {.bycopy.} = object

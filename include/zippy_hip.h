@@ -687,6 +687,85 @@ int zh_uncompress_resume_batch(zh_ctx *ctx, const void *const *srcs, const size_
                                void **new_states, size_t *new_state_lens, int32_t *why, int32_t *statuses);
 
 /* ------------------------------------------------------------------ *
+ * Streaming compress: streams fed piece by piece, flushed, finished.  *
+ * Host buffers in, library-allocated results out (zh_free); statuses  *
+ * per stream; the return value is ZH_OK unless the call as a whole    *
+ * could not run.                                                      *
+ * ------------------------------------------------------------------ */
+/* The reference runs its matcher once per deflate block, and no match crosses a block start (above: the block-parallel
+ * form).  A stream compressed piece by piece is therefore the bit-concatenation of the pieces' own raw-deflate streams
+ * with BFINAL cleared on all but the last: every byte of it can be held against the reference.  What carries a stream
+ * from one call to the next is this 64-byte little-endian blob (library-allocated, zh_free; the caller keeps it and
+ * hands it back).  No history survives a call: a piece's matches reach no further back than its own first byte. */
+enum { ZH_FLUSH_BLOCK = 0, ZH_FLUSH_SYNC = 1, ZH_FLUSH_FINISH = 2 };
+#define ZH_STREAM_MAGIC "ZHCSTRM1"
+#define ZH_STREAM_VERSION 1u
+typedef struct zh_stream_state { /* 64 bytes, little endian, nothing follows */
+  char magic[8];
+  uint32_t version;     /* 1 */
+  uint32_t data_format; /* ZH_DF_ZLIB, ZH_DF_GZIP or ZH_DF_DEFLATE */
+  int32_t level;        /* fixed at the first call */
+  uint32_t block_bytes; /* fixed at the first call */
+  uint32_t phase;       /* 1: header written, stream open */
+  uint32_t pend_bits;   /* 0..7 bits made but not yet delivered */
+  uint32_t pend_byte;   /* those bits, low first; the rest 0 */
+  uint32_t check;       /* running CRC-32 (gzip) / Adler-32 (zlib) of the input; 0 for raw deflate */
+  uint64_t total_in;    /* input consumed by all calls so far */
+  uint64_t total_out;   /* compressed bytes delivered by all calls so far, header included */
+  uint64_t reserved;    /* 0 */
+} zh_stream_state;
+
+/* WHAT THE BYTES ARE.  The output of calls 1..m of one stream, concatenated, is a bit string (deflate's order: the low
+ * bit of a byte first):
+ *  1. New stream (states[i] NULL; states NULL: all of them): the container header exactly as zh_compress of this
+ *     context writes it for this level and format -- ten bytes of gzip plus the name zh_set_gzip_fname_len asks for and
+ *     its NUL, two bytes of zlib, nothing for raw deflate.  level, data_format and block_bytes (0: 4 MiB) are those of
+ *     the call; a resumed stream takes all three from its state.
+ *  2. Each call with lens[i] > 0, or with ZH_FLUSH_FINISH: the bits [0, end) of
+ *       R = zh_compress_blocks(piece, level, ZH_DF_DEFLATE, block_bytes),
+ *     end being the closing index entry's bit_off, with the BFINAL bit of the last block (the last index entry before
+ *     the closing one) cleared unless the call is ZH_FLUSH_FINISH.  They are placed behind the k = pend_bits pending
+ *     bits as follows; let p be the bit_off of the first STORED block of R (BTYPE 00), if there is one.
+ *       - Without a stored block every bit moves up by k.
+ *       - With one, bits [0, p + 3) move up by k, and zero bits follow up to the next byte boundary of the
+ *         DESTINATION.  Everything from source byte ceil((p + 3) / 8) on (LEN, NLEN, data, all later blocks) follows
+ *         at destination byte ceil((p + k + 3) / 8): a whole-byte move of 0 or 1.
+ *       - A stored block aligns source and destination alike, so every later stored block keeps its own padding:
+ *         there are only ever these two regimes.
+ *  3. ZH_FLUSH_BLOCK with an empty piece: nothing.
+ *  4. ZH_FLUSH_FINISH with an empty piece: the block that zh_compress(empty, level, ZH_DF_DEFLATE) makes
+ *     (01 00 00 ff ff; at HuffmanOnly the coded block 03 00), placed by the same rule.
+ *  5. ZH_FLUSH_SYNC: then three zero bits, zero bits to the byte boundary, and 00 00 FF FF (an empty stored block).
+ *     After it pend_bits is 0, and everything delivered so far decodes to everything fed so far.
+ *  6. ZH_FLUSH_FINISH: zero bits to the byte boundary, then the trailer over the whole input -- gzip: CRC-32 and
+ *     total_in mod 2^32, little endian; zlib: Adler-32, big endian; raw deflate: nothing.  The stream is over:
+ *     new_states[i] is NULL.
+ *  7. Delivery: a call delivers the whole bytes of what exists so far (dsts[i] / dst_lens[i], zh_free; NULL for no
+ *     bytes); the up to 7 bits left over go into the state, not into the output.
+ * Identity: pieces that are multiples of block_bytes fed with ZH_FLUSH_BLOCK, the last piece with ZH_FLUSH_FINISH,
+ * give byte for byte zh_compress_blocks(whole, level, data_format, block_bytes) -- with block_bytes 0 the reference's
+ * own compress(whole): a file larger than memory gets the reference's bytes.  (At level 0 the unit is 65535 bytes: the
+ * reference cuts stored chunks there whatever the block size.)  After zh_set_l1_parse(ctx, 1) R is that mode's
+ * stream: the rule is unchanged and the bytes are valid, but not the reference's.
+ * flush[i] is one of ZH_FLUSH_* (flush NULL: all ZH_FLUSH_SYNC).  One status per stream; statuses[i] != ZH_OK gives
+ * stream i no output and no state and never disturbs its neighbours.  A state that cannot be right -- magic, version,
+ * format, level outside -2..9, block_bytes not a multiple of 32768 in 32768..4194304, phase != 1, pend_bits > 7, bits of
+ * pend_byte at or above pend_bits, reserved != 0, a length other than 64 -- fails its stream with
+ * ZH_ERR_INVALID_BUFFER before anything is uploaded.  ZH_ERR_ARGUMENT for the call: NULL arrays; a NULL source with a
+ * non-zero length; a NULL state with a non-zero length; flush[i] > 2; state_lens without states or states without
+ * state_lens; a bad level, format (ZH_DF_DETECT is not a format to write) or block_bytes when any stream is new.
+ * n == 0 launches nothing.  A call that fails as a whole hands nothing out: every dsts[i] and new_states[i] is NULL.
+ * Streams of one level and block size share a compress plan; scratch is bounded by ZH_SCRATCH_MB, groups of streams
+ * taking turns.  Small pieces pay for it in ratio (every piece starts without history and with codes of its own) and
+ * in speed (a call has a plan's fixed cost): DESIGN.md 4.19 has the measurements. */
+int zh_compress_stream_batch(zh_ctx *ctx, const void *const *srcs, const size_t *lens, size_t n,
+                             int level, int data_format, size_t block_bytes,      /* for new streams; 0 = 4 MiB */
+                             const void *const *states, const size_t *state_lens, /* NULL entry: a new stream */
+                             const uint8_t *flush,                                /* per stream; NULL = all SYNC */
+                             void **dsts, size_t *dst_lens, void **new_states, size_t *new_state_lens,
+                             int32_t *statuses);
+
+/* ------------------------------------------------------------------ *
  * ZIP archives as batch clients of the codec. *
  * Record parsing / assembly of src/zippy/ziparchives.nim on the host, *
  * every entry's deflate stream and CRC-32 in ONE GPU batch.  The file *

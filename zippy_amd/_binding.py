@@ -132,6 +132,11 @@ _SIGS = {
                                               _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t),
                                               _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32),
                                               _c.POINTER(_c.c_int32)]),
+    "zh_compress_stream_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
+                                            _c.c_int, _c.c_int, _c.c_size_t, _c.POINTER(_c.c_void_p),
+                                            _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_uint8),
+                                            _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_void_p),
+                                            _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int32)]),
     "zh_crc32_batch": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t), _c.c_size_t,
                                   _c.POINTER(_c.c_uint32)]),
     "zh_compress_batch_crc32": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_size_t),
@@ -1119,6 +1124,47 @@ class Engine:
                     self.lib.zh_free(ns[i])
         self._check(rc)
         return outs, list(used)[:n], new_states, list(why)[:n], list(sts)[:n]
+
+    # ---- streaming compress ----
+    def compress_stream_batch(self, srcs, states=None, flush=None, level=DefaultCompression, dataFormat=dfGzip,
+                              block_bytes=0):
+        """One step of every stream (zh_compress_stream_batch): srcs[i] is the next piece of stream i, states[i] the state
+        the step before returned (None: a new stream; states None: all new), flush None (all FLUSH_SYNC), one number, or
+        one FLUSH_* a stream.  level, dataFormat and block_bytes (0: 4 MiB) are those of new streams; a resumed stream
+        keeps its own.
+        -> (outputs, new_states, statuses); an output is b"" and a state None where nothing came."""
+        n = len(srcs)
+        m = max(1, n)
+        keep = [bytes(b) for b in srcs]
+        blobs = [bytes(b) if b is not None else None for b in (states if states is not None else [None] * n)]
+        if len(blobs) != n:
+            raise ValueError("states: one per stream")
+        modes = None if flush is None else list(flush) if hasattr(flush, "__len__") else [flush] * n
+        if modes is not None and len(modes) != n:
+            raise ValueError("flush: one per stream")
+        ptrs = (_c.c_void_p * m)(*[_c.cast(_c.c_char_p(k), _c.c_void_p) for k in keep])
+        lens = (_c.c_size_t * m)(*[len(k) for k in keep])
+        sp = (_c.c_void_p * m)(*[_c.cast(_c.c_char_p(b), _c.c_void_p) if b is not None else None for b in blobs])
+        sl = (_c.c_size_t * m)(*[len(b) if b is not None else 0 for b in blobs])
+        fl = (_c.c_uint8 * m)(*[int(f) & 0xff for f in modes]) if modes is not None else None
+        dsts, dlens = (_c.c_void_p * m)(), (_c.c_size_t * m)()
+        ns, nsl, sts = (_c.c_void_p * m)(), (_c.c_size_t * m)(), (_c.c_int32 * m)()
+        rc = self.lib.zh_compress_stream_batch(self._h, ptrs, lens, n, int(level), int(dataFormat), int(block_bytes),
+                                               sp if states is not None else None, sl if states is not None else None,
+                                               fl, dsts, dlens, ns, nsl, sts)
+        outs, new_states = [], []
+        try:
+            for i in range(n):
+                outs.append(_c.string_at(dsts[i], dlens[i]) if dsts[i] else b"")
+                new_states.append(_c.string_at(ns[i], nsl[i]) if ns[i] else None)
+        finally:
+            for i in range(n):
+                if dsts[i]:
+                    self.lib.zh_free(dsts[i])
+                if ns[i]:
+                    self.lib.zh_free(ns[i])
+        self._check(rc)
+        return outs, new_states, list(sts)[:n]
 
     def crc32(self, src):
         src = bytes(src)

@@ -236,6 +236,60 @@ def uncompress_chunks(chunks, dataFormat=dfDetect, max_out=1 << 20):
         yield out
 
 
+FLUSH_BLOCK, FLUSH_SYNC, FLUSH_FINISH = 0, 1, 2
+
+
+def compress_stream_batch(srcs, states=None, flush=None, level=DefaultCompression, dataFormat=dfGzip, block_bytes=0):
+    """One step of many streams that are compressed piece by piece (zlib, gzip, raw), in one call: every stream's piece
+    becomes whole deflate blocks of its own, placed bit-exactly behind what the stream has made so far.  srcs[i]: the
+    next piece of stream i; states[i]: the state its step before returned (None: a new stream, which takes level,
+    dataFormat and block_bytes -- 0: 4 MiB -- from this call); flush[i]: FLUSH_BLOCK (the blocks, up to 7 bits held
+    back), FLUSH_SYNC (the default: then an empty stored block, so that all that was fed decodes from all that was
+    delivered), FLUSH_FINISH (the last block and the trailer; no state comes back).
+    -> (outputs, new_states, statuses)."""
+    return engine().compress_stream_batch(srcs, states, flush, level, dataFormat, block_bytes)
+
+
+class Deflater:
+    """One stream compressed as its bytes arrive: feed(piece) -> the compressed bytes so far, finish() -> the rest with
+    the trailer.  Pieces that are multiples of block_bytes fed with FLUSH_BLOCK and finished give compress()'s own bytes
+    (block_bytes 0) or compress_blocks()'s; any other cut gives a valid stream of the same data.  A piece starts without
+    history: small pieces cost ratio.  Raises ZippyError where a call fails."""
+
+    def __init__(self, level=DefaultCompression, dataFormat=dfGzip, block_bytes=0):
+        self.level, self.fmt, self.block_bytes = level, dataFormat, block_bytes
+        self.state, self.started, self.done = None, False, False
+
+    def feed(self, piece, flush=FLUSH_SYNC):
+        if self.done:
+            raise ValueError("the stream is finished")
+        eng = engine()
+        outs, states, sts = eng.compress_stream_batch([piece], [self.state] if self.started else None, [flush],
+                                                      self.level, self.fmt, self.block_bytes)
+        eng._raise_first(outs, sts)
+        self.state, self.started, self.done = states[0], True, flush == FLUSH_FINISH
+        return outs[0]
+
+    def finish(self, piece=b""):
+        return self.feed(piece, FLUSH_FINISH)
+
+
+def compress_chunks(chunks, level=DefaultCompression, dataFormat=dfGzip, block_bytes=0, flush=FLUSH_SYNC):
+    """compress() of data that comes as an iterable of byte pieces: yields the stream as it is made, every piece flushed
+    with `flush`, the last one finished; the twin of uncompress_chunks."""
+    d = Deflater(level, dataFormat, block_bytes)
+    held = None
+    for chunk in chunks:
+        if held is not None:
+            out = d.feed(held, flush)
+            if out:
+                yield out
+        held = chunk
+    out = d.finish(held if held is not None else b"")
+    if out:
+        yield out
+
+
 def openZipArchive(image):
     """ziparchives.nim:183 openZipArchive on the bytes of an archive -> reader with walk_files(),
     extract_file(path), extract_batch(indices)."""

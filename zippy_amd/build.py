@@ -16,7 +16,7 @@ OBJDIR = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libzippy_hip.so")
 SOURCES = ["zh_context.hip", "zh_plan_compress.hip", "zh_plan_uncompress.hip", "zh_plan_run.hip", "zh_plan_pack.hip", "zh_host_batch.hip", "zh_host_calls.hip", "zh_checksum.hip", "zh_inflate.hip", "zh_inflate_split.hip", "zh_inflate_seg.hip", "zh_l1_match.hip", "zh_l1p_match.hip",
            "zh_chain_match.hip", "zh_huffman.hip", "zh_emit.hip", "zh_zip.hip", "zh_tar.hip", "zh_tar_create.hip", "zh_zip_write.hip", "zh_tar_open_batch.hip",
-           "zh_zip_open_batch.hip", "zh_zip_read_batch.hip", "zh_tar_read_batch.hip", "zh_ranges.hip", "zh_bgzf.hip", "zh_seek.hip", "zh_gzip.hip", "zh_resume.hip"]
+           "zh_zip_open_batch.hip", "zh_zip_read_batch.hip", "zh_tar_read_batch.hip", "zh_ranges.hip", "zh_bgzf.hip", "zh_seek.hip", "zh_gzip.hip", "zh_resume.hip", "zh_stream.hip"]
 HEADERS = ["zh_common.h", "zh_host.h", "zh_tables.h", "zh_kprof.h", "zh_inflate_tables.h", "zh_inflate_header.h", "zh_inflate_pair.h", "zh_walk.h", "zh_scan.h", "zh_range_host.h", "zh_gather.h", "zh_zip_reader.h", "zh_zip_dev.h", "zh_tar_dev.h", os.path.join("..", "..", "include", "zippy_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=default",

@@ -1,5 +1,5 @@
 // Host side of the C ABI, shared declarations (not installed: include/zippy_hip.h is the public header).
-// The host side lives in seventeen files -- zh_context.hip (contexts, the device block cache, bounds),
+// The host side lives in eighteen files -- zh_context.hip (contexts, the device block cache, bounds),
 // zh_plan_compress.hip / zh_plan_uncompress.hip (device-resident plans: descriptors and scratch),
 // zh_plan_run.hip (kernel sequencing -- run_compress, run_uncompress with run_segmented, run_ranges; work beside a run
 // on the context's second stream: SideLane --, switches, results), zh_plan_pack.hip (a plan's streams back to back for the
@@ -7,7 +7,8 @@
 // zh_host_calls.hip (single-buffer calls, the block-parallel form, checksums, debug hooks), zh_ranges.hip (byte-range
 // reads from block-indexed streams: geometry, host call and its two kernels), zh_seek.hip (seek indexes for foreign
 // streams: build, range reads and their kernels), zh_resume.hip (resumable uncompress: the host call and the resuming
-// form of the wave-pair kernel), the batch writers
+// form of the wave-pair kernel), zh_stream.hip (streaming compress: the host call and the two kernels that splice a
+// piece's stream behind the bits pending from the call before), the batch writers
 // zh_zip_write.hip / zh_tar_create.hip and the batch readers zh_tar_open_batch.hip / zh_tar_read_batch.hip /
 // zh_zip_open_batch.hip / zh_zip_read_batch.hip (whose kernels sit next to their host code; zh_walk.h holds the walk
 // all four share, zh_scan.h the signature scan of zh_zip_read_batch.hip and zh_bgzf.hip with its host driver,
